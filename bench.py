@@ -4,13 +4,18 @@
 120k-point SemanticKITTI-like scan (BASELINE.json config C3: d=3, sigma 0.9, capacity 100000,
 V=F=32, fp32).
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One process per GPU; independent clouds are sharded across ranks (weak scaling, no data-path
 collective).  RCCL is used only to broadcast the filter bank once and to reduce timings /
 checksums.  Rank 0 prints ONE JSON line.  Inputs are resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every secondary
+figure and check: graph replays against the eager step, the run without pre-warm, one-pass latency,
+per-kernel rooflines, stages, the CPU baselines, the whole-network step, the copy ceiling and the
+per-operator table.  --dump-outputs DIR writes what rank 0's last timed step computed as .npy files.
 """
 from __future__ import annotations
 
@@ -50,6 +55,32 @@ WORKLOADS = {
 }
 
 FINAL_LINE_LIMIT = 4096  # bytes: the driver keeps only the tail of stdout, so the LAST line must stay far below that
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes of .npy data in all
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BYTES, seed: int = 0) -> dict:
+    """Writes every array as out_dir/<name>.npy in float32 (float64 stays float64).  If the arrays hold more than `budget` bytes
+    together, each array of more than one row keeps a seeded sample of its rows instead (the same rows in every run with the same
+    shapes), in ascending order, and the sampled row numbers go to <name>_rows.npy (float64), so that the files stay within
+    `budget`.  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(a, np.float64 if np.asarray(a).dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    sampled = lambda a: a.ndim > 0 and a.shape[0] > 1
+    frac = 1.0
+    if sum(a.nbytes for a in arrays.values()) > budget:  # every sampled row also costs 8 bytes of row number
+        fixed = sum(a.nbytes for a in arrays.values() if not sampled(a))
+        frac = max(budget - fixed, 0) / sum(a.nbytes + 8 * a.shape[0] for a in arrays.values() if sampled(a))
+    written = {}
+    for name, a in arrays.items():
+        if frac < 1.0 and sampled(a):
+            k = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows"] = (k,)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = a.shape
+    return written
 
 
 def _pick(src, keys):
@@ -407,7 +438,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000,
                     help="timed steps (scans).  The timed region has a fixed cost of ~0.3 ms (first graph launch, drain of the last scans in "
-                         "flight, the final synchronize): it is 0.3 % of 2000 steps and 14 % of 20")
+                         "flight, the final synchronize): it is 0.3 %% of 2000 steps and 14 %% of 20")
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--prewarm-ms", type=float, default=60.0,
                     help="untimed replays for this long BEFORE the W warm-up steps, so that W + K short steps run at the clocks of a busy GPU "
@@ -450,7 +481,18 @@ def main():
                          "once for the batch; value counts all points.  0 = the workload's default (C2: 8, others: 1)")
     ap.add_argument("--row-slack", type=float, default=0.06,
                     help="graph mode: static row bound = largest vertex count of the calibration clouds x (1 + slack), rounded up to 256")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary figure and check (off: set-up, warm-up, the K timed steps and the line only): graph replays "
+                         "compared with the eager step, value_no_prewarm, latency, roofline / roofline_others, stages, the CPU baselines "
+                         "(--cpu-seconds), the whole-network step (--full-unet), the copy ceiling and the per-operator table (--ops-table); "
+                         "--extras 0 drops latency, roofline_others, stages, the whole-network step, the copy ceiling and the table again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last timed step computed as DIR/<name>.npy (float32): out = slice output "
+                         "[points, F], grad_lattice_values = gradient of the lattice values [vertices, V] with rows in ascending lattice-key "
+                         f"order, grad_filter = filter gradient [9 V, F]; at most {DUMP_BYTES >> 20} MB in all (a seeded row sample beyond)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "ops":
+        ap.error("--dump-outputs needs a workload with a timed path (not ops)")
 
     from lattice_net_amd import sharding
     world, rank, local_rank = sharding.env_world()
@@ -558,14 +600,15 @@ def main():
                 c["state"].clear()
 
         def capture(self):
-            """Eager reference result of every pool cloud, then CapturedStep: row bound + kd planes from the calibration clouds,
-            warm-up, one hipGraph per pool cloud."""
+            """Eager step of every pool cloud (its vertex count; with --full its result, the reference of check()), then
+            CapturedStep: row bound + kd planes from the calibration clouds, warm-up, one hipGraph per pool cloud."""
             for c in self.clouds:
                 self.step_on(c)()
                 torch.cuda.synchronize()
                 c["m_real"] = c["state"]["m"]
-                c["eager_out"] = c["state"]["out"].detach().clone()
-                c["eager_gw"] = c["state"]["gw"].detach().clone()
+                if args.full:
+                    c["eager_out"] = c["state"]["out"].detach().clone()
+                    c["eager_gw"] = c["state"]["gw"].detach().clone()
             steps = [self.step_on(c) for c in self.clouds]
             self.cap = CapturedStep(steps[0], [self.lat], row_slack=args.row_slack, regions=bool(args.regions),
                                     region_indices=lambda: self.calibration[0]["state"]["idx"], stream=self.stream,
@@ -579,8 +622,10 @@ def main():
                 self.cap.launch(i % pool)
 
         def check(self):
-            """Last replayed build inside its bounds; the replayed result of EVERY pool cloud equal to its eager step's."""
+            """Last replayed build inside its bounds; with --full, the replayed result of EVERY pool cloud equal to its eager step's."""
             self.cap.check()  # raises if the last replayed build overflowed its row bound or a bucket
+            if not args.full:
+                return None
             worst = {"out_max_rel": 0.0, "grad_filter_max_rel": 0.0}
             for c in self.clouds:
                 st = c["state"]
@@ -608,10 +653,11 @@ def main():
         for i in range(pool * in_flight):  # validation replays (untimed): every captured graph once ...
             sets[i % in_flight].launch(i // in_flight)
         barrier()
-        errs = [cs.check() for cs in sets]  # ... compared with the eager results before anything is timed
-        graph_err = {k: max(er[k] for er in errs) for k in errs[0]}
+        errs = [cs.check() for cs in sets]  # ... inside their row bounds and, with --full, compared with the eager results before anything is timed
+        if args.full:
+            graph_err = {k: max(er[k] for er in errs) for k in errs[0]}
     value_no_prewarm = None
-    if args.prewarm_ms > 0 and graph_mode:  # the same W + K steps ONCE before the pre-warm (the driver's command on a chip that idled through set-up)
+    if args.full and args.prewarm_ms > 0 and graph_mode:  # the same W + K steps ONCE before the pre-warm (the driver's command on a chip that idled through set-up)
         for i in range(max(args.warmup, in_flight)):
             sets[i % in_flight].launch(i // in_flight)
         barrier()
@@ -640,13 +686,24 @@ def main():
     if graph_mode:
         for cs in sets:
             cs.check()
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on scan set (K - 1) % in_flight, cloud (K - 1) // in_flight of its pool, and was that set's last build
+        last = args.steps - 1
+        cs_last = sets[last % in_flight]
+        st = cs_last.clouds[(last // in_flight) % pool]["state"]
+        m_last = cs_last.cap.check()[0] if graph_mode else st["m"]
+        keys = cs_last.lat.m_hash_table.m_keys_tensor[:m_last].cpu().numpy()
+        by_key = np.lexsort(keys.T[::-1])  # row numbering is the build's own; lattice keys name the vertices in every build
+        dump_outputs(args.dump_outputs, {"out": st["out"].detach().float().cpu().numpy(),
+                                         "grad_lattice_values": st["gv"][:m_last].float().cpu().numpy()[by_key],
+                                         "grad_filter": st["gw"].float().cpu().numpy()})
     checksum_local = sum(float(c["state"]["out"].double().abs().sum().item()) for cs in sets for c in cs.clouds if "out" in c["state"])
     m_all = [[c.get("m_real", c["state"].get("m")) for c in cs.clouds] for cs in sets]
     min_elapsed, max_elapsed = sharding.min_max_over_ranks(dist, elapsed, dev)
     checksum = sharding.gather_sum(dist, checksum_local, dev)
     cs0 = sets[0]
     m = int(np.mean([x for x in m_all[0] if x]))  # vertices of a typical scan (the algorithmic byte counts below use it)
-    extras = bool(args.extras) and rank == 0
+    extras = args.full and bool(args.extras) and rank == 0
 
     # ---- latency of ONE scan (wall time of one pass, hipEvent pairs, median): the same graphs, one scan at a time
     latency = None
@@ -739,7 +796,7 @@ def main():
                           (f"; avg_us_in_flight: while the other {in_flight - 1} scans replay their graphs back to back" if loaded else "")}
 
     roofline, others = None, []
-    if rank == 0:
+    if rank == 0 and args.full:
         for _ in range(3):
             eager_step()
         torch.cuda.synchronize()
@@ -862,7 +919,7 @@ def main():
     if rank == 0:
         value = n * world * args.steps / max_elapsed / 1e6
         cpu = cpu1 = None
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             # the CPU fallback with torch.set_num_threads(1) and with all cores.  index_add_ / scatter on many threads
             # contend (128 threads are SLOWER than one on this chain), so a 16-thread leg is timed too and `cpu_baseline` is the
             # fastest of the multi-threaded legs; `cpu_baseline_1thread` is always reported beside it.

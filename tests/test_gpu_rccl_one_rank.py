@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -155,13 +156,14 @@ def test_many_rank_bench_control_flow_on_one_host(ranks):
 
 
 def test_driver_command_prints_a_short_parseable_last_line():
-    """The driver's exact command (`python3 bench.py --gpus 1 --steps 20 --warmup 5`, every secondary leg on): the LAST stdout line
+    """The driver's command with every secondary leg on (`python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`): the LAST stdout line
     is under 4 KB, parses, and carries the headline, `roofline`, `cpu_baseline` and `config.workload`; the per-operator table and
     the other secondary figures are on the `DETAILS ` line in front of it and in bench_details.json."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LATTICE_FORCE_DIST"):
         env.pop(k, None)
-    line, full = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], env, details=True)
+    line, full = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], env,
+                             details=True)
     assert line["metric"].startswith("Mpoints/sec") and line["unit"] == "Mpoints/s" and line["n_gpus"] == 1
     assert line["steps"] == 20 and line["warmup"] == 5 and line["value"] > 100.0 and line["vs_baseline"] is None
     assert abs(line["value"] - 120000 / (line["ms_per_step"] * 1e3)) <= 0.01 * line["value"]
@@ -174,3 +176,26 @@ def test_driver_command_prints_a_short_parseable_last_line():
     assert "ops" in full and "stages" in full and "roofline_others" in full
     with open(os.path.join(ROOT, line["details_file"])) as fh:
         assert json.load(fh)["value"] == line["value"]
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the line holds the headline and no secondary leg,
+    and DIR holds what the last timed step computed (one scan, one cloud: its slice output is what the checksum sums)."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LATTICE_FORCE_DIST"):
+        env.pop(k, None)
+    out_dir = tmp_path / "outputs"
+    line, full = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--in-flight", "1",
+                              "--pool", "1", "--dump-outputs", str(out_dir)], env, details=True)
+    assert line["steps"] == 12 and line["warmup"] == 3 and line["value"] > 0
+    assert abs(line["value"] - 120000 / (line["ms_per_step"] * 1e3)) <= 0.01 * line["value"]
+    for k in ("roofline", "cpu_baseline", "latency", "stages", "full_unet", "ops", "hbm_copy_ceiling", "value_no_prewarm"):
+        assert full[k] is None, k
+    assert full["roofline_others"] == []
+    out = np.load(out_dir / "out.npy")
+    gv = np.load(out_dir / "grad_lattice_values.npy")
+    gw = np.load(out_dir / "grad_filter.npy")
+    assert out.dtype == gv.dtype == gw.dtype == np.float32
+    assert out.shape == (120000, 32) and gv.shape == (full["config"]["vertices"], 32) and gw.shape == (9 * 32, 32)
+    assert abs(np.abs(out.astype(np.float64)).sum() - full["config"]["checksum"]) <= 1e-6 * full["config"]["checksum"]
+    assert np.isfinite(gv).all() and np.abs(gv).max() > 0 and np.isfinite(gw).all() and np.abs(gw).max() > 0

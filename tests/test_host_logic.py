@@ -204,6 +204,30 @@ def test_bench_final_line_is_short_whatever_the_details_hold():
     assert line["roofline"]["traffic"] is None and line["cpu_baseline"] is None and len(json.dumps(line)) < 2048
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 files as they are while they fit; beyond the budget the same seeded rows in every
+    run, with their row numbers beside them, and the files together within the budget."""
+    import os
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"out": rng.standard_normal((1000, 8)).astype(np.float16), "grad_filter": rng.standard_normal((18, 8)).astype(np.float32)}
+    small = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert small == {"out": (1000, 8), "grad_filter": (18, 8)}
+    got = np.load(tmp_path / "a" / "out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, arrays["out"].astype(np.float32))
+    budget = 12000
+    for run in ("b", "c"):
+        written = bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["grad_filter.npy", "grad_filter_rows.npy", "out.npy", "out_rows.npy"]
+        data_bytes = sum(np.load(tmp_path / run / f).nbytes for f in files)
+        assert data_bytes <= budget
+    rows = np.load(tmp_path / "b" / "out_rows.npy")
+    assert rows.dtype == np.float64 and written["out"] == (rows.size, 8) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "out_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "out.npy"), arrays["out"][rows.astype(np.int64)].astype(np.float32))
+
+
 def test_launch_thread_pinning_cuts_the_allowed_cores_into_rank_slices():
     import os
     from lattice_net_amd import sharding
@@ -219,11 +243,14 @@ def test_launch_thread_pinning_cuts_the_allowed_cores_into_rank_slices():
     assert (lo, hi) == (2.5, 2.5)
 
 
-def test_launch_thread_pinning_follows_the_numa_node_of_the_ranks_gpu(tmp_path):
+def test_launch_thread_pinning_follows_the_numa_node_of_the_ranks_gpu(tmp_path, monkeypatch):
     """sharding.pin_launch_thread with a sysfs that names the GPUs' NUMA nodes (a fake tree): two GPUs on node 1, one on node 0; the
     ranks of node 1 share its cores, the rank of node 0 gets all of node 0's; devices of other vendors / classes are ignored."""
     import os
     from lattice_net_amd import sharding
+    # every GPU of the fake tree is visible: a device subset handed to the calling job would remap the ranks onto other GPUs
+    for k in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "LATTICE_NO_AFFINITY"):
+        monkeypatch.delenv(k, raising=False)
     have = sorted(os.sched_getaffinity(0))
     if len(have) < 6:
         pytest.skip("needs six cores")

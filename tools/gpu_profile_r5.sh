@@ -47,11 +47,11 @@ pmc clock_ops "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES" python3 $ROOT/tools/ops_roofline.
 cd $ROOT
 # the bench lines of every workload, unprofiled (the compact last line + the DETAILS line)
 for W in C3 C2 C4 C5; do
-  python3 bench.py --workload $W --cpu-seconds 4 > $OUT/bench_$W.log 2>$OUT/bench_$W.err
+  python3 bench.py --workload $W --cpu-seconds 4 --full > $OUT/bench_$W.log 2>$OUT/bench_$W.err
   grep -h "^{\"metric\"" $OUT/bench_$W.log | tail -1 > $OUT/bench_${W}_line.json
   grep -h "^DETAILS " $OUT/bench_$W.log | tail -1 | cut -c9- > $OUT/bench_${W}_details.json
 done
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.log 2>$OUT/bench_driver.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.log 2>$OUT/bench_driver.err
 grep -h "^{\"metric\"" $OUT/bench_driver.log | tail -1 > $OUT/bench_driver_line.json
 grep -h "^DETAILS " $OUT/bench_driver.log | tail -1 | cut -c9- > $OUT/bench_driver_details.json
 python3 tools/conv_time.py > $OUT/conv_time.txt 2>&1

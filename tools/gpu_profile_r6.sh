@@ -36,11 +36,11 @@ stats lnn_scannet python3 $ROOT/tools/bench_lnn.py --config scannet --steps 6 --
 stats lnn_shapenet python3 $ROOT/tools/bench_lnn.py --config shapenet --steps 10 --warmup 3
 cd $ROOT
 for W in C3 C2 C4 C5; do
-  python3 bench.py --workload $W --cpu-seconds 4 > $OUT/bench_$W.log 2>$OUT/bench_$W.err
+  python3 bench.py --workload $W --cpu-seconds 4 --full > $OUT/bench_$W.log 2>$OUT/bench_$W.err
   grep -h "^{\"metric\"" $OUT/bench_$W.log | tail -1 > $OUT/bench_${W}_line.json
   grep -h "^DETAILS " $OUT/bench_$W.log | tail -1 | cut -c9- > $OUT/bench_${W}_details.json
 done
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.log 2>$OUT/bench_driver.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.log 2>$OUT/bench_driver.err
 grep -h "^{\"metric\"" $OUT/bench_driver.log | tail -1 > $OUT/bench_driver_line.json
 grep -h "^DETAILS " $OUT/bench_driver.log | tail -1 | cut -c9- > $OUT/bench_driver_details.json
 for t in kitti scannet shapenet; do python3 tools/bench_lnn.py --config $t --graph --steps 12 --warmup 4 2>&1 | tail -1; done > $OUT/lnn_graph_steps.txt

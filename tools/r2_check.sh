@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/r2_check
 rm -rf $OUT; mkdir -p $OUT
 for cfg in "graph2:--mode graph --in-flight 2" "graph1:--mode graph --in-flight 1" "eager:--mode eager" "graph4:--mode graph --in-flight 4"; do
   name=${cfg%%:*}; flags=${cfg#*:}
-  timeout 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 0 --full-unet 0 $flags > $OUT/bench_$name.log 2>&1
+  timeout 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 0 --full-unet 0 --full $flags > $OUT/bench_$name.log 2>&1
   echo "bench $name rc=$?"
   grep "^{" $OUT/bench_$name.log | tail -1 | python3 -c "
 import json,sys
