@@ -294,6 +294,71 @@ struct LnReduceArgs {
     int deterministic;  // LnCsr.dense & 2: one lane group per ROW, tokens in CSR order, no atomics (run-to-run identical sums)
 };
 
+// The entries beg .. end-1 of one segment, row chunk c, summed into acc: batches of 4 tokens {4 ids} -> {4 weights, 4 row chunks}.
+// No branch per entry (round 6): the entries of the last, partly filled batch re-read the segment's last entry with weight 0, and an id
+// of -1 (left behind by an overflowed build) reads row 0 with weight 0 — the 4 ids, then the 4 weights and 4 row chunks go out back to
+// back instead of each behind its own exec-mask test.  0 * Inf is NaN, though: an Inf on the re-read last entry (an fp16 slice backward
+// that overflowed under a scaled loss) or on row 0 would turn a row's +-Inf, or an unrelated row, into NaN.  SAFE: such entries also
+// select 0 for their row chunk, an exact zero term.  That select costs the C3 reduce 6 % (every C3 batch is a last batch: 2.6 tokens
+// per vertex), so ln_reduce_chunk runs SAFE only for a segment whose plain sum came out NaN.
+template <int VEC, bool HALF, bool SAFE>
+__device__ __forceinline__ void ln_reduce_entries(float (&acc)[VEC], int beg, int end, int c, const int* __restrict__ csr_tok,
+                                                  const float* __restrict__ w, const void* src_v, int src_div, int src_stride, bool pow2,
+                                                  int shift) {
+    const float* __restrict__ src = static_cast<const float*>(src_v);
+    const _Float16* __restrict__ src16 = static_cast<const _Float16*>(src_v);
+    constexpr int U = 4;
+    for (int e0 = beg; e0 < end; e0 += U) {
+        int tk[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ok[u] = e0 + u < end;
+            tk[u] = csr_tok[min(e0 + u, end - 1)];
+        }
+        float wt[U];
+        float x[U][VEC];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const bool valid = ok[u] && tk[u] >= 0;
+            const int t = max(tk[u], 0);
+            const float wl = w[t];
+            wt[u] = valid ? wl : 0.f;
+            {
+                const int srow = pow2 ? (t >> shift) : (t / src_div);
+                const size_t off = (size_t)srow * src_stride + c * VEC;
+                if constexpr (HALF) {
+                    if constexpr (VEC == 8) {  // 16-byte words: a 64-channel fp16 row on 8 lanes, 8 segments per wave
+                        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+                        const h8 v8 = *reinterpret_cast<const h8*>(src16 + off);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) x[u][k] = (float)v8[k];
+                    } else if constexpr (VEC == 4) {
+                        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+                        const h4 v4 = *reinterpret_cast<const h4*>(src16 + off);
+                        x[u][0] = (float)v4[0]; x[u][1] = (float)v4[1]; x[u][2] = (float)v4[2]; x[u][3] = (float)v4[3];
+                    } else {
+                        x[u][0] = (float)src16[off];
+                    }
+                } else if constexpr (VEC == 4) {
+                    const float4 v4 = *reinterpret_cast<const float4*>(src + off);
+                    x[u][0] = v4.x; x[u][1] = v4.y; x[u][2] = v4.z; x[u][3] = v4.w;
+                } else {
+                    x[u][0] = src[off];
+                }
+            }
+            if constexpr (SAFE) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) x[u][k] = valid ? x[u][k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) acc[k] = fmaf(x[u][k], wt[u], acc[k]);
+    }
+}
+
 // one block of segments (256 threads).  Per segment: descriptor -> row -> batches of 4 tokens {4 ids} -> {4 weights, 4 row chunks}.
 // Measured on MI355X (C3, 17.5 us): the kernel is insensitive to the length of this dependency chain — prefetching the next
 // batch's ids with the current gathers (6 trips instead of 10): 18.4 us; all 16 ids + 8 gathers in flight (4 trips, 128
@@ -308,12 +373,9 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
     const int* __restrict__ csr_tok = a.csr_tok;
     const int4* __restrict__ seg_desc = a.seg_desc;
     const int* __restrict__ grp_row = a.grp_row;
-    const float* __restrict__ src = static_cast<const float*>(a.src);
-    const _Float16* __restrict__ src16 = static_cast<const _Float16*>(a.src);
     const float* __restrict__ w = a.w;
     float* __restrict__ dst = a.dst;
     const int chunks = L8 ? L8 : a.chunks, lanes_per_seg = L8 ? L8 : a.lanes_per_seg, src_div = a.src_div, src_stride = a.src_stride;
-    constexpr int U = 4;
     const int lc = so.lane_in_seg;
     const int lane = threadIdx.x & 63;
     const int grp_in_wave = lane / lanes_per_seg;
@@ -350,53 +412,14 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
         if (cok) {
-            for (int e0 = beg; e0 < end; e0 += U) {
-                // No branch per entry (round 6): the entries of the last, partly filled batch re-read the segment's last entry with
-                // weight 0 (a row that is summed anyway), and an id of -1 (left behind by an overflowed build) reads row 0 with weight 0 —
-                // the 4 ids, then the 4 weights and 4 row chunks go out back to back instead of each behind its own exec-mask test.
-                int tk[U];
-                bool ok[U];
+            ln_reduce_entries<VEC, HALF, false>(acc, beg, end, c, csr_tok, w, a.src, src_div, src_stride, pow2, shift);
+            bool nan = false;
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    ok[u] = e0 + u < end;
-                    tk[u] = csr_tok[min(e0 + u, end - 1)];
-                }
-                float wt[U];
-                float x[U][VEC];
+            for (int k = 0; k < VEC; ++k) nan |= acc[k] != acc[k];
+            if (nan) {  // a NaN or an Inf in the segment's rows: again, with the padding and the -1 ids selected out (rare: off the hot path)
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const bool valid = ok[u] && tk[u] >= 0;
-                    const int t = max(tk[u], 0);
-                    const float wl = w[t];
-                    wt[u] = valid ? wl : 0.f;
-                    {
-                        const int srow = pow2 ? (t >> shift) : (t / src_div);
-                        const size_t off = (size_t)srow * src_stride + c * VEC;
-                        if constexpr (HALF) {
-                            if constexpr (VEC == 8) {  // 16-byte words: a 64-channel fp16 row on 8 lanes, 8 segments per wave
-                                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-                                const h8 v8 = *reinterpret_cast<const h8*>(src16 + off);
-#pragma unroll
-                                for (int k = 0; k < 8; ++k) x[u][k] = (float)v8[k];
-                            } else if constexpr (VEC == 4) {
-                                typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                                const h4 v4 = *reinterpret_cast<const h4*>(src16 + off);
-                                x[u][0] = (float)v4[0]; x[u][1] = (float)v4[1]; x[u][2] = (float)v4[2]; x[u][3] = (float)v4[3];
-                            } else {
-                                x[u][0] = (float)src16[off];
-                            }
-                        } else if constexpr (VEC == 4) {
-                            const float4 v4 = *reinterpret_cast<const float4*>(src + off);
-                            x[u][0] = v4.x; x[u][1] = v4.y; x[u][2] = v4.z; x[u][3] = v4.w;
-                        } else {
-                            x[u][0] = src[off];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) acc[k] = fmaf(x[u][k], wt[u], acc[k]);
+                for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+                ln_reduce_entries<VEC, HALF, true>(acc, beg, end, c, csr_tok, w, a.src, src_div, src_stride, pow2, shift);
             }
         }
         // segmented suffix reduction over the lane groups of this wave (runs of equal group id are contiguous)

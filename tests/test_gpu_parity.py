@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import lattice_oracle as O
+from tests.test_gpu_segment_reduce import assert_reduce_close, row_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -174,6 +175,17 @@ def test_f5_distribute(golden):
     assert lat.pos_dim() == 3 and lat.val_dim() == 2
 
 
+def assert_slice_classify_value_gradient(gv, grad_logits, values, delta_w, lin_w, lin_b, idx, w):
+    """The lattice-value gradient element by element against the oracle: the C-term dot product in front of the segment reduce, the
+    reduce (tests/test_gpu_segment_reduce.py), and the fp32 rounding of the oracle's result, all against sum |terms|."""
+    n, c = grad_logits.shape
+    idx, w = N(idx), N(w)
+    ref = O.slice_classify_backwards(grad_logits, values, delta_w, lin_w, lin_b, idx, w, n)[0]
+    mag = O.slice_classify_backwards(np.abs(grad_logits), values, np.zeros_like(delta_w), np.abs(lin_w), lin_b, idx,
+                                     np.abs(w + delta_w.reshape(-1)), n)[0]
+    assert_reduce_close(gv, ref, mag, row_counts(idx, ref.shape[0]), what="lattice-value gradient", extra=c + 1)
+
+
 @pytest.mark.parametrize("v", [64, 32])
 def test_f11_slice_classify_kitti_head(golden, v):
     """The wave-tiled kernels (ln_classify.hip: 64-point tiles forward, 16-point MFMA tiles backward; n = 1111 leaves both ragged)
@@ -192,6 +204,7 @@ def test_f11_slice_classify_kitti_head(golden, v):
     gdw, glw, glb = torch.zeros_like(dw), torch.zeros_like(lw), torch.zeros_like(lb)
     lat.slice_classify_backwards_with_precomputation(T(g["grad_logits"]), pos, lat.values(), dw, lw, lb, 20, gv, gdw, glw, glb, idx, w)
     close(N(gv), g[f"g_values_{v}"])
+    assert_slice_classify_value_gradient(gv, g["grad_logits"], g[f"lattice_values_{v}"], g["delta_w"], g[f"lin_w_{v}"], g[f"lin_b_{v}"], idx, w)
     close(N(gdw), g[f"g_delta_w_{v}"])
     close(N(glw), g[f"g_lin_w_{v}"])
     close(N(glb), g[f"g_lin_b_{v}"])
@@ -211,6 +224,7 @@ def test_f6_slice_classify(golden):
     gdw, glw, glb = torch.zeros_like(dw), torch.zeros_like(lw), torch.zeros_like(lb)
     lat.slice_classify_backwards_with_precomputation(T(g["grad_logits"]), pos, lat.values(), dw, lw, lb, 5, gv, gdw, glw, glb, idx, w)
     close(N(gv), g["g_values"])
+    assert_slice_classify_value_gradient(gv, g["grad_logits"], g["lattice_values"], g["delta_w"], g["lin_w"], g["lin_b"], idx, w)
     close(N(gdw), g["g_delta_w"])
     close(N(glw), g["g_lin_w"])
     close(N(glb), g["g_lin_b"])

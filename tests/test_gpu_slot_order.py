@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import lattice_oracle as O
+from tests.test_gpu_segment_reduce import assert_reduce_close, row_counts
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-5
@@ -199,6 +200,9 @@ def _splat_values_case(pos_np, vals_np, sigma, cap, half=False):
     got = N(lv).astype(np.float64)
     assert not got[m:].any(), "rows beyond the vertex count must stay zero"
     np.testing.assert_allclose(got[:m][np.argsort(perm)], ov, rtol=RTOL, atol=RTOL * float(np.abs(ov).max()))
+    oabs = np.zeros((m, v), np.float64)  # sum |x * w| per element: the scale of the per-element bound of the segment reduce
+    np.add.at(oabs, oidx[oidx >= 0], (np.abs(vals_np).astype(np.float64)[:, None, :] * np.abs(ow).reshape(n, 4, 1).astype(np.float64)).reshape(n * 4, v)[oidx >= 0])
+    assert_reduce_close(got[:m][np.argsort(perm)], ov, oabs, row_counts(oidx, m), what="splat values")
     return lat
 
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import lattice_oracle as O
+from tests.test_gpu_segment_reduce import assert_reduce_close, row_counts
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-5
@@ -104,6 +105,9 @@ def test_slice_classify_autograd_against_oracle(n, v, c):
     logits.backward(T(gl_np))
     gv, gd, gw, gb = O.slice_classify_backwards(gl_np, vals_np, dw_np, lw_np, lb_np, oidx, ow, n)
     close(N(vals.grad), gv)
+    # per element: the C-term dot product in front of the segment reduce, the reduce, and the fp32 rounding of the oracle's result
+    gabs = O.slice_classify_backwards(np.abs(gl_np), vals_np, np.zeros_like(dw_np), np.abs(lw_np), lb_np, oidx, np.abs(ow + dw_np.reshape(-1)), n)[0]
+    assert_reduce_close(vals.grad, gv, gabs, row_counts(oidx, m), what="lattice-value gradient", extra=c + 1)
     close(N(dw.grad), gd)
     close(N(lw.grad), gw)
     close(N(lb.grad), gb)
@@ -412,6 +416,9 @@ def test_fp16_feature_path_splat_conv_slice_end_to_end():
     expect = np.zeros((m, v), np.float64)
     np.add.at(expect, oidx, np.repeat(vals.cpu().double().numpy(), 4, axis=0) * ow[:, None])
     close(N(lv[:m]), expect, rtol=1e-5)
+    mag = np.zeros((m, v), np.float64)
+    np.add.at(mag, oidx, np.repeat(np.abs(vals.cpu().double().numpy()), 4, axis=0) * np.abs(ow.astype(np.float64))[:, None])
+    assert_reduce_close(lv[:m], expect, mag, row_counts(oidx, m), what="fp16 splat values")
     lvh = lv[:m].half().requires_grad_(True)
     cv, cwrap = ConvIm2RowLattice.apply(lvh, lat, W, 1)
     out = SliceLattice.apply(cv, cwrap.lattice, pos, idx, w)
@@ -458,6 +465,10 @@ def test_c5_full_size_fp16_feature_chain():
     expect = np.zeros((m, v), np.float64)
     np.add.at(expect, oidx, np.repeat(vals.cpu().double().numpy(), 4, axis=0) * ow[:, None])
     close(N(lv[:m]), expect, rtol=1e-5)  # fp16 rows accumulated in fp32
+    mag = np.zeros((m, v), np.float64)
+    np.add.at(mag, oidx, np.repeat(np.abs(vals.cpu().double().numpy()), 4, axis=0) * np.abs(ow.astype(np.float64))[:, None])
+    counts = row_counts(oidx, m)
+    assert_reduce_close(lv[:m], expect, mag, counts, what="C5 splat values")
     lvh = lv[:m].half().requires_grad_(True)
     cv, cwrap = ConvIm2RowLattice.apply(lvh, lat, W, 1)
     out = SliceLattice.apply(cv, cwrap.lattice, pos, idx, w)
@@ -482,6 +493,14 @@ def test_c5_full_size_fp16_feature_chain():
     close(N(out.float()), out_ref.detach().numpy(), scale=float(out_ref.abs().max()), rtol=4e-3)
     close(N(lvh.grad.float()), v64.grad.numpy(), scale=float(v64.grad.abs().max()), rtol=4e-3)
     close(N(W.grad.float()), w64.grad.numpy(), scale=float(w64.grad.abs().max()), rtol=4e-3)
+    # a second splat on the same lattice: the steady state of a training run, where the vertex count of the first build selects the
+    # workgroup-combining instance of the fused reduce (k_reduce_and_neighbours<8, 3, true, true, 8> on this dense cloud)
+    lv2, _, idx2, w2 = SplatLattice.apply(lat, pos, vals)
+    assert lat.nr_lattice_vertices() == m
+    np.testing.assert_array_equal(N(idx2), oidx)
+    np.testing.assert_array_equal(N(w2), ow)
+    close(N(lv2[:m]), expect, rtol=1e-5)
+    assert_reduce_close(lv2[:m], expect, mag, counts, what="C5 splat values, second build")
 
 
 @pytest.mark.parametrize("d,v", [(3, 64), (3, 12), (2, 20), (4, 8), (5, 40)])
