@@ -30,9 +30,6 @@ __device__ __forceinline__ void ln_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#ifndef LN_SCW_PROBE
-#define LN_SCW_PROBE 0
-#endif
 #ifndef LN_SCW_FWD_WAVES
 #define LN_SCW_FWD_WAVES 3  // waves per SIMD the register budget is held to (LDS admits three workgroups per CU)
 #endif
@@ -41,9 +38,6 @@ __device__ __forceinline__ float ln_dpp(float v) {  // the value of another lane
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
 }
 
-#ifndef LN_SCB_PROBE
-#define LN_SCB_PROBE 0
-#endif
 #ifndef LN_SCW_BWD_WAVES
 #define LN_SCW_BWD_WAVES 2
 #endif
@@ -75,11 +69,7 @@ __global__ void __launch_bounds__(256, LN_SCW_FWD_WAVES)
 #pragma unroll
             for (int r = 0; r < DP1; ++r) {
                 rows[ps][r] = s_idx[lp * DP1 + r];
-#if LN_SCW_PROBE == 2
-                x[ps][r] = make_float4(1.f, 2.f, 3.f, float(rows[ps][r]));
-#else
                 x[ps][r] = reinterpret_cast<const float4*>(values + (size_t)(rows[ps][r] >= 0 ? rows[ps][r] : 0) * V + ch * 32)[s];
-#endif
             }
         }
     };
@@ -145,10 +135,6 @@ __global__ void __launch_bounds__(256, LN_SCW_FWD_WAVES)
                 const float* wc[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) wc[k] = wch + (c0 + k < C ? c0 + k : C - 1) * V;
-#if LN_SCW_PROBE == 1
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[c0 + k] = acc[c0 + k] + wc[k][0] * hv[k];
-#else
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     float4 w4[4];
@@ -163,7 +149,6 @@ __global__ void __launch_bounds__(256, LN_SCW_FWD_WAVES)
 #pragma unroll
                     for (int k = 0; k < 4; ++k) acc[c0 + k] = acc[c0 + k] + w4[k].w * hv[4 * j + 3];
                 }
-#endif
             }
             ln_wave_sync();  // the next chunk overwrites s_h
         }
@@ -343,11 +328,7 @@ __global__ void __launch_bounds__(256, LN_SCW_BWD_WAVES)
                     const float4* src = reinterpret_cast<const float4*>(values + (size_t)(rows[ps][r] >= 0 ? rows[ps][r] : 0) * V);
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
-#if LN_SCB_PROBE & 1
-                        x[ps][r][u] = make_float4(1.f, 2.f, float(rows[ps][r]), 3.f);
-#else
                         x[ps][r][u] = src[s + 8 * u];
-#endif
                     }
                 }
             };
@@ -372,9 +353,7 @@ __global__ void __launch_bounds__(256, LN_SCW_BWD_WAVES)
                         dot[r] = dot[r] + (xv.x * g4.x + xv.y * g4.y + xv.z * g4.z + xv.w * g4.w);
                     }
                     *reinterpret_cast<float4*>(cell) = h;  // in place: gh of this cell has been read by this lane only
-#if !(LN_SCB_PROBE & 2)
                     if (p < n) reinterpret_cast<float4*>(grad_sliced + (size_t)p * V)[s + 8 * u] = g4;
-#endif
                 }
 #pragma unroll
                 for (int r = 0; r < DP1; ++r) {  // sum over the 8 lanes of the point: DPP within the quad, then across the two quads
@@ -396,10 +375,8 @@ __global__ void __launch_bounds__(256, LN_SCW_BWD_WAVES)
         // accumulated into (Lattice.cu:1091-1115): old value fetched with the tile's tokens, one lane-linear store
         if (lane < 16 * DP1 && p0 * DP1 + lane < tok_end) g_delta_w[p0 * DP1 + lane] = t_gdw_cur + s_dw[lane];
         // (3) gW += g^T @ [h | 1]: A[i = class][k = point], B[k = point][j = channel]
-#if !(LN_SCB_PROBE & 4)
 #pragma unroll
-#endif
-        for (int ks = (LN_SCB_PROBE & 4) ? 3 : 0; ks < 4; ++ks) {
+        for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const float b = s_gh[(ks * 4 + q) * SG + nt * 16 + i];

@@ -42,15 +42,7 @@ static bool ln_conv_b3_enabled();
                            // against 55 for the bf16x3 form at T = 3: profiles/r6_kernel_stats_C4_one_in_flight.csv)
 #endif
 static int ln_bwd_subtiles(int m) {
-    const int max_t = (ln_conv_b3_enabled() && !(ln_debug_mask() & 65536)) ? LN_BWD_B3_MAX_T : LN_BWD_MAX_SUBTILES;
-    {
-        static int forced = -1;  // experiment knob: LN_BWD_T=1..4 forces the sub-tile count
-        if (forced < 0) {
-            const char* e = getenv("LN_BWD_T");
-            forced = e ? atoi(e) : 0;
-        }
-        if (forced >= 1 && forced <= LN_BWD_MAX_SUBTILES) return forced;
-    }
+    const int max_t = ln_conv_b3_enabled() ? LN_BWD_B3_MAX_T : LN_BWD_MAX_SUBTILES;
     const int s = (m + 63) / 64;
     int best = 1, best_cost = 1 << 30;
     for (int t = 1; t <= max_t; ++t) {
@@ -338,9 +330,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #ifndef LN_CONV_LDS_E
 #define LN_CONV_LDS_E 16  // filter extents up to 2 (d + 1) + 1 with d <= 6 keep their neighbour ids in LDS
 #endif
-#ifndef LN_CONV_PROBE
-#define LN_CONV_PROBE 0  // timing ablations (wrong results): 1 no matrix products, 2 no operand split, 4 no bank staging, 8 no gather
-#endif
 // Waves per SIMD by gathered width (registers: 2 x V/4 row quarters + the staged bank slice + 4 NT accumulators; LDS: 36-48 KB bank
 // slice + 4 KB ids per workgroup): 3 up to 128 channels (<= 168 registers, 3 x 52 KB of LDS), 2 above (192 / 256 channels need
 // 174 / 220 registers: at 3 they spill, 1.77 ms instead of 0.63 at 256 x 256).  Measured at 46 k rows, 2 -> 3 waves: 64 x 64 37.7 -> 32.1 us,
@@ -349,9 +338,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // T sub-tiles of 64 rows per workgroup (256 T threads) share ONE staging of the slot's bank slice: T = 3 (one workgroup per CU, the
 // shape of k_conv_forward_b3) re-reads the bank from L2 and writes it to LDS a third as often as T = 1 (three workgroups per CU) —
 // at 46 k rows x 64 channels the bank traffic of T = 1 (727 workgroups x 9 slices of 24 KB = 157 MB) exceeds the gathered rows (107 MB).
-#ifndef LN_MFMA_B3_LINE
-#define LN_MFMA_B3_LINE 1  // 0: fragment-shaped gathers at 64 channels too (A/B)
-#endif
 template <int V, int NT, bool FLIP, int T>
 __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(LN_CONV_B3_WAVES(V), LN_CONV_B3_WAVES(V))))
     k_conv_mfma_b3(const int* __restrict__ nbr, const float* __restrict__ values, const u32x4* __restrict__ bank, int m, int E,
@@ -390,7 +376,7 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(LN
     // the stores (8 adjacent lanes = half a row).  Taken where it measures faster (A/B of two builds on one box, tools/probes/r6_ab_conv64.sh):
     // 64 -> 32 at 46.5 k rows 20.8 -> 18.2 us, 64 -> 64 at 11.4 k rows 13.8 -> 12.9; with three sub-tiles and 64 or 128 columns per
     // chunk the kernel is bound by its bank slices and LDS reads, not by the gather: 23.5 -> 24.0 and 39.7 -> 40.3 us — left as they were.
-    constexpr bool LINE = LN_MFMA_B3_LINE && V == 64 && (NT <= 2 || (T == 1 && NT <= 4));
+    constexpr bool LINE = V == 64 && (NT <= 2 || (T == 1 && NT <= 4));
     __shared__ floatx4 s_x[LINE ? 4 * T : 1][LINE ? 16 * 16 : 1];
     const int lr = lane >> 4, pc = lane & 15;
     auto fsw = [](int r) -> int { return (r & 3) | (((r >> 2) & 1) << 3); };
@@ -491,14 +477,7 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(LN
     for (int e = e_begin; e < e_end; ++e) {
         if (e + 1 < e_end) {
             if constexpr (!LINE) nb_nn = load_nb(e + 2);
-#if LN_CONV_PROBE & 8
-#pragma unroll
-            for (int k = 0; k < KQ; ++k) a_nxt[k] = a_cur[k] * 1.5f;
-#elif LN_CONV_PROBE & 4
-            ln_load_quarter<KQ>(values + (size_t)(nb_nxt >= 0 ? nb_nxt : 0) * V + q * KQ, a_nxt);
-#else
             issue(e + 1, nb_nxt, a_nxt);
-#endif
         }
         // (at 128 channels with one sub-tile per workgroup the staged bank slice takes 24-48 registers per thread: the double buffer spills there)
         constexpr bool PIPE = LN_CONV_B3_PIPE(V) && (V <= 96 || T == 3 || NT == 1);
@@ -522,16 +501,7 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(LN
                 p2[j] = ln_pack_hi(m0_, m1_);
                 p3[j] = ln_pack_hi(l0, l1);
             }
-#if LN_CONV_PROBE & 2
-            p1 = u32x4{__float_as_uint(a_cur[st * 8]), __float_as_uint(a_cur[st * 8 + 1]), __float_as_uint(a_cur[st * 8 + 2]), __float_as_uint(a_cur[st * 8 + 3])};
-            p2 = u32x4{__float_as_uint(a_cur[st * 8 + 4]), __float_as_uint(a_cur[st * 8 + 5]), __float_as_uint(a_cur[st * 8 + 6]), __float_as_uint(a_cur[st * 8 + 7])};
-            p3 = p1;
-#endif
             const bf16x8 a1 = __builtin_bit_cast(bf16x8, p1), a2 = __builtin_bit_cast(bf16x8, p2), a3 = __builtin_bit_cast(bf16x8, p3);
-#if LN_CONV_PROBE & 1
-            acc[0][0] += __uint_as_float((p1[0] ^ p2[1] ^ p3[2]) + (p1[1] ^ p2[2] ^ p3[3]) + (p1[2] ^ p2[3] ^ p3[0]) + (p1[3] ^ p2[0] ^ p3[1]));
-            continue;
-#endif
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 // PIPE: the three bank fragments of the NEXT chain are read from LDS ahead of this chain's six products, which
@@ -563,11 +533,9 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(LN
             }
         }
         if (e + 1 < e_end) {
-#if !(LN_CONV_PROBE & 4)
             __syncthreads();  // every wave is done with W_e
             stage();
             __syncthreads();
-#endif
         }
         // unconditional (a_nxt is initialised): no register of a_cur is ever undefined on a path through the loop — with
         // undefined lanes in the loop-carried registers hipcc 7.2 has mis-assigned the operands of the split's pack instructions
@@ -664,26 +632,7 @@ __global__ void __launch_bounds__(256)
 #else
 // (the scheduling barrier stays in the product build: left free, hipcc moves the split of the next rows and the fragment reads across
 // the phase boundaries and the kernel is 5-8 % slower than the instrumented build)
-#ifndef LN_CONV_R32_PIN
-#define LN_CONV_R32_PIN 1
-#endif
-#if LN_CONV_R32_PIN
 #define LN_R32_PHASE(k) __builtin_amdgcn_sched_barrier(0)
-#else
-#define LN_R32_PHASE(k) do { } while (0)
-#endif
-#endif
-#ifndef LN_CONV_R32_SPREAD
-#define LN_CONV_R32_SPREAD 0  // 1: the requests of an iteration go out in two halves
-#endif
-#ifndef LN_CONV_R32_PRIO
-#define LN_CONV_R32_PRIO 0    // 1..3: s_setprio around the products of a K-step
-#endif
-#ifndef LN_CONV_R32_SKEW
-#define LN_CONV_R32_SKEW 0    // 1: the second K-step's products are held back behind the next barrier
-#endif
-#ifndef LN_CONV_R32_PROBE
-#define LN_CONV_R32_PROBE 0  // timing ablations (wrong results): 1 no matrix products, 2 no operand split, 4 no A gather (one row), 8 no B staging
 #endif
 // Workgroup = RT row tiles of 32 rows x CH column groups of 32 NTW columns: RT * CH waves, wave (rt, ch) owns the [32 x 32 NTW]
 // block of the output.  The CH waves of a row tile share its gathered A chunk (double buffered: the partner may still be reading
@@ -749,9 +698,6 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
             const int j = k - BPW;
             const int nb = ids[j];
             const float* src = (nb >= 0 ? values + (size_t)nb * V : g_ln_zero_row) + kc_n * 32 + a_off[j];
-#if LN_CONV_R32_PROBE & 4
-            src = values + (size_t)(m0 + 8 * (ch * APW + j) + a_row < m ? m0 + 8 * (ch * APW + j) + a_row : 0) * V + a_off[j];
-#endif
             ln_glds16(src, lds_a + (unsigned)((CH > 1 ? buf_n : 0) * (RT * 4096) + j * 1024));
         }
     };
@@ -796,11 +742,6 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
             p2[j] = __builtin_amdgcn_perm(__float_as_uint(r11), __float_as_uint(r10), 0x07060302u);
             p3[j] = __builtin_amdgcn_perm(__float_as_uint(r21), __float_as_uint(r20), 0x07060302u);
         }
-#if LN_CONV_R32_PROBE & 2
-        p1 = araw[s][0];
-        p2 = araw[s][1];
-        p3 = p1;
-#endif
         dst[s][0] = __builtin_bit_cast(bf16x8, p1), dst[s][1] = __builtin_bit_cast(bf16x8, p2), dst[s][2] = __builtin_bit_cast(bf16x8, p3);
     };
 
@@ -855,21 +796,11 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
     // products of K-step s of one chunk: the NTW accumulation chains advance together (product p of every column tile, then
     // product p + 1); small terms first, the dominant product last
     auto products = [&](bf16x8 (&a)[3], u32x4 (&f)[NTW][3]) {
-#if LN_CONV_R32_PRIO
-        __builtin_amdgcn_s_setprio(LN_CONV_R32_PRIO);
-#endif
-#if LN_CONV_R32_PROBE & 1
-        acc[0][0] += __uint_as_float(f[0][0][0] ^ f[NTW - 1][1][1] ^ f[0][2][2]) + (float)a[0][0] + (float)a[1][1] + (float)a[2][2];
-#else
 #define LN_R32_PRODUCT(PA, PB)                                                                                                        \
     _Pragma("unroll") for (int nt = 0; nt < NTW; ++nt)                                                                                \
         acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], __builtin_bit_cast(bf16x8, f[nt][PB]), acc[nt], 0, 0, 0);
         LN_R32_PRODUCT(2, 0) LN_R32_PRODUCT(0, 2) LN_R32_PRODUCT(1, 1) LN_R32_PRODUCT(1, 0) LN_R32_PRODUCT(0, 1) LN_R32_PRODUCT(0, 0)
 #undef LN_R32_PRODUCT
-#endif
-#if LN_CONV_R32_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
     };
     // the walk's next three chunks, advanced once per iteration (no division in the loop); past the end they stay on the last chunk
     int w_e[3], w_kc[3];
@@ -891,9 +822,7 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
 #pragma unroll
         for (int k = first; k < last; ++k) {
             if (k < BPW) {
-#if !(LN_CONV_R32_PROBE & 8)
                 dma_piece(k, e1, kc1, (it + 1) & 1);
-#endif
             } else {
                 // (CH == 1: into the private region the rows of chunk it + 1 have just been read from, once those reads have returned)
                 if (CH == 1 && k == BPW) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -916,49 +845,26 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
             for (int x = 0; x < 3; ++x) fb0[nt][x] = sb[(nt * 3 + x) * 64];
         read_a((it + 1) & 1);  // rows of chunk it + 1
         LN_R32_PHASE(3);  // LDS reads issued
-#if LN_CONV_R32_SKEW
-        if (it > 0) products(nxt[1], fb1);  // second K-step of chunk it - 1 (its operands are in the other register set)
-        LN_R32_PHASE(4);  // held-back products issued
-        requests(it, 0, LN_CONV_R32_SPREAD ? NPIECES / 2 : NPIECES);
-        load_ids_of_slot(w_e[2]);
-        LN_R32_PHASE(5);  // requests issued
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-            for (int x = 0; x < 3; ++x) fb1[nt][x] = sb[((NT + nt) * 3 + x) * 64];
-        products(cur[0], fb0);
-        LN_R32_PHASE(6);  // first K-step's products issued
-        split_step(0, nxt);
-        if (LN_CONV_R32_SPREAD) requests(it, NPIECES / 2, NPIECES);
-        split_step(1, nxt);
-        LN_R32_PHASE(7);  // next rows split
-#else
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt)
 #pragma unroll
             for (int x = 0; x < 3; ++x) fb1[nt][x] = sb[((NT + nt) * 3 + x) * 64];
         products(cur[0], fb0);
         LN_R32_PHASE(4);  // first K-step's products issued
-        requests(it, 0, LN_CONV_R32_SPREAD ? NPIECES / 2 : NPIECES);
+        requests(it, 0, NPIECES);
         load_ids_of_slot(w_e[2]);
         LN_R32_PHASE(5);  // requests issued
         split_step(0, nxt);
         products(cur[1], fb1);
         LN_R32_PHASE(6);  // second K-step's products issued
-        if (LN_CONV_R32_SPREAD) requests(it, NPIECES / 2, NPIECES);
         split_step(1, nxt);
         LN_R32_PHASE(7);  // next rows split
-#endif
         advance(it);
     };
     for (int it = 0; it < total; it += 2) {
         iteration(it, ap, ap_b);
         if (it + 1 < total) iteration(it + 1, ap_b, ap);
     }
-#if LN_CONV_R32_SKEW
-    if (total & 1) products(ap[1], fb1);
-    else products(ap_b[1], fb1);
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the redundant last requests must not outlive the workgroup's LDS
 #ifdef LN_STAMPS
     if (g_ln_stamps_conv && lane == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
@@ -1348,19 +1254,13 @@ static int ln_conv_slots_per_split(int m, int E, int nr_filters) {
 #endif
 static size_t ln_conv_bank_bytes(int m, int E, int val_dim, int nr_filters);
 // Slot split of the WIDE form on mid-size lattices (0 / 1: not taken), from 128 gathered channels on where the 192-row workgroups of
-// the unsplit wide form would fill less than half the chip.  LN_CONV_WIDE_SPLIT=0 switches it off, =N forces N (A/B; read once).
+// the unsplit wide form would fill less than half the chip.
 // Measured at 11.4 k rows (level 2 of the SemanticKITTI network; tools/conv_time.py --coarse 1, us per call incl. bank split and
 // partial sum): 128 -> 128 46.9 -> 35.7, 256 -> 256 296 -> 109, 192 -> 192 191 -> 76, 256 -> 128 157 -> 55, 128 -> 64 32.2 -> 26.3.
 template <int V>
 static int ln_conv_wide_split(int m, int E, int nr_filters, bool have_bank) {
-    static int knob = -2;
-    if (knob == -2) {
-        const char* e = getenv("LN_CONV_WIDE_SPLIT");
-        knob = e ? atoi(e) : -1;
-    }
-    if (knob == 0 || !have_bank || V % 32 != 0 || V < LN_CONV_WIDE_SPLIT_MIN_V || nr_filters % 32 != 0 || E < 3 || m < LN_CONV_B3_MIN_ROWS) return 0;
+    if (!have_bank || V % 32 != 0 || V < LN_CONV_WIDE_SPLIT_MIN_V || nr_filters % 32 != 0 || E < 3 || m < LN_CONV_B3_MIN_ROWS) return 0;
     if ((long long)ln_div_up(m, 192) * ln_div_up(nr_filters, 128) >= LN_BWD_CUS / 2) return 0;  // the unsplit wide form already runs
-    if (knob > 1) return knob <= E ? knob : E;
     // workgroups of the widest launch: the 128-column chunks go out together, a narrower rest as a launch of its own
     const long long wgs = (long long)ln_div_up(m, 192) * (nr_filters >= 128 ? nr_filters / 128 : 1);
     // rounds of one workgroup per CU x slots walked per workgroup; the smallest split among the cheapest (fewer partial slabs)
@@ -1401,10 +1301,7 @@ static int ln_conv_slots_per_split_rt(int m, int E, int val_dim, int nr_filters)
 }
 
 // bf16x3 path: channel counts that are multiples of 32, lattices large enough to be matrix-bound, LN_CONV_EXACT_F32=1 switches
-// it off (A/B; read once)
-#ifndef LN_CONV_B3_MIN_ROWS
-#define LN_CONV_B3_MIN_ROWS 4096
-#endif
+// it off (read once per process)
 static bool ln_conv_b3_enabled() {
     static int v = -1;
     if (v < 0) {
@@ -1413,23 +1310,19 @@ static bool ln_conv_b3_enabled() {
     }
     return v == 1;
 }
-static bool ln_conv_rows32_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("LN_CONV_ROWS32");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
 static size_t ln_conv_bank_bytes(int m, int E, int val_dim, int nr_filters) {
     if (val_dim % 32 != 0 || nr_filters % 16 != 0 || m < LN_CONV_B3_MIN_ROWS || E > LN_CONV_LDS_E || !ln_conv_b3_enabled()) return 0;
     return (((size_t)E * val_dim * nr_filters * 3 * sizeof(unsigned short)) + 255) & ~size_t(255);
 }
 
+// shapes of the small-filter fast path, which needs no split bank
+static bool ln_conv_small_filter(int filter_extent, int val_dim, int nr_filters) {
+    return filter_extent == 9 && (size_t)filter_extent * val_dim * nr_filters * 4 <= 64 * 1024 && val_dim <= 32;
+}
+
 extern "C" size_t ln_conv_bank_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters) {
     if (m <= 0 || nr_filters % 16 != 0) return 0;
-    const bool small_filter = filter_extent == 9 && (size_t)filter_extent * val_dim * nr_filters * 4 <= 64 * 1024 && val_dim <= 32;
-    return small_filter ? 0 : ln_conv_bank_bytes(m, filter_extent, val_dim, nr_filters);
+    return ln_conv_small_filter(filter_extent, val_dim, nr_filters) ? 0 : ln_conv_bank_bytes(m, filter_extent, val_dim, nr_filters);
 }
 
 extern "C" size_t ln_conv_forward_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters) {
@@ -1439,22 +1332,15 @@ extern "C" size_t ln_conv_forward_workspace_bytes(int m, int filter_extent, int 
     if (ws_ > 1) e_per = (filter_extent + ws_ - 1) / ws_;
     const int nsplit = (filter_extent + e_per - 1) / e_per;
     // + the filter bank split into three bf16 parts (bf16x3 path of the per-slot kernel; not the small-filter fast path)
-    const bool small_filter = filter_extent == 9 && (size_t)filter_extent * val_dim * nr_filters * 4 <= 64 * 1024 && val_dim <= 32;
-    const size_t bank = small_filter ? 0 : ln_conv_bank_bytes(m, filter_extent, val_dim, nr_filters);
+    const size_t bank = ln_conv_small_filter(filter_extent, val_dim, nr_filters) ? 0 : ln_conv_bank_bytes(m, filter_extent, val_dim, nr_filters);
     return bank + (nsplit > 1 ? (size_t)nsplit * m * nr_filters * sizeof(float) : 0) + 256;
 }
 
 // Sub-tiles per workgroup of the bf16x3 per-slot kernel: 3 (one 768-thread workgroup per CU) where the kernel runs at three waves per
-// SIMD and there are at least as many such workgroups as CUs; LN_CONV_B3_T=1|3 forces it (A/B, read once).
+// SIMD and there are at least as many such workgroups as CUs.
 template <int V>
 static int ln_conv_b3_subtiles(int m, int chunks) {
-    static int forced = -1;
-    if (forced < 0) {
-        const char* e = getenv("LN_CONV_B3_T");
-        forced = e ? atoi(e) : 0;
-    }
     if (LN_CONV_B3_WAVES(V) != 3) return 1;
-    if (forced == 1 || forced == 3) return forced;
     return (long long)ln_div_up(m, 192) * chunks >= LN_BWD_CUS * 3 / 4 ? 3 : 1;
 }
 
@@ -1508,11 +1394,11 @@ static bool ln_conv_launch_v(int nr_filters, const int* nbr, const float* values
     int f_off = 0;
     size_t bank_off = 0;  // bf16 elements
     // wide form (both operands by LDS-DMA, 32-row MFMA tiles, every output column in one pass over the gathered rows): column
-    // chunks of 128, then one narrower chunk.  LN_CONV_ROWS32=0 keeps the 16-row kernels (A/B; read once)
+    // chunks of 128, then one narrower chunk
     if constexpr (V % 32 == 0) {
         // taken from 96 gathered channels on (below, the 16-row kernels' gathers are as fast: 64 x 64 27 vs 29 us at 46 k rows) and
         // while the 192-row workgroups alone fill half the chip (no slot split in this form)
-        if (b3 && nr_filters % 32 == 0 && V >= 96 && ln_conv_rows32_enabled() &&
+        if (b3 && nr_filters % 32 == 0 && V >= 96 &&
             (wide_mid || (nsplit == 1 && (long long)ln_div_up(m, 192) * ln_div_up(nr_filters, 128) >= LN_BWD_CUS / 2))) {
 #define LN_CONV_R32SK(NTC, RTT)                                                                                                     \
     {                                                                                                                               \
@@ -1548,13 +1434,8 @@ static bool ln_conv_launch_v(int nr_filters, const int* nbr, const float* values
     }
             // 96 columns (three tiles: no even split of the columns over a pair of waves) take the split-K pairs: 96 -> 96 62.5 -> 54.1 us,
             // 128 -> 96 80.7 -> 69.1 us at 46.5 k rows; at 128 / 64 columns the column-split pairs are faster (80 vs 85, 50.6 vs 52 us:
-            // the pair's partial sums cost a pass through LDS at the end).  LN_CONV_R32_SK=0: column-split everywhere (A/B; read once)
-            static int sk = -1;
-            if (sk < 0) {
-                const char* ev = getenv("LN_CONV_R32_SK");
-                sk = (ev && ev[0] == '0') ? 0 : 1;
-            }
-            if (sk == 1 && (nr_filters - f_off) % 128 == 96) {
+            // the pair's partial sums cost a pass through LDS at the end)
+            if ((nr_filters - f_off) % 128 == 96) {
                 LN_CONV_R32(4, 2, 2, 6) LN_CONV_R32SK(3, 6)
             }
             LN_CONV_R32(4, 2, 2, 6) LN_CONV_R32(3, 3, 1, 4) LN_CONV_R32(2, 1, 2, 6) LN_CONV_R32(1, 1, 1, 4)
@@ -1612,9 +1493,6 @@ static bool ln_conv_launch_v(int nr_filters, const int* nbr, const float* values
 //   B = W_e split while the bank is staged: one 16-byte fragment per (slot, column tile, part, lane (f, q)) = W[e][8q..8q+7][f].
 // After the one barrier behind the staging the slot loop is gathers, register splits and 12 matrix instructions per slot and wave.
 // ------------------------------------------------------------------------------------------
-#ifndef LN_FWD_LINE
-#define LN_FWD_LINE 1  // 0: the fragment-shaped gathers of rounds 2-4 (A/B)
-#endif
 template <int T>
 __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T, T)))
     k_conv_forward_b3(const int* __restrict__ nbr, const float* __restrict__ values, const float* __restrict__ filter, int m,
@@ -1624,7 +1502,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     constexpr int FRAG16 = E * NT * 3 * 64;  // 16-byte fragments of the split bank (54 KB)
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[FRAG16 * 16];
     const u32x4* s_frag = reinterpret_cast<const u32x4*>(s_raw);
-#if LN_FWD_LINE
     // Line-shaped gathers (round 5).  Loads shaped like the MFMA fragment — lane (i, q) reads its 32-byte quarter of row i — touch 64
     // different 128-byte lines per wave-instruction and run at half the rate of loads in which 8 adjacent lanes read one whole row
     // (tools/probes/gather_layout_probe.cpp: 3.5 vs 7.0 TB/s whatever the hit rate).  So lane l loads piece l & 7 (16 bytes) of rows
@@ -1634,7 +1511,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     // (8 adjacent lanes = one row).  LDS operations of one wave execute in program order: no barrier, only a compiler fence.
     __shared__ __attribute__((aligned(16))) floatx4 s_x[4 * T][16 * 8];
     __shared__ int s_nbr[64 * T * E];
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int i = lane & 15;
@@ -1657,7 +1533,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
 #pragma unroll
         for (int j = 0; j < 8; ++j) wv[s][j] = filter[(ev8 * 8 + j) * F + f];
     }
-#if LN_FWD_LINE
     {
         const size_t g0 = (size_t)bx * (64 * T) * E, g_end = (size_t)m * E;
         for (int x = tid; x < 64 * T * E; x += THREADS) s_nbr[x] = (g0 + x < g_end) ? nbr[g0 + x] : -1;
@@ -1686,16 +1561,10 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     for (int j = 0; j < 2; ++j) xw[j] = &s_x[wv_][(8 * j + lr) * 8 + ((lane & 7) ^ fsw(8 * j + lr))];
     const floatx4* xr0 = &s_x[wv_][i * 8 + ((2 * q) ^ fsw(i))];
     const floatx4* xr1 = &s_x[wv_][i * 8 + ((2 * q + 1) ^ fsw(i))];
-#else
-    int nb[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) nb[e] = (my_row < m) ? nbr[(size_t)my_row * E + e] : -1;
-#endif
 #ifndef LN_FWD_DEPTH
 #define LN_FWD_DEPTH 4
 #endif
     constexpr int DEPTH = LN_FWD_DEPTH;  // ring of gathered quarter rows: DEPTH - 1 gathers in flight (4: 14.9 us, 7: 15.7, 10 = all nine up front: 17.1)
-#if LN_FWD_LINE
     floatx4 a[DEPTH][2];
     auto gather = [&](int e, floatx4 (&dst)[2]) {
 #pragma unroll
@@ -1704,11 +1573,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     };
 #pragma unroll
     for (int k = 0; k < DEPTH - 1 && k < E; ++k) gather(k, a[k]);
-#else
-    float a[DEPTH][KQ];
-#pragma unroll
-    for (int k = 0; k < DEPTH - 1 && k < E; ++k) ln_load_quarter<KQ>(values + (size_t)(nb[k] >= 0 ? nb[k] : 0) * V + q * KQ, a[k]);
-#endif
     // bank -> split -> LDS fragments (16-byte unit ((e * NT + f / 16) * 3 + part) * 64 + (v / 8) * 16 + f % 16 holds rows v..v+7)
     u32x4* s_frag_w = reinterpret_cast<u32x4*>(s_raw);
 #pragma unroll
@@ -1734,7 +1598,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-#if LN_FWD_LINE
         if (e + DEPTH - 1 < E) gather(e + DEPTH - 1, a[(e + DEPTH - 1) % DEPTH]);
         // rows of absent neighbours are zeroed by the lane that loaded them; then the wave's 16 x 32 floats change shape through LDS
 #pragma unroll
@@ -1747,22 +1610,12 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const float ae[KQ] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-        #else
-        float (&ae)[KQ] = a[e % DEPTH];
-        if (e + DEPTH - 1 < E)
-            ln_load_quarter<KQ>(values + (size_t)(nb[e + DEPTH - 1] >= 0 ? nb[e + DEPTH - 1] : 0) * V + q * KQ, a[(e + DEPTH - 1) % DEPTH]);
-#endif
         u32x4 p1, p2, p3;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             unsigned int h0, m0_, l0, h1, m1_, l1;
-#if LN_FWD_LINE
             ln_split3_bits(ae[2 * j], h0, m0_, l0);
             ln_split3_bits(ae[2 * j + 1], h1, m1_, l1);
-#else
-            ln_split3_bits(nb[e] >= 0 ? ae[2 * j] : 0.f, h0, m0_, l0);
-            ln_split3_bits(nb[e] >= 0 ? ae[2 * j + 1] : 0.f, h1, m1_, l1);
-#endif
             p1[j] = ln_pack_hi(h0, h1);
             p2[j] = ln_pack_hi(m0_, m1_);
             p3[j] = ln_pack_hi(l0, l1);
@@ -1772,17 +1625,12 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         for (int nt = 0; nt < NT; ++nt) {
             const u32x4* pb = s_frag + ((e * NT + nt) * 3) * 64 + lane;
             const bf16x8 b1 = __builtin_bit_cast(bf16x8, pb[0]), b2 = __builtin_bit_cast(bf16x8, pb[64]), b3 = __builtin_bit_cast(bf16x8, pb[128]);
-#ifdef LN_CONV_PROBE_NO_MFMA  // attribution build (wrong results): the gathers and operand loads stay, ONE matrix instruction per slot and tile
-            asm volatile("" ::"v"(a2), "v"(a3), "v"(b2), "v"(b3));  // (operands stay computed and loaded)
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[nt], 0, 0, 0);
-#else
             acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, b1, acc[nt], 0, 0, 0);
             acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b3, acc[nt], 0, 0, 0);
             acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, acc[nt], 0, 0, 0);
             acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b1, acc[nt], 0, 0, 0);
             acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b2, acc[nt], 0, 0, 0);
             acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[nt], 0, 0, 0);
-#endif
         }
     }
     // C/D layout: col = lane & 15, row = (lane >> 4) * 4 + reg
@@ -1800,18 +1648,10 @@ static int ln_conv_dispatch(const int* nbr, const float* values_neigh, const flo
                             int nr_filters, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
     bool done = false;
     if (filter_extent == 9 && (reinterpret_cast<uintptr_t>(filter) & 15) == 0) {  // d = 3 small-filter fast path
-        if constexpr (!FLIP && !WT) {  // V = F = 32 forward on the bf16 matrix cores (LN_DEBUG_MASK & 524288: fp32 form, A/B)
-            if (val_dim == 32 && nr_filters == 32 && m >= LN_CONV_B3_MIN_ROWS && ln_conv_b3_enabled() && !(ln_debug_mask() & 524288) &&
+        if constexpr (!FLIP && !WT) {  // V = F = 32 forward on the bf16 matrix cores
+            if (val_dim == 32 && nr_filters == 32 && m >= LN_CONV_B3_MIN_ROWS && ln_conv_b3_enabled() &&
                 (reinterpret_cast<uintptr_t>(values_neigh) & 15) == 0) {
-                int t = min(ln_bwd_subtiles(m), 3);
-                {
-                    static int forced = -1;  // experiment knob: LN_FWD_T=1..3 forces the forward's sub-tile count alone (read once)
-                    if (forced < 0) {
-                        const char* e = getenv("LN_FWD_T");
-                        forced = e ? atoi(e) : 0;
-                    }
-                    if (forced >= 1 && forced <= 3) t = forced;
-                }
+                const int t = min(ln_bwd_subtiles(m), 3);
                 const dim3 grid_t(ln_div_up(m, 64 * t)), block_t(256 * t);
                 if (t == 1) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<1>), grid_t, block_t, 0, st, nbr, values_neigh, filter, m, out, g_ln_row_partition);
                 else if (t == 2) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<2>), grid_t, block_t, 0, st, nbr, values_neigh, filter, m, out, g_ln_row_partition);
@@ -2076,9 +1916,6 @@ typedef short gf_short4 __attribute__((ext_vector_type(4)));
 #ifndef LN_GFB_WAVES
 #define LN_GFB_WAVES 2
 #endif
-#ifndef LN_GFB_PROBE
-#define LN_GFB_PROBE 0  // timing ablations (wrong results): 1 no matrix products / fragment reads, 2 no gather, 4 no operand split
-#endif
 #ifndef LN_GFB_EG
 #define LN_GFB_EG 3   // slots per workgroup: E = 9 as three groups (gridDim.y); the gradient rows are split three times instead of nine
 #endif
@@ -2142,11 +1979,7 @@ __global__ void __launch_bounds__(64 * WV * WF, (WV * WF) > 8 ? 1 : LN_GFB_WAVES
             const int x4 = tid + THREADS * k;
             const int c4 = x4 % (V / 4);
             ra[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-#if LN_GFB_PROBE & 2
-            ra[k] = make_float4(1.f + nb[k], 2.f, 3.f + c4, 4.f);
-#else
             if (nb[k] >= 0) ra[k] = *reinterpret_cast<const float4*>(values + (size_t)nb[k] * v_total + v_off + c4 * 4);
-#endif
         }
     };
     auto fetch_g = [&](int sub) {
@@ -2161,15 +1994,10 @@ __global__ void __launch_bounds__(64 * WV * WF, (WV * WF) > 8 ? 1 : LN_GFB_WAVES
     };
     auto stage = [&](const float4& x, unsigned short* dst, int plane) {  // four consecutive channels of one row -> three planes
         unsigned int h[4], md[4], lo[4];
-#if LN_GFB_PROBE & 4
-        h[0] = md[0] = lo[0] = __float_as_uint(x.x); h[1] = md[1] = lo[1] = __float_as_uint(x.y);
-        h[2] = md[2] = lo[2] = __float_as_uint(x.z); h[3] = md[3] = lo[3] = __float_as_uint(x.w);
-#else
         ln_split3_bits(x.x, h[0], md[0], lo[0]);
         ln_split3_bits(x.y, h[1], md[1], lo[1]);
         ln_split3_bits(x.z, h[2], md[2], lo[2]);
         ln_split3_bits(x.w, h[3], md[3], lo[3]);
-#endif
         *reinterpret_cast<uint2*>(dst) = make_uint2(ln_pack_hi(h[0], h[1]), ln_pack_hi(h[2], h[3]));
         *reinterpret_cast<uint2*>(dst + plane) = make_uint2(ln_pack_hi(md[0], md[1]), ln_pack_hi(md[2], md[3]));
         *reinterpret_cast<uint2*>(dst + 2 * plane) = make_uint2(ln_pack_hi(lo[0], lo[1]), ln_pack_hi(lo[2], lo[3]));
@@ -2223,7 +2051,7 @@ __global__ void __launch_bounds__(64 * WV * WF, (WV * WF) > 8 ? 1 : LN_GFB_WAVES
                 fetch_ids(sub + LN_GFB_SUB);
             }
 #pragma unroll
-            for (int st = 0; st < ((LN_GFB_PROBE & 1) ? 0 : LN_GFB_SUB / 32); ++st) {
+            for (int st = 0; st < LN_GFB_SUB / 32; ++st) {
                 const int row0 = 32 * st + 4 * q + (i >> 2);
                 bf16x8 fa[TPV][3], fb[TPF][3];
 #pragma unroll
@@ -2267,21 +2095,12 @@ __global__ void __launch_bounds__(64 * WV * WF, (WV * WF) > 8 ? 1 : LN_GFB_WAVES
 // rows per workgroup of the bf16x3 filter gradient: as few as fill the chip (>= 512 workgroups over chunks x slot groups x sub-blocks) while the
 // slabs the chunks write (and k_reduce_slabs4 reads back) stay under LN_GFB_SLAB_BYTES; a multiple of the 64-row sub-tile
 #define LN_GFB_SLAB_BYTES (24ll << 20)
-// LN_GFB_WIDE=0 keeps the 64 x 64 sub-blocks of round 4 (A/B; read once)
-static bool ln_gfb_wide() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("LN_GFB_WIDE");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
 static bool ln_gfb_block(int val_dim, int nr_filters, int* vs, int* fs) {
     // (whole faces of 128 x 64, 64 x 128 and 96 x 96 on 4 x 2 / 2 x 4 / 3 x 2 waves measured the same as their 64 x 64 / 32 x 96
     // sub-blocks — 65 vs 66 us, 71 vs 71 us at 46 k rows —, and 96 x 96 on 2 x 2 waves spills: only 128 x 128 takes the whole face)
     static const int cand[7][2] = {{128, 128}, {64, 64}, {32, 96}, {96, 32}, {64, 32}, {32, 64}, {32, 32}};
     for (auto& c : cand)
-        if (val_dim % c[0] == 0 && nr_filters % c[1] == 0 && (ln_gfb_wide() || (c[0] + c[1] <= 128))) {
+        if (val_dim % c[0] == 0 && nr_filters % c[1] == 0) {
             *vs = c[0];
             *fs = c[1];
             return true;
@@ -2304,8 +2123,7 @@ static int ln_gfb_rows(int m, int filter_extent, int val_dim, int nr_filters) {
 }
 static bool ln_gfb_enabled(int m, int filter_extent, int val_dim, int nr_filters) {
     int vs, fs;
-    return filter_extent == 9 && m >= LN_CONV_B3_MIN_ROWS && ln_conv_b3_enabled() && !(ln_debug_mask() & 8388608) &&
-           ln_gfb_block(val_dim, nr_filters, &vs, &fs);
+    return filter_extent == 9 && m >= LN_CONV_B3_MIN_ROWS && ln_conv_b3_enabled() && ln_gfb_block(val_dim, nr_filters, &vs, &fs);
 }
 
 // Any multiple of 16 in both dimensions: the [V, F] block of a slot is covered by sub-blocks of {64, 32, 16} x {64, 32, 16}.
@@ -2316,7 +2134,7 @@ extern "C" size_t ln_conv_grad_filter_workspace_bytes(int m, int filter_extent, 
     // one [E, V, F] slab per row chunk; the fused backward of a same-lattice convolution (ln_conv_backward) has its own chunking
     int chunks = ln_bwd_fused_shape(filter_extent, val_dim, nr_filters) ? max(ln_div_up(m, LN_GF_ROWS), ln_bwd_workgroups(m))
                                                                         : ln_div_up(m, LN_GF_ROWS);
-    const int rows_b3 = ln_gfb_rows(m, filter_extent, val_dim, nr_filters);  // (whichever of the two forms runs: LN_DEBUG_MASK can switch)
+    const int rows_b3 = ln_gfb_rows(m, filter_extent, val_dim, nr_filters);  // (whichever of the two forms runs)
     if (rows_b3 > 0) chunks = max(chunks, ln_div_up(m, rows_b3));
     return (size_t)chunks * filter_extent * val_dim * nr_filters * sizeof(float) + 256;
 }
@@ -2597,10 +2415,10 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
 //                    as bf16 — the SAME parts it feeds the value gradient with — and the column access the MFMA needs (lane (f, q):
 //                    rows 8q..8q+7 of column f) comes from ds_read_b64_tr_b16, the LDS transpose read (tools/probes/tr_read_probe.cpp)
 // Per slot and wave 12 + 12 MFMAs of 16 cycles instead of 16 + 16 of 32: backward 31.0 -> 24.5 us at C3.
-// T = 1..3 (four sub-tiles of staging do not fit LDS; LN_DEBUG_MASK & 65536 selects the fp32 kernel for A/B).
+// T = 1..3 (four sub-tiles of staging do not fit LDS).
 // History worth keeping: for a while only T = 3 was launched, because with T = 1 / 2 — workgroups that leave room on their CU for
 // waves of other kernels — two concurrently replayed scans returned wrong filter gradients in 1-3 % of the replays.  The kernel was
-// never wrong (a -DLN_TR_CHECK build re-reads every transposed fragment element by element): its INPUT was, reduced by the other
+// never wrong (an investigation build re-read every transposed fragment element by element): its INPUT was, reduced by the other
 // scan's k_csr_reduce_segments while this kernel was on the chip.  Cause, isolated in tools/probes/pk_fma_vs_mfma_probe.cpp: on this
 // part a packed fp32 instruction whose LOW result takes a source from the HIGH half of a register pair (v_pk_fma_f32 op_sel:[0,1,0],
 // v_pk_mul_f32 op_sel:[0,1] — the compiler's weight broadcasts in the reduce) returns a wrong low result while a wave of another kernel
@@ -2609,14 +2427,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
 // 0 of 300 after; tests/test_gpu_parity.py::test_other_streams_unharmed_beside_fused_backward keeps the pair under test.
 // ------------------------------------------------------------------------------------------
 typedef short short4v __attribute__((ext_vector_type(4)));
-#ifdef LN_TR_CHECK  // investigation build (tools/probes/fused_b3_stress.py): transposed fragments re-read element by element
-__device__ int ln_dbg[4 + 16 * 8];
-extern "C" int ln_debug_dump(int* host, int n) {
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(ln_dbg), n * sizeof(int)) != hipSuccess) return 1;
-    static int zeros[4 + 16 * 8];
-    return hipMemcpyToSymbol(HIP_SYMBOL(ln_dbg), zeros, sizeof zeros) != hipSuccess;
-}
-#endif
 template <int T>
 __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T, T)))
     k_conv_backward_fused_b3(const int* __restrict__ nbr, const float* __restrict__ values, const float* __restrict__ grad_out,
@@ -2626,12 +2436,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     constexpr int THREADS = 256 * T;
     constexpr int BANK = E * V * F;                      // floats of one slab (the parking area at the end)
     constexpr int FRAG16 = E * NT * 3 * 64;              // 16-byte fragments of the split bank
-#ifndef LN_BWD_SWZ
-#define LN_BWD_SWZ 1  // 0: the padded 80-byte rows of rounds 3-5 (A/B)
-#endif
-#ifndef LN_BWD_LINE
-#define LN_BWD_LINE LN_BWD_SWZ  // line-shaped gathers of the gradient rows (below); 0: the fragment-shaped ones of rounds 3-5 (A/B)
-#endif
     // Staged G_e rows.  Rounds 3-5: 64 bytes + 16 of padding per row — conflict-free for the 16-byte staging stores but not for the
     // transposing reads (rows r and r + 3 / r + 8 and r + 11 of a lane group overlap).  Round 6: no padding, the 16-byte piece p of row r
     // sits at position p ^ swz(r), swz(r) = ((r >> 1) & 3) ^ (bit 3 of r) << 1, chosen against the lane groups of MI355X_MICROARCH.md §LDS:
@@ -2640,12 +2444,8 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     //   ds_read_b64_tr_b16 — 32 lanes (rows R .. R + 3 and R + 8 .. R + 11, 32 bytes each) over 256 bytes: rows R + j and R + 8 + j share
     //                   a 64-byte column and, bit 3 flipping the half, read its two different halves.
     // 12 KB less LDS per sub-tile.
-    constexpr int RS = LN_BWD_SWZ ? 32 : 40;             // bf16 elements per staged G_e row
-#if LN_BWD_LINE
+    constexpr int RS = 32;                               // bf16 elements per staged G_e row
     auto swz = [](int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; };  // {0, 2, 3, 1} by row quad (see the line-shaped gathers below)
-#else
-    auto swz = [](int r) { return ((r >> 1) & 3) ^ ((r >> 2) & 2); };
-#endif
     constexpr int PART = 64 * RS;                        // one part of one sub-tile's G_e
     constexpr int STAGE = 2 * 3 * PART;                  // double-buffered, three parts (bf16 elements)
     constexpr int LDS_BYTES_A = FRAG16 * 16 + T * STAGE * 2;
@@ -2675,13 +2475,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         const int x4 = tid + s * THREADS;
         wv[s] = (N4 % THREADS == 0 || x4 < N4) ? reinterpret_cast<const float4*>(filter)[x4] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-#if !LN_BWD_LINE
-    int nb[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) nb[e] = (my_row < m) ? nbr[(size_t)my_row * E + (e < E - 1 ? (e ^ 1) : e)] : -1;
-#else
-    static_assert(LN_BWD_SWZ, "the line-shaped gathers stage unpadded, swizzled rows");
-#endif
     const int vt = wave / FT, ft = wave % FT;
     // A operand of the filter gradient, split: step s (32 rows), part p -> 8 bf16 = rows 32s + 8q + j of column vt*16 + i
     u32x4 va[2][3];
@@ -2709,7 +2502,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
 #endif
     constexpr int DEPTH = LN_BWD_DEPTH;  // gathers in flight per lane
     auto slot_of = [](int k) { return k == 0 ? E - 1 : k - 1; };
-#if LN_BWD_LINE
     // Line-shaped gathers (round 6; the forward has them since round 5).  A load shaped like the MFMA fragment — lane (i, q) reads its
     // 32-byte quarter of row i — touches 16 lines per wave-instruction, half of each; here lane l loads piece l & 7 (16 bytes) of the rows
     // l >> 3 and 8 + (l >> 3) of the wave's 16: 8 whole lines per instruction.  The rows are staged for the filter gradient anyway; the lane
@@ -2738,13 +2530,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         a[0][j] = *reinterpret_cast<const floatx4*>(grad_out + (size_t)(m0 + 8 * j + lr < m ? m0 + 8 * j + lr : 0) * F + c8 * 4);
 #pragma unroll
     for (int k = 1; k < DEPTH && k < E; ++k) gather(slot_of(k), a[k % (DEPTH + 1)]);
-#else
-    float a[DEPTH + 1][KQ];
-    ln_load_quarter<KQ>(grad_out + (size_t)(my_row < m ? my_row : 0) * F + q * KQ, a[0]);
-#pragma unroll
-    for (int k = 1; k < DEPTH && k < E; ++k)
-        ln_load_quarter<KQ>(grad_out + (size_t)(nb[slot_of(k)] >= 0 ? nb[slot_of(k)] : 0) * F + q * KQ, a[k % (DEPTH + 1)]);
-#endif
     // bank -> split -> LDS fragments of W_e^T: x = (e*V + v)*F + f, four consecutive f = elements j..j+3 of ONE fragment
 #pragma unroll
     for (int s = 0; s < NST; ++s) {
@@ -2780,7 +2565,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     for (int k = 0; k < E; ++k) {
         const int e = slot_of(k);
         unsigned short* sg = s_stage + (size_t)sub * STAGE + (k & 1) * (3 * PART);
-#if LN_BWD_LINE
         if (k + DEPTH < E) gather(slot_of(k + DEPTH), a[(k + DEPTH) % (DEPTH + 1)]);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {  // this lane's piece of rows lr and 8 + lr: split once, staged for both gradients
@@ -2803,51 +2587,17 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
             p2 = *reinterpret_cast<const u32x4*>(src + PART);
             p3 = *reinterpret_cast<const u32x4*>(src + 2 * PART);
         }
-#else
-        float (&ae)[KQ] = a[k % (DEPTH + 1)];
-        if (k + DEPTH < E)
-            ln_load_quarter<KQ>(grad_out + (size_t)(nb[slot_of(k + DEPTH)] >= 0 ? nb[slot_of(k + DEPTH)] : 0) * F + q * KQ, a[(k + DEPTH) % (DEPTH + 1)]);
-        // this lane's quarter of G_e[row], split once: the A fragments of the value gradient AND what is staged for the filter gradient
-        u32x4 p1, p2, p3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            unsigned int h0, m0_, l0, h1, m1_, l1;
-            ln_split3_bits(nb[e] >= 0 ? ae[2 * j] : 0.f, h0, m0_, l0);
-            ln_split3_bits(nb[e] >= 0 ? ae[2 * j + 1] : 0.f, h1, m1_, l1);
-            p1[j] = ln_pack_hi(h0, h1);
-            p2[j] = ln_pack_hi(m0_, m1_);
-            p3[j] = ln_pack_hi(l0, l1);
-        }
-        {
-            unsigned short* dst = sg + (wave * 16 + i) * RS + (LN_BWD_SWZ ? ((q ^ swz(wave * 16 + i)) * KQ) : q * KQ);
-            *reinterpret_cast<u32x4*>(dst) = p1;
-            *reinterpret_cast<u32x4*>(dst + PART) = p2;
-            *reinterpret_cast<u32x4*>(dst + 2 * PART) = p3;
-        }
-        __syncthreads();
-#ifdef LN_TR_CHECK
-        {
-            const u32x4 rb = *reinterpret_cast<volatile u32x4*>(sg + (wave * 16 + i) * RS + (LN_BWD_SWZ ? ((q ^ swz(wave * 16 + i)) * KQ) : q * KQ));
-            if (rb[0] != p1[0] || rb[1] != p1[1] || rb[2] != p1[2] || rb[3] != p1[3]) atomicAdd(&ln_dbg[1], 1);
-        }
-#endif
-#endif
         const bf16x8 a1 = __builtin_bit_cast(bf16x8, p1), a2 = __builtin_bit_cast(bf16x8, p2), a3 = __builtin_bit_cast(bf16x8, p3);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const u32x4* pb = s_frag + ((e * NT + nt) * 3) * 64 + q * 16 + (i ^ (2 * q));
             const bf16x8 b1 = __builtin_bit_cast(bf16x8, pb[0]), b2 = __builtin_bit_cast(bf16x8, pb[64]), b3 = __builtin_bit_cast(bf16x8, pb[128]);
-#ifdef LN_CONV_PROBE_NO_MFMA  // attribution build (wrong results): one matrix instruction instead of six
-            asm volatile("" ::"v"(a2), "v"(a3), "v"(b2), "v"(b3));
-            acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc_v[nt], 0, 0, 0);
-#else
             acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, b1, acc_v[nt], 0, 0, 0);
             acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b3, acc_v[nt], 0, 0, 0);
             acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, acc_v[nt], 0, 0, 0);
             acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b1, acc_v[nt], 0, 0, 0);
             acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b2, acc_v[nt], 0, 0, 0);
             acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc_v[nt], 0, 0, 0);
-#endif
         }
         // filter gradient: two 32-row steps; B fragments through the LDS transpose read (lane: 4 contiguous bf16 of row
         // row0 + (i >> 2), columns ft*16 + 4 (i & 3) ..; it receives rows row0..row0+3 of column ft*16 + i)
@@ -2860,8 +2610,8 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
                 // lane: 4 contiguous bf16 (half a 16-byte piece) of row r0 + (i >> 2), elements ft * 16 + 4 (i & 3) ..
                 const int r_lo = 32 * st + 8 * q + (i >> 2), r_hi = r_lo + 4;
                 const int piece = ft * 2 + ((i & 3) >> 1), inner = (i & 1) * 4;
-                const unsigned short* base = sg + part * PART + r_lo * RS + (LN_BWD_SWZ ? ((piece ^ swz(r_lo)) * 8 + inner) : (ft * 16 + (i & 3) * 4));
-                const unsigned short* base_hi = sg + part * PART + r_hi * RS + (LN_BWD_SWZ ? ((piece ^ swz(r_hi)) * 8 + inner) : (ft * 16 + (i & 3) * 4));
+                const unsigned short* base = sg + part * PART + r_lo * RS + (piece ^ swz(r_lo)) * 8 + inner;
+                const unsigned short* base_hi = sg + part * PART + r_hi * RS + (piece ^ swz(r_hi)) * 8 + inner;
                 const short4v lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(base));
                 const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(base_hi));
                 u32x4 packed;
@@ -2870,46 +2620,15 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
                 packed[2] = (unsigned int)(unsigned short)hi4[0] | ((unsigned int)(unsigned short)hi4[1] << 16);
                 packed[3] = (unsigned int)(unsigned short)hi4[2] | ((unsigned int)(unsigned short)hi4[3] << 16);
                 b[part] = __builtin_bit_cast(bf16x8, packed);
-#ifdef LN_TR_CHECK
-                {
-                    unsigned int badm = 0, ex2 = 0, got2 = 0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int rr_ = 32 * st + 8 * q + j, ee_ = ft * 16 + i;
-                        const unsigned int ex = *(volatile unsigned short*)(sg + part * PART + rr_ * RS + (LN_BWD_SWZ ? ((((ee_ >> 3) ^ swz(rr_)) << 3) | (ee_ & 7)) : ee_));
-                        const unsigned int got = (packed[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                        if (ex != got) { badm |= 1u << j; ex2 = ex; got2 = got; }
-                    }
-                    if (badm) {
-                        const int slot = atomicAdd(&ln_dbg[0], 1);
-                        if (slot < 16) {
-                            int* r = ln_dbg + 4 + slot * 8;
-                            r[0] = blockIdx.x;
-                            r[1] = lane | wave << 8 | k << 16 | part << 24 | st << 28;
-                            r[2] = (int)badm;
-                            r[3] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 6);   // HW_REG_LDS_ALLOC
-                            r[4] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID
-                            r[5] = (int)__builtin_amdgcn_s_getreg((3 << 11) | 20);   // XCC id
-                            r[6] = (int)(ex2 | got2 << 16);
-                            r[7] = (int)(size_t)(sg - reinterpret_cast<unsigned short*>(s_raw));
-                        }
-                    }
-                }
-#endif
             }
             const bf16x8 v1 = __builtin_bit_cast(bf16x8, va[st][0]), v2 = __builtin_bit_cast(bf16x8, va[st][1]), v3 = __builtin_bit_cast(bf16x8, va[st][2]);
             floatx4& acc = st ? w1 : w0;
-#ifdef LN_CONV_PROBE_NO_MFMA
-            asm volatile("" ::"v"(v2), "v"(v3), "v"(b[1]), "v"(b[2]));
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, b[0], acc, 0, 0, 0);
-#else
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v3, b[0], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, b[2], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v2, b[1], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v2, b[0], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, b[1], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, b[0], acc, 0, 0, 0);
-#endif
         }
         acc_w[e] = w0 + w1;
     }
@@ -2948,8 +2667,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     }
 }
 
-static bool ln_bwd_fused_enabled() { return !(ln_debug_mask() & 2048); }  // LN_DEBUG_MASK & 2048: the two-launch backward (A/B)
-
 // Both gradients of out = conv(values_neigh; nbr_q, filter[E*V, F]):
 //   grad_filter[E*V, F] = im2row(values_neigh; nbr_q)^T @ grad_out            (ln_conv_grad_filter)
 //   grad_values[mn, V]  = conv(grad_out; nbr_n, filter, FLIP | TRANSPOSED)     (ln_conv_forward)
@@ -2967,21 +2684,20 @@ extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float*
         float* partial = static_cast<float*>(workspace);
         const int total = filter_extent * val_dim * nr_filters;
         const int bwd_t = ln_bwd_subtiles(mn);
-        if (nbr_q == nbr_n && mq == mn && ln_bwd_fused_shape(filter_extent, val_dim, nr_filters) && ln_bwd_fused_enabled()) {
+        if (nbr_q == nbr_n && mq == mn && ln_bwd_fused_shape(filter_extent, val_dim, nr_filters)) {
             // same lattice on both sides: one gather per (vertex, slot) serves both gradients
             const int wgs = ln_div_up(mn, 64 * bwd_t);
 #define LN_BWD_FUSED(TT)                                                                                                               \
     case TT:                                                                                                                           \
         if constexpr (TT <= LN_BWD_B3_MAX_T) { /* bf16 matrix cores, exactly split operands */                                         \
-            if (ln_conv_b3_enabled() && !(ln_debug_mask() & 65536)) {                                                                  \
+            if (ln_conv_b3_enabled()) {                                                                                                \
                 LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused_b3<TT>), dim3(wgs), dim3(256 * TT), 0, st, nbr_n, values_neigh, grad_out, \
                           filter, mn, grad_values, partial, g_ln_row_partition);                                                       \
                 break;                                                                                                                 \
             }                                                                                                                          \
         }                                                                                                                              \
-        if (true)                                                                                                                         \
-            LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused<32, 32, 9, TT>), dim3(wgs), dim3(256 * TT), 0, st, nbr_n, values_neigh, grad_out, \
-                      filter, mn, grad_values, partial);                                                                               \
+        LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused<32, 32, 9, TT>), dim3(wgs), dim3(256 * TT), 0, st, nbr_n, values_neigh, grad_out, \
+                  filter, mn, grad_values, partial);                                                                                   \
         break;
             switch (bwd_t) { LN_BWD_FUSED(1) LN_BWD_FUSED(2) LN_BWD_FUSED(3) LN_BWD_FUSED(4) }
 #undef LN_BWD_FUSED
@@ -3002,13 +2718,8 @@ extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float*
 #undef LN_BWD_FULL
     }
     if (fused) return ln_check_launch("ln_conv_backward");
-    static int fuse_sum = -1;  // LN_BWD_SLAB_SUM_IN_SPLIT=0: the slab sum as a launch of its own (A/B; read once)
-    if (fuse_sum < 0) {
-        const char* ev = getenv("LN_BWD_SLAB_SUM_IN_SPLIT");
-        fuse_sum = (ev && ev[0] == '0') ? 0 : 1;
-    }
     int rc = ln_conv_grad_filter_impl(nbr_q, values_neigh, grad_out, mq, filter_extent, val_dim, nr_filters, grad_filter, workspace, workspace_bytes,
-                                      stream, fuse_sum == 1);
+                                      stream, true);
     if (rc) {
         (void)ln_take_slab_job();
         return rc;

@@ -102,9 +102,6 @@ __global__ void __launch_bounds__(256)
 //   bank [E*V, F]   : a thread reads 8 rows x 8 columns (eight 16-byte loads) and writes the 8 units of its columns;
 //   bank^T [E*F, V] : a thread reads 8 consecutive k of one column (one 16-byte load) = one unit.
 // ------------------------------------------------------------------------------------------
-#ifndef LN_F16_LINE
-#define LN_F16_LINE 1  // 0: fragment-shaped gathers at 64 channels too (A/B)
-#endif
 template <int V, int NT, bool FLIP, bool WT>
 __global__ void __launch_bounds__(1024)
     k_conv_f16_tiled(const int* __restrict__ nbr, const _Float16* __restrict__ values, const _Float16* __restrict__ filter, int m,
@@ -123,7 +120,7 @@ __global__ void __launch_bounds__(1024)
     // l >> 3 and 8 + (l >> 3) of the wave's 16, and the wave re-shapes its 2 KB through a private, XOR-swizzled LDS region into the
     // fragment shape (lane (i, q) = pieces 2q, 2q + 1 of row i).  The fragment-shaped loads gathered 81 MB in 23 us = 3.5 TB/s at C5:
     // the rate of that shape whatever the hit rate (tools/probes/gather_layout_probe.cpp).
-    constexpr bool LINE = (V == 64) && LN_F16_LINE;
+    constexpr bool LINE = V == 64;
     constexpr int DEPTH = 4;  // ring of gathered quarter rows: DEPTH - 1 gathers in flight
     __shared__ __attribute__((aligned(16))) halfx8 s_x[LINE ? 16 : 1][16 * 8];
     __shared__ int s_nbr[LINE ? 256 * E : 1];
@@ -235,14 +232,8 @@ __global__ void __launch_bounds__(1024)
 }
 
 // sub-tiles per workgroup of k_conv_f16_tiled: the launch runs in rounds of 256 CUs x (workgroups that fit a CU's LDS); the T with the
-// cheapest rounds(T) * T wins, larger T (fewer bank stagings) on ties.  LN_F16_T = 1..4 forces it (experiments).
+// cheapest rounds(T) * T wins, larger T (fewer bank stagings) on ties.
 static int ln_f16_subtiles(int m, size_t lds_bytes) {
-    static int forced = -1;
-    if (forced < 0) {
-        const char* e = getenv("LN_F16_T");
-        forced = e ? atoi(e) : 0;
-    }
-    if (forced >= 1 && forced <= 4) return forced;
     const int per_cu = lds_bytes * 2 <= 150 * 1024 ? 2 : 1;
     const int tiles = (m + 63) / 64;
     int best = 1, best_cost = 1 << 30;
@@ -264,12 +255,11 @@ static int ln_f16_subtiles(int m, size_t lds_bytes) {
 template <bool FLIP, bool WT>
 static bool ln_conv_f16_tiled(const int* nbr, const _Float16* values, const _Float16* filter, int m, int E, int val_dim, int nr_filters,
                               _Float16* out, hipStream_t st) {
-    static const bool off = getenv("LN_F16_PER_SLOT") != nullptr;  // A/B: the per-slot kernel for every shape
-    if (off || E != 9 || ((reinterpret_cast<uintptr_t>(values) | reinterpret_cast<uintptr_t>(filter)) & 15) != 0) return false;
+    if (E != 9 || ((reinterpret_cast<uintptr_t>(values) | reinterpret_cast<uintptr_t>(filter)) & 15) != 0) return false;
 #define LN_F16_TILED(VV, NN)                                                                                                         \
     if (val_dim == VV && nr_filters == 16 * NN) {                                                                                    \
         /* (at 64 channels: + the re-shaping regions of up to 16 waves and the ids, see the kernel) */                               \
-        const int t = ln_f16_subtiles(m, (size_t)9 * VV * 16 * NN * 2 + ((VV == 64 && LN_F16_LINE) ? 16 * 2048 + 256 * 9 * 4 : 0));  \
+        const int t = ln_f16_subtiles(m, (size_t)9 * VV * 16 * NN * 2 + (VV == 64 ? 16 * 2048 + 256 * 9 * 4 : 0));          \
         LN_LAUNCH("k_conv_mfma_f16", (k_conv_f16_tiled<VV, NN, FLIP, WT>), dim3(ln_div_up(m, 64 * t)), dim3(256 * t), 0, st, nbr, values, \
                   filter, m, out);                                                                                                   \
         return true;                                                                                                                 \

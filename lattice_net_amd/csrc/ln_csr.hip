@@ -290,7 +290,6 @@ struct LnReduceArgs {
     int chunks, lanes_per_seg, src_div, src_stride;
     float* dst;
     long long seg_region;
-    int dbg_plain;  // experiment: plain stores instead of atomics (wrong sums, timing only)
     int deterministic;  // LnCsr.dense & 2: one lane group per ROW, tokens in CSR order, no atomics (run-to-run identical sums)
 };
 
@@ -475,7 +474,7 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
         }
         if (cok && head && !absorbed) {
             float* d = dst + (size_t)row * V + c * VEC;
-            if ((beg == rbeg && run_end == rend) || a.dbg_plain) {  // this run is the whole group: no other writer
+            if (beg == rbeg && run_end == rend) {  // this run is the whole group: no other writer
                 if constexpr (VEC == 8) {
                     *reinterpret_cast<float4*>(d) = make_float4(acc[0], acc[1], acc[2], acc[3]);
                     *reinterpret_cast<float4*>(d + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
@@ -522,15 +521,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// LN_REDUCE_L8=0: the general kernels for the 8-lane, 8-chunk shape too (A/B; read once)
-static bool ln_reduce_l8() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("LN_REDUCE_L8");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
 static int ln_reduce_args(const char* who, const LnCsr* csr, const int* grp_row, long long max_segments, const void* src, bool half,
                           const float* w, int val_dim, int src_div, int src_stride, float* dst, LnReduceArgs& a, int& vec, long long& work) {
     LN_REQUIRE(max_segments >= 0 && val_dim >= 1 && src_div >= 1 && src_stride >= val_dim, LN_ERR_ARG, "%s: bad sizes", who);
@@ -546,7 +536,7 @@ static int ln_reduce_args(const char* who, const LnCsr* csr, const int* grp_row,
     while (lanes < chunks && lanes < 64) lanes <<= 1;
     work = max_segments * lanes;
     if (max_segments > 0) a = LnReduceArgs{csr->grp_start, csr->csr_tok, reinterpret_cast<const int4*>(csr->seg_desc), csr->seg_count, grp_row, src, w, chunks, lanes,
-                                           src_div, src_stride, dst, csr->seg_region, (ln_debug_mask() & 128) ? 1 : 0, (csr->dense & 2) ? 1 : 0};
+                                           src_div, src_stride, dst, csr->seg_region, (csr->dense & 2) ? 1 : 0};
     return LN_OK;
 }
 
@@ -565,11 +555,11 @@ static int ln_csr_reduce_rows_impl(const char* who, const LnCsr* csr, const int*
     const bool wg = ((csr->dense & 1) != 0 || a.lanes_per_seg >= 16) && vec >= 4 && !(csr->dense & 2);
 #define LN_REDUCE_LAUNCH(VV, HH)                                                                                                     \
     {                                                                                                                                \
-        if (wg && VV == 8 && HH && a.lanes_per_seg == 8 && a.chunks == 8 && ln_reduce_l8())                                          \
+        if (wg && VV == 8 && HH && a.lanes_per_seg == 8 && a.chunks == 8)                                                            \
             LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<8, true, true, 8>), grid, block, 0, st, a);                    \
         else if (wg)                                                                                                                 \
             LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<VV, HH, (VV >= 4)>), grid, block, 0, st, a);                   \
-        else if (VV == 4 && !HH && a.lanes_per_seg == 8 && a.chunks == 8 && ln_reduce_l8())                                          \
+        else if (VV == 4 && !HH && a.lanes_per_seg == 8 && a.chunks == 8)                                                            \
             LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<4, false, false, 8>), grid, block, 0, st, a);                  \
         else                                                                                                                         \
             LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<VV, HH, false>), grid, block, 0, st, a);                       \
@@ -617,13 +607,13 @@ static int ln_splat_tail_impl(const char* who, const LnCsr* csr, const int* grp_
     const dim3 grid(reduce_blocks + nbr_blocks), block(256);
 #define LN_FUSED_LAUNCH(VV, DD, HH)                                                                                                  \
     {                                                                                                                                \
-        if (wg && VV == 8 && HH && a.lanes_per_seg == 8 && a.chunks == 8 && ln_reduce_l8())                                          \
+        if (wg && VV == 8 && HH && a.lanes_per_seg == 8 && a.chunks == 8)                                                            \
             LN_LAUNCH("k_reduce_and_neighbours", (k_reduce_and_neighbours<8, DD, true, true, 8>), grid, block, 0, st, a, reduce_blocks, \
                       *table, query_rows_upper, nbr);                                                                                \
         else if (wg)                                                                                                                 \
             LN_LAUNCH("k_reduce_and_neighbours", (k_reduce_and_neighbours<VV, DD, HH, (VV >= 4)>), grid, block, 0, st, a, reduce_blocks, \
                       *table, query_rows_upper, nbr);                                                                                \
-        else if (VV == 4 && !HH && a.lanes_per_seg == 8 && a.chunks == 8 && ln_reduce_l8())                                          \
+        else if (VV == 4 && !HH && a.lanes_per_seg == 8 && a.chunks == 8)                                                            \
             LN_LAUNCH("k_reduce_and_neighbours", (k_reduce_and_neighbours<4, DD, false, false, 8>), grid, block, 0, st, a, reduce_blocks, \
                       *table, query_rows_upper, nbr);                                                                                \
         else                                                                                                                         \
@@ -792,14 +782,10 @@ __global__ void __launch_bounds__(256)
     unsigned long long* d = packed + (size_t)row * channels + c;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-#ifdef LN_SEGMAX_PLAIN  // timing ablation (wrong results): what the 64-bit atomics cost
-        d[k] = best[k];
-#else
         if (whole_row)
             d[k] = best[k];
         else
             atomicMax(d + k, best[k]);
-#endif
     }
     if (counts && c == 0) {  // vertex degree on the side (the fused PointNet reduction needs it; integer adds: order-free)
         if (whole_row)

@@ -118,9 +118,6 @@ __global__ void __launch_bounds__(256)
     const int chunks = CH ? CH : chunks_arg;
     using T = typename VecT<VEC>::type;
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-#ifdef LN_PROBE_NO_CLEAR  // timing probe (wrong results): no zero fill
-    zero_fill = nullptr;
-#endif
     if (zero_fill) {  // the accumulator the backward pass of this slice will scatter into, zeroed on the way
         const long long threads = (long long)gridDim.x * blockDim.x;
         for (long long i = g; i < zero_elems; i += threads) zero_fill[i] = 0.f;
@@ -722,7 +719,7 @@ extern "C" int ln_slice_classify_forward(const float* values, const float* delta
     LN_REQUIRE(nr_classes >= 1 && (n == 0 || (delta_w && lin_w && lin_b && w)), LN_ERR_ARG, "ln_slice_classify_forward: bad args");
     if (n == 0) return LN_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (!(ln_debug_mask() & 1048576) && ln_sc_forward_wave(values, delta_w, lin_w, lin_b, idx, w, n, pos_dim, val_dim, nr_classes, logits, st))
+    if (ln_sc_forward_wave(values, delta_w, lin_w, lin_b, idx, w, n, pos_dim, val_dim, nr_classes, logits, st))
         return ln_check_launch("ln_slice_classify_forward");  // wave-tiled kernel (ln_classify.hip): V % 32 == 0, C <= 32, d in {2, 3}
     if (val_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(values) & 15) == 0) {
         // float4 kernel: largest tile whose [C + PB, V+1] + 2 [PB, d+1] arrays fit 64 KiB and whose threads own <= 16 classes each
@@ -1034,8 +1031,8 @@ extern "C" int ln_slice_classify_backward(const float* grad_logits, const float*
     float* slabs = static_cast<float*>(workspace);
     const int cv = nr_classes * val_dim;
     int grid = 0;
-    const bool wave_kernel = !(ln_debug_mask() & 1048576) && ln_sc_backward_wave(grad_logits, values, delta_w, lin_w, idx, w, n, pos_dim, val_dim, nr_classes,
-                                                                          g_delta_w, grad_sliced, w_eff, slabs, &grid, st);
+    const bool wave_kernel = ln_sc_backward_wave(grad_logits, values, delta_w, lin_w, idx, w, n, pos_dim, val_dim, nr_classes,
+                                                 g_delta_w, grad_sliced, w_eff, slabs, &grid, st);
     if (!wave_kernel) {
     const int cp = (nr_classes + 3) & ~3;
     const bool v4 = (val_dim % 4 == 0) && (cp * val_dim <= 256 * LN_SC_BLOCKS * 16) &&

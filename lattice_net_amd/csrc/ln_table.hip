@@ -45,16 +45,6 @@ int ln_check_launch(const char* what) {
 
 extern "C" const char* ln_last_error_string(void) { return g_ln_error; }
 
-#include <stdlib.h>
-int ln_debug_mask() {
-    static int mask = -1;
-    if (mask < 0) {
-        const char* e = getenv("LN_DEBUG_MASK");
-        mask = e ? atoi(e) : 0;
-    }
-    return mask;
-}
-
 // ------------------------------------------------------------------------------------------
 // live per-kernel timing: a (start, stop) event pair bound to each dispatch of the armed kernels
 // (bench.py's roofline block is computed from these)
@@ -545,9 +535,6 @@ __global__ void __launch_bounds__(TH)
        // before it (1.6 us at C3 when they came first); here only the end of the kernel does.
         const long long stride = (long long)gridDim.x * TH;
         const long long g = (long long)blockIdx.x * TH + threadIdx.x;
-#ifdef LN_PROBE_NO_CLEAR  // timing probe (wrong results): the values are not cleared
-        clear_values = nullptr;
-#endif
         if (clear_values) {
             const long long n4 = clear_values_elems >> 2;
             float4* v4 = reinterpret_cast<float4*>(clear_values);
@@ -1307,16 +1294,14 @@ __global__ void __launch_bounds__(256) k_canon_idx(int* __restrict__ idx, long l
 
 template <int D>
 static int ln_canonicalize_impl(const LnTable& t, int* idx, long long tokens, const LnCsr* csr, const BuildWs& ws, hipStream_t st) {
-    const int dbg = ln_debug_mask();
-    if (dbg & 256) return LN_OK;
     if (ln_zero_async(ws.bitmap, (size_t)ws.nb * 4 * sizeof(unsigned long long), st)) return LN_ERR_LAUNCH;
     const int slot_blocks = ln_div_up(t.capacity, 256);
     LN_LAUNCH("k_canon_mark", k_canon_mark, dim3(slot_blocks), dim3(256), 0, st, t, ws.bitmap);
     LN_LAUNCH("k_scan_blocks", k_scan_blocks, dim3(1), dim3(1024), 0, st, (const int*)nullptr, ws.bitmap, ws.nb, ws.block_prefix, t.nr_filled, t.status,
               (int*)nullptr, 0, 1);
-    if (!(dbg & 512)) LN_LAUNCH("k_canon_slots", k_canon_slots<D>, dim3(slot_blocks), dim3(256), 0, st, t, ws.bitmap, ws.block_prefix, ws.tok_pos);
-    if (idx && !(dbg & 64)) LN_LAUNCH("k_canon_idx", k_canon_idx, dim3(ws.nb), dim3(256), 0, st, idx, tokens, ws.tok_pos);
-    if (csr && csr->seg_desc && csr->seg_count && !(dbg & 32))
+    LN_LAUNCH("k_canon_slots", k_canon_slots<D>, dim3(slot_blocks), dim3(256), 0, st, t, ws.bitmap, ws.block_prefix, ws.tok_pos);
+    if (idx) LN_LAUNCH("k_canon_idx", k_canon_idx, dim3(ws.nb), dim3(256), 0, st, idx, tokens, ws.tok_pos);
+    if (csr && csr->seg_desc && csr->seg_count)
         LN_LAUNCH("k_canon_segs", k_canon_segs, dim3(ln_div_up((long long)LN_XCD_GROUPS * csr->seg_region, 256)), dim3(256), 0, st,
                   reinterpret_cast<int4*>(csr->seg_desc), csr->seg_count, csr->seg_region, ws.tok_pos);
     return ln_check_launch("ln_canonicalize");
@@ -1369,13 +1354,9 @@ static int ln_build_points(const LnTable* t, const float* positions_raw, const f
             const int nbk = t->slot_map ? (ln_bucket_count(t->capacity) / LN_XCD_GROUPS) * LN_XCD_GROUPS : ln_bucket_count(t->capacity);
             const size_t lds = bucket_lds;
             int* dropped_idx = write_idx ? idx : (int*)nullptr;  // tokens that never reach a bucket get idx = -1 in pass 1
-            // the same 512-point tile (the same number of cursor atomics) on 512 threads (a whole point each), 1024 (half a point each) or
-            // 256 (two points each): LN_DEBUG_MASK & 2097152 selects 256, & 4194304 selects 1024 (A/B)
-            if (D <= 3 && (ln_debug_mask() & 4194304))
-                LN_LAUNCH("k_point_keys", (k_point_keys<D, (D <= 3 ? 1024 : 256)>), dim3(ln_div_up(n, 512)), dim3(1024), 0, st, *t, positions_raw, sc, n, sb,
-                          nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed,
-                          csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub);
-            else if (D <= 3 && !(ln_debug_mask() & 2097152))
+            // the same 512-point tile (the same number of cursor atomics) on 512 threads (a whole point each); measured against 1024
+            // (half a point each) and 256 (two points each)
+            if (D <= 3)
                 LN_LAUNCH("k_point_keys", (k_point_keys<D, (D <= 3 ? 512 : 256)>), dim3(ln_div_up(n, 512)), dim3(512), 0, st, *t, positions_raw, sc, n, sb,
                           nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed,
                           csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub);
@@ -1388,12 +1369,7 @@ static int ln_build_points(const LnTable* t, const float* positions_raw, const f
             // pack beside the other scans' kernels: C3 1407 -> 1441 Mpoints/s, C4 (3 100 tokens per bucket) 947 -> 980, C2 with 16 clouds
             // per step 494 -> 508 — C5, 7 500 tokens per bucket, 1421 -> 1401 (LN_BKT_THREADS=512 builds, one box).  The caller says
             // whether builds overlap with other work (ln_build_concurrency); alone, and on big buckets, 1024 stays.
-            static int narrow_ok = -1;  // LN_BKT_NARROW=0: 1024-thread bucket workgroups whatever the concurrency (A/B; read once)
-            if (narrow_ok < 0) {
-                const char* ev = getenv("LN_BKT_NARROW");
-                narrow_ok = (ev && ev[0] == '0') ? 0 : 1;
-            }
-            const bool narrow = narrow_ok && g_ln_build_concurrency > 1 && tokens <= (long long)LN_BKT_NARROW_TOKENS * nbk;
+            const bool narrow = g_ln_build_concurrency > 1 && tokens <= (long long)LN_BKT_NARROW_TOKENS * nbk;
             if (narrow)
                 LN_LAUNCH("k_bucket_rows", (k_bucket_rows<D, 512>), dim3(nbk), dim3(512), lds, st, *t, sb, nbk, ws.capb, t->slot_cnt,
                       ws.part_tok, ws.part_pk, ws.part_slot, ws.part_pos, dropped_idx, *csr, ws.pub);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """F12 (SemanticKITTI network at 120 000 points) on the GPU against the fixture: error statistics of the logits and of every gradient.
-LN_CONV_EXACT_F32=1 / LN_CONV_ROWS32=0 / LN_GFB_WIDE=0 select other kernels for an A/B."""
+LN_CONV_EXACT_F32=1 selects the fp32 convolution kernels for an A/B."""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

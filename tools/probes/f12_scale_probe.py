@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where does the GPU network leave the float64 oracle-lattice network as the cloud grows?  The SemanticKITTI model (F12's cfg and seeded
 parameters) on lidar clouds of n points: GPU float32 against this package's definition in float64 over tests/oracle_lattice (CPU).
-usage: f12_scale_probe.py n [n ...]   (environment toggles select kernels: LN_CONV_EXACT_F32=1, LN_CONV_ROWS32=0, LN_GFB_WIDE=0, ...)"""
+usage: f12_scale_probe.py n [n ...]   (LN_CONV_EXACT_F32=1 selects the fp32 convolution kernels)"""
 import os, sys, tempfile
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Which kernel is the victim?  One stream loops the fused convolution backward of scan A (the form chosen by LN_BWD_T /
-LN_DEBUG_MASK in the environment), a second stream loops a kernel of scan B on fixed inputs and compares every result with its
+"""Which kernel is the victim?  One stream loops the fused convolution backward of scan A (the form chosen by
+LN_CONV_EXACT_F32 in the environment), a second stream loops a kernel of scan B on fixed inputs and compares every result with its
 first one: the segment reduce of the slice backward (k_csr_reduce_segments), the convolution forward, a torch elementwise kernel.
 argv: rounds.  (wrong gradient rows when the one- / two-sub-tile bf16x3 backward runs beside other kernels.)"""
 import sys
