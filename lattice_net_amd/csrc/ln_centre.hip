@@ -39,7 +39,9 @@ __global__ void __launch_bounds__(256)
         for (int k = 0; k < LN_MC_MAX_K; ++k)
             if (k < K) {
                 v[k] = xr[(size_t)k * C];
-                if (v[k] > mx) {  // first maximum wins
+                // first maximum wins; a NaN counts as larger than everything (x.max(1) of the reference expression: NaN propagates),
+                // the first NaN wins
+                if (v[k] > mx || (v[k] != v[k] && mx == mx)) {
                     mx = v[k];
                     am = k;
                 }

@@ -7,6 +7,11 @@
 //   apply      : every workgroup rebuilds the per-channel scale/shift from the C channel sums in LDS, then one
 //                float4 pass over its slab
 // Backward uses the same two shapes: per-channel sums of gy*x and gy, then dx = gy*gamma*rstd + x*c2[g] + c3[g].
+// Every fp32 sum that involves x is a sum of x - p over the LN_GN_PASSES rows of ONE thread, with the pivot p the first of these
+// rows: sum (x-p)^2 and sum gy*(x-p) have the size of the spread of those rows, not of their offset from zero, and a pivot that is an
+// outlier spoils 16 rows' worth of a sum it is itself a term of, never the whole statistic.  Each thread then puts its pivot back in
+// fp64 (sum x = S1 + n p, sum x^2 = S2 + 2 p S1 + n p^2, sum gy x = S + p sum gy): everything from there on, the fold of the
+// workgroup, the atomics and E[x^2] - mean^2, is fp64, where the cancellation costs 2^-53, not 2^-24.
 #include "ln_common.h"
 
 #define LN_GN_MAX_C 1024
@@ -22,7 +27,7 @@ __global__ void __launch_bounds__(256)
     k_gn_stats(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift, int relu, int m, int c,
                double* __restrict__ acc, const int* __restrict__ rows_dev) {
     if (rows_dev) m = min(m, *rows_dev);  // static-rows mode: the tensors are taller than the lattice, only its rows count
-    __shared__ float4 s_p[256], s_q[256];
+    __shared__ double s_p[256][4], s_q[256][4];
     const int tid = threadIdx.x;
     const int quads = c >> 2;                 // c % 4 == 0, c <= 1024  ->  quads <= 256
     const int rows_per_pass = 256 / quads;
@@ -31,8 +36,12 @@ __global__ void __launch_bounds__(256)
     const bool live = rp < rows_per_pass;
     const long long r0 = (long long)blockIdx.x * rows_per_pass * LN_GN_PASSES;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), q = p;
+    double pd[4] = {0.0, 0.0, 0.0, 0.0}, qd[4] = {0.0, 0.0, 0.0, 0.0};
     if (live) {
         float4 a = p, b = p;
+        // pivots: this thread's first row (with no row of its own all its terms are zero)
+        const float4 pv = r0 + rp < m ? reinterpret_cast<const float4*>(x + (r0 + rp) * c)[qi] : p;
+        int n = 0;
         if (gy && relu) {
             a = reinterpret_cast<const float4*>(scale_shift)[qi];
             b = reinterpret_cast<const float4*>(scale_shift + c)[qi];
@@ -42,7 +51,8 @@ __global__ void __launch_bounds__(256)
         for (int k = 0; k < LN_GN_PASSES; ++k) {
             const long long row = r0 + (long long)k * rows_per_pass + rp;
             const bool ok = row < m;
-            xv[k] = ok ? reinterpret_cast<const float4*>(x + row * c)[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
+            n += ok;
+            xv[k] = ok ? reinterpret_cast<const float4*>(x + row * c)[qi] : pv;  // (x - p = 0 beyond the last row)
             if (gy) gv[k] = ok ? reinterpret_cast<const float4*>(gy + row * c)[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
@@ -55,28 +65,42 @@ __global__ void __launch_bounds__(256)
                     if (!(xv[k].z * a.z + b.z > 0.f)) g.z = 0.f;
                     if (!(xv[k].w * a.w + b.w > 0.f)) g.w = 0.f;
                 }
-                p.x += g.x * xv[k].x; p.y += g.y * xv[k].y; p.z += g.z * xv[k].z; p.w += g.w * xv[k].w;
+                p.x += g.x * (xv[k].x - pv.x); p.y += g.y * (xv[k].y - pv.y); p.z += g.z * (xv[k].z - pv.z); p.w += g.w * (xv[k].w - pv.w);
                 q.x += g.x; q.y += g.y; q.z += g.z; q.w += g.w;
             } else {
-                p.x += xv[k].x; p.y += xv[k].y; p.z += xv[k].z; p.w += xv[k].w;
-                q.x += xv[k].x * xv[k].x; q.y += xv[k].y * xv[k].y; q.z += xv[k].z * xv[k].z; q.w += xv[k].w * xv[k].w;
+                const float4 d = make_float4(xv[k].x - pv.x, xv[k].y - pv.y, xv[k].z - pv.z, xv[k].w - pv.w);
+                p.x += d.x; p.y += d.y; p.z += d.z; p.w += d.w;
+                q.x += d.x * d.x; q.y += d.y * d.y; q.z += d.z * d.z; q.w += d.w * d.w;
             }
         }
+        // the pivot goes back in, in fp64
+        const float ps[4] = {p.x, p.y, p.z, p.w}, qs[4] = {q.x, q.y, q.z, q.w}, pvs[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double s1 = ps[j], s2 = qs[j], pj = pvs[j];
+            pd[j] = gy ? s1 + pj * s2 : s1 + n * pj;
+            qd[j] = gy ? s2 : s2 + 2.0 * pj * s1 + n * pj * pj;
+        }
     }
-    s_p[tid] = p;
-    s_q[tid] = q;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s_p[tid][j] = pd[j];
+        s_q[tid][j] = qd[j];
+    }
     __syncthreads();
     if (live && rp == 0) {  // fold the threads that share a channel quad, then one fp64 atomic per channel sum
-        for (int r = 1; r < rows_per_pass; ++r) {
-            const float4 pp = s_p[r * quads + qi], qq = s_q[r * quads + qi];
-            p.x += pp.x; p.y += pp.y; p.z += pp.z; p.w += pp.w;
-            q.x += qq.x; q.y += qq.y; q.z += qq.z; q.w += qq.w;
-        }
+        for (int r = 1; r < rows_per_pass; ++r)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                pd[j] += s_p[r * quads + qi][j];
+                qd[j] += s_q[r * quads + qi][j];
+            }
         double* dst = acc + (size_t)(blockIdx.x % LN_GN_REPLICAS) * 2 * c + 8 * qi;
-        atomicAdd(dst + 0, (double)p.x); atomicAdd(dst + 1, (double)q.x);
-        atomicAdd(dst + 2, (double)p.y); atomicAdd(dst + 3, (double)q.y);
-        atomicAdd(dst + 4, (double)p.z); atomicAdd(dst + 5, (double)q.z);
-        atomicAdd(dst + 6, (double)p.w); atomicAdd(dst + 7, (double)q.w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            atomicAdd(dst + 2 * j, pd[j]);
+            atomicAdd(dst + 2 * j + 1, qd[j]);
+        }
     }
 }
 
@@ -114,11 +138,11 @@ __device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ 
         }
         const double cnt = (double)m * cg;
         const double mean = s / cnt;
-        double var = ss / cnt - mean * mean;
+        double var = ss / cnt - mean * mean;  // (fp64 sums of fp32 data: the cancellation costs 2^-53 mean^2 / var)
         if (var < 0.0) var = 0.0;
         const float rstd = (float)(1.0 / sqrt(var + (double)eps));
         const float a = (gamma ? gamma[col] : 1.f) * rstd;
-        const float b = (beta ? beta[col] : 0.f) - (float)mean * a;
+        const float b = (float)((beta ? (double)beta[col] : 0.0) - mean * (double)a);
         s_a[col] = a;
         s_b[col] = b;
         if (blockIdx.x == 0) {
@@ -165,7 +189,7 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// dx = gy' * gamma * rstd + x * c2[g] + c3[g];   block 0 writes dgamma = (ds - db*mean)*rstd, dbeta = db
+// dx = gy' * gamma * rstd + x * c2[g] + c3[g];   block 0 writes dgamma = (ds - db*mean)*rstd, dbeta = db   (all of it in fp64)
 __global__ void __launch_bounds__(256)
     k_gn_backward_apply(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
                         const float* __restrict__ gamma, const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m,

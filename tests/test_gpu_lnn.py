@@ -124,13 +124,13 @@ def test_group_norm_kernels_match_torch(m, c, relu):
     b64 = mod.gn.bias.detach().double().cpu().requires_grad_(True)
     ref = torch.nn.functional.group_norm(x64.t().unsqueeze(0), mod.gn.num_groups, w64, b64, mod.gn.eps).squeeze(0).t()
     if relu:
-        ref = torch.relu(ref)
+        # the mask of the fused ReLU is the kernel's own (an element on the kink within rounding may fall on either side of it): with
+        # it every element of every gradient is compared (tests/test_gpu_dense_layers.py derives the bounds element by element)
+        torch.testing.assert_close(y.detach().cpu().double(), torch.relu(ref).detach(), rtol=1e-4, atol=1e-5)
+        ref = ref * (y.detach() > 0).cpu().double()
     ref.backward(gy.double().cpu())
     torch.testing.assert_close(y.detach().cpu().double(), ref.detach(), rtol=1e-4, atol=1e-5)
-    # elements that sit on the ReLU kink within rounding can flip their mask: compare gradients in aggregate too
-    gx = x.grad.cpu().double()
-    mism = (gx - x64.grad).abs() > 1e-4 + 1e-3 * x64.grad.abs()
-    assert mism.float().mean() < 1e-4, float(mism.float().mean())
+    torch.testing.assert_close(x.grad.cpu().double(), x64.grad, rtol=1e-3, atol=1e-4)
     torch.testing.assert_close(mod.gn.weight.grad.cpu().double(), w64.grad, rtol=2e-4, atol=2e-4 * float(w64.grad.abs().max()))
     torch.testing.assert_close(mod.gn.bias.grad.cpu().double(), b64.grad, rtol=2e-4, atol=2e-4 * float(b64.grad.abs().max()))
 
