@@ -512,6 +512,26 @@ int ln_nll_forward(const float* log_probs, const long long* target, long long n,
 int ln_nll_backward(const long long* target, const float* grad_loss, const float* loss_count, long long n, int classes,
                     long long ignore_index, float* grad_log_probs, void* stream);
 
+/* Lovasz-Softmax loss of the training loop (ln_train.py:156-158, lovasz_loss.py:17-57) over log_probs [n, classes] float and target
+ * [n] int64 (labels outside [0, classes) are clamped), for all classes at once.  Per class c: p = exp(log_probs[:, c]),
+ * fg_i = [label_i == c], e_i = |fg_i - p_i|; the errors in descending order, EQUAL ERRORS BY ASCENDING POINT INDEX (a stable sort);
+ * loss_c = sum_k e_(k) g_k with the Jaccard gradient in closed form — G = #fg, U = G + #background and I = G - #foreground among
+ * the first k+1 elements: g_k = 1 / U (element k foreground), I / (U (U - 1)) (background).  A class counts when G > 0 and
+ * c != ignore_index (pass a value no class takes, e.g. LLONG_MIN, for none; points that carry the ignore label still act as
+ * background of the other classes).  reduction 0: loss[0] = sum over the counting classes / max(#counting, 1); 1: the sum.
+ * per_class [classes] (may be NULL): loss_c, 0 for a class that does not count.  p below the smallest normal float counts as 0.
+ * The forward call also writes every element of dloss_dlogp [n, classes] = d loss / d log_probs = scale_c s g_rank(i) p_ic
+ * (s = -1 foreground, +1 background; scale_c = 0 for a class that does not count, else 1 (sum) or 1 / #counting (mean));
+ * ln_lovasz_backward multiplies it by grad_loss[0] into grad_log_probs [n, classes] (one elementwise launch).
+ * Limits (LN_ERR_ARG otherwise, nothing launched): 1 <= classes <= 1024, n >= 0, n * classes < 2^31; n == 0 sets loss (and
+ * per_class) to 0 and runs no sort.  All scratch is the caller's workspace (ln_lovasz_workspace_bytes: a pure host function);
+ * no host synchronisation, no allocation: safe inside a stream capture.  Every sum is taken in a fixed order and there are no
+ * float atomics: loss and gradient are bitwise reproducible. */
+size_t ln_lovasz_workspace_bytes(long long n, int classes);
+int ln_lovasz_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index, int reduction,
+                      void* workspace, size_t workspace_bytes, float* loss, float* per_class, float* dloss_dlogp, void* stream);
+int ln_lovasz_backward(const float* dloss_dlogp, const float* grad_loss, long long n, int classes, float* grad_log_probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

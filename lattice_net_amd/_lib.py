@@ -148,6 +148,9 @@ SIGNATURES = {
     "ln_nll_workspace_bytes": (_sz, []),
     "ln_nll_forward": (_i, [_vp, _vp, _ll, _i, _ll, _vp, _sz, _vp, _vp]),
     "ln_nll_backward": (_i, [_vp, _vp, _vp, _ll, _i, _ll, _vp, _vp]),
+    "ln_lovasz_workspace_bytes": (_sz, [_ll, _i]),
+    "ln_lovasz_forward": (_i, [_vp, _vp, _ll, _i, _ll, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ln_lovasz_backward": (_i, [_vp, _vp, _ll, _i, _vp, _vp]),
     "ln_max_centre_forward": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp]),
     "ln_max_centre_backward_workspace_bytes": (_sz, [_ll, _i, _i]),
     "ln_max_centre_backward": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -1,0 +1,378 @@
+// Lovasz-Softmax loss of the training loop (ln_train.py:156-158, lovasz_loss.py:17-57; Berman et al., CVPR 2018) over
+// log-probabilities [n, C] and labels [n], all classes at once, forward value and the gradient wrt the log-probabilities.
+//
+// Per class c:  p_i = exp(lp[i, c]),  fg_i = [clamp(y_i, 0, C-1) == c],  e_i = |fg_i - p_i|;  the errors in DESCENDING order, equal
+// errors by ASCENDING point index (a stable sort);  loss_c = sum_k e_(k) g_k  with g the discrete gradient of the Jaccard loss along
+// that order.  With G = #fg, F_k / B_k = foreground / background elements among the first k+1, U = G + B_k, I = G - F_k:
+//        g_k = 1 / U               (element k foreground)
+//        g_k = I / (U (U - 1))     (element k background)
+// — the closed form of J_k - J_{k-1}, J_k = 1 - I/U: no difference of two O(1) numbers that agree in all but their last digits.
+// A class counts when G > 0 and c != ignore_index;  loss = sum over the counting classes (/ max(#counting, 1) for "mean").
+//
+// Arithmetic, pinned so that tests/lovasz_reference.py can count its roundings:
+//   p = expf(lp), a result below the smallest normal float counts as 0 (whether expf returns subnormals is the math library's
+//   business);  e = p for background and |expm1f(lp)| for foreground (1 - p cancels when the prediction is right: expm1f keeps e to
+//   an ulp);  U (U - 1) in 64-bit integers, converted once;  IEEE division;  no contraction (-ffp-contract=off).
+//
+// Stages (every sum in a fixed order, no float atomics: loss and gradient are bitwise reproducible):
+//   k_lovasz_keys      [n, C] -> class-major (key, payload): key = 0x7FFFFFFF - bits(e) (the bits of a non-negative float are monotone
+//                      as an integer, so ascending keys = descending errors), payload = point | fg << 31
+//   4 x { k_lovasz_hist, k_lovasz_scan, k_lovasz_scatter }   stable LSD radix sort of the C segments, 8 bits per pass; bit 31 of
+//                      the key is 0, so four passes cover every non-negative float (also inf / NaN of wild inputs: no index
+//                      depends on a value being in [0, 1]).  Points arrive in index order and every pass is stable: the tie rule.
+//   k_lovasz_fg_count, k_lovasz_scan    foreground count of every tile of the sorted order, exclusive scan per class (its total: G)
+//   k_lovasz_dot       F_k from the tile base + wave ballots, g_k, the tile's sum of e g, and the coefficient
+//                      scale_c s g p scattered to dloss_dlogp[point, c]  (s = -1 foreground, +1 background)
+//   k_lovasz_finish    tile sums -> per-class losses -> loss
+//   k_lovasz_backward  grad_log_probs = grad_loss * dloss_dlogp
+#include "ln_common.h"
+
+#define LN_LV_THREADS 256
+#define LN_LV_WAVES (LN_LV_THREADS / 64)
+#define LN_LV_IPT 8                                  // items per thread
+#define LN_LV_TILE (LN_LV_THREADS * LN_LV_IPT)       // items per workgroup: 2048
+#define LN_LV_SCAN_THREADS 1024
+#define LN_LV_PASSES 4
+#define LN_LV_MAX_CLASSES 1024
+#define LN_LV_FG 0x80000000u
+
+__device__ __forceinline__ float ln_lv_prob(float lp) {
+    const float p = expf(lp);
+    return p < 1.17549435e-38f ? 0.f : p;
+}
+__device__ __forceinline__ float ln_lv_error(float lp, bool fg) { return fg ? fabsf(expm1f(lp)) : ln_lv_prob(lp); }
+
+// item `j` of this thread inside tile `b`: waves own contiguous runs of 64 * IPT items, a round of a wave is 64 consecutive items —
+// position order = (wave, round, lane), loads and stores of a round are coalesced
+__device__ __forceinline__ long long ln_lv_item(int b, int j) {
+    return (long long)b * LN_LV_TILE + (threadIdx.x >> 6) * (64 * LN_LV_IPT) + j * 64 + (threadIdx.x & 63);
+}
+
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_keys(const float* __restrict__ lp, const long long* __restrict__ target, long long n, int C, uint32_t* __restrict__ keys,
+                  uint32_t* __restrict__ pay) {
+    const long long i = (long long)blockIdx.x * LN_LV_THREADS + threadIdx.x;
+    const int c = blockIdx.y;
+    if (i >= n) return;
+    const long long t = target[i];
+    const long long tc = t < 0 ? 0 : (t >= C ? C - 1 : t);
+    const bool fg = tc == c;
+    const float e = ln_lv_error(lp[i * C + c], fg);
+    keys[(long long)c * n + i] = 0x7FFFFFFFu - (__float_as_uint(e) & 0x7FFFFFFFu);
+    pay[(long long)c * n + i] = uint32_t(i) | (fg ? LN_LV_FG : 0u);
+}
+
+// digit histogram of every tile: hist[(c * 256 + digit) * nblk + b]
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_hist(const uint32_t* __restrict__ keys, long long n, int nblk, int shift, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t s_h[256];
+    const int b = blockIdx.x, c = blockIdx.y;
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t* k = keys + (long long)c * n;
+#pragma unroll
+    for (int j = 0; j < LN_LV_IPT; ++j) {
+        const long long pos = ln_lv_item(b, j);
+        if (pos < n) atomicAdd(&s_h[(k[pos] >> shift) & 255u], 1u);  // (integer: the order of the additions is immaterial)
+    }
+    __syncthreads();
+    hist[((long long)c * 256 + threadIdx.x) * nblk + b] = s_h[threadIdx.x];
+}
+
+// exclusive scan in place of `len` ints per class (one workgroup per class, contiguous chunk per thread); totals[c] = the sum
+__global__ void __launch_bounds__(LN_LV_SCAN_THREADS)
+    k_lovasz_scan(uint32_t* __restrict__ data, long long len, int* __restrict__ totals) {
+    __shared__ int s_tmp[LN_LV_SCAN_THREADS / 64];
+    uint32_t* d = data + (long long)blockIdx.x * len;
+    const long long chunk = (len + LN_LV_SCAN_THREADS - 1) / LN_LV_SCAN_THREADS;
+    const long long lo = threadIdx.x * chunk;
+    const long long hi = lo + chunk < len ? lo + chunk : len;
+    int sum = 0;
+    for (long long k = lo; k < hi; ++k) sum += int(d[k]);
+    int total;
+    int run = ln_block_excl_scan<LN_LV_SCAN_THREADS / 64>(sum, s_tmp, &total);
+    for (long long k = lo; k < hi; ++k) {
+        const int v = int(d[k]);
+        d[k] = uint32_t(run);
+        run += v;
+    }
+    if (totals && threadIdx.x == 0) totals[blockIdx.x] = total;
+}
+
+// one stable pass: an item goes to  (items of smaller digits) + (items of its digit in earlier tiles)  [both: the scanned hist]
+//                                 + (items of its digit earlier in this tile: earlier waves, earlier rounds, lower lanes)
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ pay_in, uint32_t* __restrict__ keys_out,
+                     uint32_t* __restrict__ pay_out, const uint32_t* __restrict__ hist, long long n, int nblk, int shift) {
+    __shared__ uint32_t s_cnt[LN_LV_WAVES][256];
+    const int b = blockIdx.x, c = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long seg = (long long)c * n;
+    uint32_t key[LN_LV_IPT], pl[LN_LV_IPT], rank[LN_LV_IPT];
+#pragma unroll
+    for (int j = 0; j < LN_LV_IPT; ++j) {
+        const long long pos = ln_lv_item(b, j);
+        key[j] = pos < n ? keys_in[seg + pos] : 0u;
+        pl[j] = pos < n ? pay_in[seg + pos] : 0u;
+    }
+#pragma unroll
+    for (int w = 0; w < LN_LV_WAVES; ++w) s_cnt[w][threadIdx.x] = 0;
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < LN_LV_IPT; ++j) {
+        const bool valid = ln_lv_item(b, j) < n;
+        const uint32_t d = (key[j] >> shift) & 255u;
+        unsigned long long peers = __ballot(valid);  // lanes of this round that hold the same digit
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const bool mine = (d >> bit) & 1u;
+            const unsigned long long m = __ballot(mine);
+            peers &= mine ? m : ~m;
+        }
+        rank[j] = 0;
+        if (valid) {
+            const uint32_t prior = s_cnt[wave][d];  // items of this digit in the wave's earlier rounds
+            rank[j] = prior + __popcll(peers & below);
+            // every peer has read before the lowest one writes: the LDS serves one wave's accesses in program order
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if ((peers & below) == 0) s_cnt[wave][d] = prior + __popcll(peers);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    {  // thread = digit: wave counts -> first destination of every wave's items of that digit
+        uint32_t run = hist[((long long)c * 256 + threadIdx.x) * nblk + b];
+#pragma unroll
+        for (int w = 0; w < LN_LV_WAVES; ++w) {
+            const uint32_t v = s_cnt[w][threadIdx.x];
+            s_cnt[w][threadIdx.x] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < LN_LV_IPT; ++j) {
+        if (ln_lv_item(b, j) >= n) continue;
+        const long long dst = (long long)s_cnt[wave][(key[j] >> shift) & 255u] + rank[j];
+        if (dst < n) {  // (always, by construction)
+            keys_out[seg + dst] = key[j];
+            pay_out[seg + dst] = pl[j];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_fg_count(const uint32_t* __restrict__ pay, long long n, int nblk, uint32_t* __restrict__ fgcnt) {
+    __shared__ int s_w[LN_LV_WAVES];
+    const int b = blockIdx.x, c = blockIdx.y;
+    const uint32_t* p = pay + (long long)c * n;
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < LN_LV_IPT; ++j) {
+        const long long pos = ln_lv_item(b, j);
+        const bool fg = pos < n && (p[pos] & LN_LV_FG);
+        cnt += __popcll(__ballot(fg));  // wave-uniform
+    }
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+#pragma unroll
+        for (int w = 0; w < LN_LV_WAVES; ++w) t += s_w[w];
+        fgcnt[(long long)c * nblk + b] = uint32_t(t);
+    }
+}
+
+// number of classes that count (G > 0, not the ignore class), by every thread of the workgroup
+__device__ __forceinline__ int ln_lv_counting(const int* __restrict__ G, int C, long long ignore_index, int* s_tmp) {
+    int mine = 0;
+    for (int k = threadIdx.x; k < C; k += LN_LV_THREADS) mine += (G[k] > 0 && k != ignore_index) ? 1 : 0;
+    int total;
+    (void)ln_block_excl_scan_256(mine, s_tmp, &total);
+    return total;
+}
+
+// fixed tree over a 256-thread workgroup: shuffle tree inside every wave, the four wave sums in order (valid in thread 0)
+__device__ __forceinline__ float ln_lv_block_sum(float x, float* s_w) {
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
+    __syncthreads();
+    float t = s_w[0];
+#pragma unroll
+    for (int w = 1; w < LN_LV_WAVES; ++w) t += s_w[w];
+    return t;
+}
+
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_dot(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pay, const uint32_t* __restrict__ fgbase,
+                 const int* __restrict__ G, const float* __restrict__ lp, long long n, int C, int nblk, long long ignore_index,
+                 int reduction, float* __restrict__ partial, float* __restrict__ dl) {
+    __shared__ int s_tmp[8];
+    __shared__ int s_fg[LN_LV_WAVES];
+    __shared__ float s_w[LN_LV_WAVES];
+    const int b = blockIdx.x, c = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long seg = (long long)c * n;
+    const int counting = ln_lv_counting(G, C, ignore_index, s_tmp);
+    const int Gc = G[c];
+    const bool counts = Gc > 0 && c != ignore_index;
+    const float scale = reduction == 0 ? 1.f / float(counting < 1 ? 1 : counting) : 1.f;
+    uint32_t key[LN_LV_IPT], pl[LN_LV_IPT];
+    unsigned long long fgmask[LN_LV_IPT];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < LN_LV_IPT; ++j) {
+        const long long pos = ln_lv_item(b, j);
+        key[j] = pos < n ? keys[seg + pos] : 0u;
+        pl[j] = pos < n ? pay[seg + pos] : 0u;
+        fgmask[j] = __ballot((pl[j] & LN_LV_FG) != 0);
+        mine += __popcll(fgmask[j]);
+    }
+    if (lane == 0) s_fg[wave] = mine;
+    __syncthreads();
+    long long F = fgbase[(long long)c * nblk + b];  // foreground elements in front of this wave's first item
+#pragma unroll
+    for (int w = 0; w < LN_LV_WAVES; ++w)
+        if (w < wave) F += s_fg[w];
+    const unsigned long long upto = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < LN_LV_IPT; ++j) {
+        const long long pos = ln_lv_item(b, j);
+        const long long Fk = F + __popcll(fgmask[j] & upto);  // inclusive
+        F += __popcll(fgmask[j]);
+        if (pos >= n) continue;
+        const bool fg = (pl[j] & LN_LV_FG) != 0;
+        const long long i = pl[j] & ~LN_LV_FG;
+        if (i >= n) continue;  // (never: the payload is a point index)
+        float coef = 0.f;
+        if (counts) {
+            const long long U = Gc + (pos + 1 - Fk), I = Gc - Fk;
+            const float g = fg ? 1.f / float(U) : float(I) / float((unsigned long long)(U * (U - 1)));
+            const float e = __uint_as_float(0x7FFFFFFFu - key[j]);
+            acc += e * g;
+            coef = ((fg ? -g : g) * ln_lv_prob(lp[i * C + c])) * scale;
+        }
+        dl[i * C + c] = coef;
+    }
+    const float t = ln_lv_block_sum(acc, s_w);
+    if (threadIdx.x == 0) partial[(long long)c * nblk + b] = t;
+}
+
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_finish(const float* __restrict__ partial, const int* __restrict__ G, int nblk, int C, long long ignore_index, int reduction,
+                    float* __restrict__ loss, float* __restrict__ per_class) {
+    __shared__ float s_w[LN_LV_WAVES];
+    float total = 0.f;
+    int counting = 0;
+    for (int c = 0; c < C; ++c) {
+        float acc = 0.f;
+        for (int k = threadIdx.x; k < nblk; k += LN_LV_THREADS) acc += partial[(long long)c * nblk + k];
+        const float pc = ln_lv_block_sum(acc, s_w);
+        if (threadIdx.x == 0) {
+            const bool counts = G[c] > 0 && c != ignore_index;
+            if (counts) {
+                total += pc;
+                ++counting;
+            }
+            if (per_class) per_class[c] = counts ? pc : 0.f;
+        }
+    }
+    if (threadIdx.x == 0) loss[0] = reduction == 0 ? total / float(counting < 1 ? 1 : counting) : total;
+}
+
+__global__ void __launch_bounds__(256)
+    k_lovasz_backward(const float* __restrict__ dl, const float* __restrict__ grad_loss, long long total, float* __restrict__ out) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g < total) out[g] = grad_loss[0] * dl[g];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+struct LnLovaszLayout {
+    int nblk;
+    size_t keys[2], pay[2], hist, fgcnt, G, partial, bytes;
+};
+size_t ln_lv_align(size_t x) { return (x + 255) & ~size_t(255); }
+LnLovaszLayout ln_lv_layout(long long n, int classes) {
+    LnLovaszLayout L;
+    const size_t N = n > 0 ? size_t(n) : 0, C = classes > 0 ? size_t(classes) : 0;
+    L.nblk = int((N + LN_LV_TILE - 1) / LN_LV_TILE);
+    size_t at = 0;
+    for (int k = 0; k < 2; ++k) {
+        L.keys[k] = at;
+        at = ln_lv_align(at + C * N * 4);
+        L.pay[k] = at;
+        at = ln_lv_align(at + C * N * 4);
+    }
+    L.hist = at;
+    at = ln_lv_align(at + C * 256 * size_t(L.nblk) * 4);
+    L.fgcnt = at;
+    at = ln_lv_align(at + C * size_t(L.nblk) * 4);
+    L.G = at;
+    at = ln_lv_align(at + C * 4);
+    L.partial = at;
+    at = ln_lv_align(at + C * size_t(L.nblk) * 4);
+    L.bytes = at + 256;
+    return L;
+}
+}  // namespace
+
+extern "C" size_t ln_lovasz_workspace_bytes(long long n, int classes) { return ln_lv_layout(n, classes).bytes; }
+
+extern "C" int ln_lovasz_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index,
+                                 int reduction, void* workspace, size_t workspace_bytes, float* loss, float* per_class,
+                                 float* dloss_dlogp, void* stream) {
+    LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_LV_MAX_CLASSES, LN_ERR_ARG, "ln_lovasz_forward: bad sizes (n >= 0, 1 <= classes <= %d)",
+               LN_LV_MAX_CLASSES);
+    LN_REQUIRE(n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_ARG, "ln_lovasz_forward: n * classes must stay below 2^31");
+    LN_REQUIRE(reduction == 0 || reduction == 1, LN_ERR_ARG, "ln_lovasz_forward: reduction is 0 (mean) or 1 (sum)");
+    LN_REQUIRE(loss, LN_ERR_ARG, "ln_lovasz_forward: null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {  // no class is present: the loss is 0
+        int rc = ln_zero_async(loss, sizeof(float), st);
+        if (rc == LN_OK && per_class) rc = ln_zero_async(per_class, size_t(classes) * sizeof(float), st);
+        return rc;
+    }
+    LN_REQUIRE(log_probs && target && dloss_dlogp, LN_ERR_ARG, "ln_lovasz_forward: null buffer");
+    const LnLovaszLayout L = ln_lv_layout(n, classes);
+    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_lovasz_forward: null / small workspace (%zu bytes needed)", L.bytes);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(ws + L.keys[0]), reinterpret_cast<uint32_t*>(ws + L.keys[1])};
+    uint32_t* pay[2] = {reinterpret_cast<uint32_t*>(ws + L.pay[0]), reinterpret_cast<uint32_t*>(ws + L.pay[1])};
+    uint32_t* hist = reinterpret_cast<uint32_t*>(ws + L.hist);
+    uint32_t* fgcnt = reinterpret_cast<uint32_t*>(ws + L.fgcnt);
+    int* G = reinterpret_cast<int*>(ws + L.G);
+    float* partial = reinterpret_cast<float*>(ws + L.partial);
+    const dim3 tiles(L.nblk, classes), thr(LN_LV_THREADS);
+    LN_LAUNCH("k_lovasz_keys", k_lovasz_keys, dim3(ln_div_up(n, LN_LV_THREADS), classes), thr, 0, st, log_probs, target, n, classes, keys[0],
+              pay[0]);
+    for (int pass = 0; pass < LN_LV_PASSES; ++pass) {
+        const int in = pass & 1, out = in ^ 1, shift = 8 * pass;
+        LN_LAUNCH("k_lovasz_hist", k_lovasz_hist, tiles, thr, 0, st, keys[in], n, L.nblk, shift, hist);
+        LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, dim3(classes), dim3(LN_LV_SCAN_THREADS), 0, st, hist, 256ll * L.nblk, (int*)nullptr);
+        LN_LAUNCH("k_lovasz_scatter", k_lovasz_scatter, tiles, thr, 0, st, keys[in], pay[in], keys[out], pay[out], hist, n, L.nblk, shift);
+    }
+    static_assert(LN_LV_PASSES % 2 == 0, "the sorted order ends in buffer 0");
+    LN_LAUNCH("k_lovasz_fg_count", k_lovasz_fg_count, tiles, thr, 0, st, pay[0], n, L.nblk, fgcnt);
+    LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, dim3(classes), dim3(LN_LV_SCAN_THREADS), 0, st, fgcnt, (long long)L.nblk, G);
+    LN_LAUNCH("k_lovasz_dot", k_lovasz_dot, tiles, thr, 0, st, keys[0], pay[0], fgcnt, G, log_probs, n, classes, L.nblk, ignore_index, reduction,
+              partial, dloss_dlogp);
+    LN_LAUNCH("k_lovasz_finish", k_lovasz_finish, dim3(1), thr, 0, st, partial, G, L.nblk, classes, ignore_index, reduction, loss, per_class);
+    return ln_check_launch("ln_lovasz_forward");
+}
+
+extern "C" int ln_lovasz_backward(const float* dloss_dlogp, const float* grad_loss, long long n, int classes, float* grad_log_probs,
+                                  void* stream) {
+    LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_LV_MAX_CLASSES && n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_ARG,
+               "ln_lovasz_backward: bad sizes");
+    if (n == 0) return LN_OK;
+    LN_REQUIRE(dloss_dlogp && grad_loss && grad_log_probs, LN_ERR_ARG, "ln_lovasz_backward: null buffer");
+    LN_LAUNCH("k_lovasz_backward", k_lovasz_backward, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, dloss_dlogp, grad_loss,
+              n * classes, grad_log_probs);
+    return ln_check_launch("ln_lovasz_backward");
+}

@@ -4,8 +4,9 @@ latticenet_py/lattice/lovasz_loss.py:17-57) and the intersection-over-union book
 The loss is the Lovasz extension of the per-class Jaccard index (Berman et al., CVPR 2018): for class c the errors
 e_i = |1[y_i = c] - p_i(c)| are sorted in decreasing order and dotted with the discrete gradient of the Jaccard loss
 along that order; classes absent from the cloud and the ignore class are skipped, the rest averaged.  All classes are
-processed at once ([N, C] sort / cumsum) with no host synchronisation — the reference loops over classes and reads one
-scalar per class back to the host.
+processed at once with no host synchronisation — the reference loops over classes and reads one scalar per class back to
+the host.  With FUSED_LOVASZ set, float32 CUDA inputs take the HIP kernels of csrc/ln_lovasz.hip; everything else, and everything while
+the flag is off, the torch form ([C, N] sort / cumsum).
 """
 from __future__ import annotations
 
@@ -18,6 +19,9 @@ __all__ = ["GeneralizedSoftDiceLoss", "LovaszSoftmax", "Scores", "nll_loss_gathe
 
 _NO_LABEL = -(1 << 62)  # "no ignore_index": a value no label takes
 FUSED_NLL = True
+FUSED_LOVASZ = False  # off until tools/bench_losses.py has shown the kernels below the torch form on an MI355X
+_LOVASZ_MAX_CLASSES = 1024  # limits of ln_lovasz_forward (include/latticenet_hip.h)
+_LOVASZ_MAX_ELEMENTS = 1 << 31
 
 
 class _NllFunction(torch.autograd.Function):
@@ -49,6 +53,36 @@ class _NllFunction(torch.autograd.Function):
         _lib.check(_lib.load().ln_nll_backward(_lib.ptr(target), _lib.ptr(g), _lib.ptr(loss_count), n, c, ctx.ignore_index, _lib.ptr(grad),
                                                _lib.stream_ptr(g.device)), "ln_nll_backward")
         return grad, None, None
+
+
+class _LovaszFunction(torch.autograd.Function):
+    """csrc/ln_lovasz.hip: per-class stable radix sort of the errors, Jaccard gradient in closed form, sums in a fixed order.  The
+    forward call leaves d loss / d log_probs in memory; backward is one elementwise launch."""
+
+    @staticmethod
+    def forward(ctx, log_probs, target, ignore_index, reduction):
+        from . import _lib
+        lib = _lib.load()
+        n, c = log_probs.shape
+        dev = log_probs.device
+        ws = torch.empty((lib.ln_lovasz_workspace_bytes(n, c),), dtype=torch.uint8, device=dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        dloss = torch.empty((n, c), dtype=torch.float32, device=dev)
+        _lib.check(lib.ln_lovasz_forward(_lib.ptr(log_probs), _lib.ptr(target), n, c, ignore_index, reduction, _lib.ptr(ws), ws.numel(),
+                                         _lib.ptr(loss), None, _lib.ptr(dloss), _lib.stream_ptr(dev)), "ln_lovasz_forward")
+        ctx.save_for_backward(dloss)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        from . import _lib
+        dloss, = ctx.saved_tensors
+        n, c = dloss.shape
+        g = grad_loss.contiguous().float()
+        grad = torch.empty_like(dloss)
+        _lib.check(_lib.load().ln_lovasz_backward(_lib.ptr(dloss), _lib.ptr(g), n, c, _lib.ptr(grad), _lib.stream_ptr(g.device)),
+                   "ln_lovasz_backward")
+        return grad, None, None, None
 
 
 def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=None) -> torch.Tensor:
@@ -102,6 +136,12 @@ class LovaszSoftmax(torch.nn.Module):
         """inputs: log-probabilities [N, C] (the model's log-softmax, ln_train.py:156); targets: int64 [N]."""
         if inputs.dim() != 2:
             raise ValueError("LovaszSoftmax expects [N, C] log-probabilities")
+        if FUSED_LOVASZ and self.reduction in ("mean", "sum") and inputs.is_cuda and inputs.dtype == torch.float32 and \
+                inputs.is_contiguous() and targets.is_cuda and targets.dtype == torch.int64 and targets.numel() == inputs.shape[0] and \
+                inputs.shape[0] >= 1 and 1 <= inputs.shape[1] <= _LOVASZ_MAX_CLASSES and inputs.numel() < _LOVASZ_MAX_ELEMENTS:
+            # equal errors are ordered by point index and the Jaccard gradient is taken in closed form (csrc/ln_lovasz.hip)
+            return _LovaszFunction.apply(inputs, targets.reshape(-1).contiguous(), _NO_LABEL if self.ignore_index is None else int(self.ignore_index),
+                                         0 if self.reduction == "mean" else 1)
         probs = inputs.exp()
         n, c = probs.shape
         targets = targets.reshape(-1)
