@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import lattice_oracle as O
+from tests.point_reference import assert_sc_parameter_gradients
 from tests.test_gpu_segment_reduce import assert_reduce_close, row_counts
 
 pytestmark = pytest.mark.gpu
@@ -208,6 +209,7 @@ def test_f11_slice_classify_kitti_head(golden, v):
     close(N(gdw), g[f"g_delta_w_{v}"])
     close(N(glw), g[f"g_lin_w_{v}"])
     close(N(glb), g[f"g_lin_b_{v}"])
+    assert_sc_parameter_gradients(gdw, glw, glb, g["grad_logits"], g[f"lattice_values_{v}"], g["delta_w"], g[f"lin_w_{v}"], idx, w, 3, what=f"F11 V={v}")
 
 
 def test_f6_slice_classify(golden):
@@ -228,6 +230,7 @@ def test_f6_slice_classify(golden):
     close(N(gdw), g["g_delta_w"])
     close(N(glw), g["g_lin_w"])
     close(N(glb), g["g_lin_b"])
+    assert_sc_parameter_gradients(gdw, glw, glb, g["grad_logits"], g["lattice_values"], g["delta_w"], g["lin_w"], idx, w, 3, what="F6")
 
 
 def test_f8_pos_dim_2(golden):

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import lattice_oracle as O
+from tests.point_reference import assert_sc_parameter_gradients
 from tests.test_gpu_segment_reduce import assert_reduce_close, row_counts
 
 pytestmark = pytest.mark.gpu
@@ -111,6 +112,7 @@ def test_slice_classify_autograd_against_oracle(n, v, c):
     close(N(dw.grad), gd)
     close(N(lw.grad), gw)
     close(N(lb.grad), gb)
+    assert_sc_parameter_gradients(dw.grad, lw.grad, lb.grad, gl_np, vals_np, dw_np, lw_np, oidx, ow, 3, what=f"n={n} V={v} C={c}")
     # the C entry point can also scatter the lattice-value gradient itself (callers without a CSR adjacency)
     import ctypes as C
     from lattice_net_amd import _lib
@@ -564,3 +566,4 @@ def test_slice_classify_other_lattice_dimensions(d, n, v, c):
     close(N(dw.grad), gd)
     close(N(lw.grad), gw)
     close(N(lb.grad), gb)
+    assert_sc_parameter_gradients(dw.grad, lw.grad, lb.grad, gl_np, vals_np, dw_np, lw_np, oidx, ow, d, what=f"d={d} n={n} V={v} C={c}")
