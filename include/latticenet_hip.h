@@ -450,6 +450,35 @@ int ln_group_norm_backward_rows(const float* x, const float* grad_y, const float
                                 int channels, int groups, int relu, float* grad_x, float* grad_gamma, float* grad_beta, void* workspace,
                                 size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, const int* rows_device, void* stream);
 
+/* BatchNorm (+ optional fused ReLU) of BatchNormLatticeModule / BnReluConv (lattice_modules.py:570-583, 988-1009: torch.nn.BatchNorm1d
+ * on the [m, channels] values), with the device-side row count of the _rows calls above: n = min(m, *rows_device) rows count (n = m
+ * when rows_device is NULL), rows beyond n are written as zeros (y, grad_x) and contribute to nothing.
+ * training != 0: statistics per channel over the n live rows (GroupNorm with one channel per group: the same sums, biased variance
+ *           clamped at 0);  y = act(x * a[c] + b[c]),  a = gamma * rstd[c],  b = beta - mean[c] * a;  writes mean_rstd[2 * channels]
+ *           (batch means then rstds) and scale_shift[2 * channels] (a then b) for the backward call, and moves the running statistics
+ *           in place, with no host readback:  running_mean = (1 - momentum) running_mean + momentum mean,  running_var = (1 - momentum)
+ *           running_var + momentum var n / (n - 1)  (unbiased, as torch), each formed in fp64 and rounded to fp32 once.
+ *           n < 2: the running statistics keep their bits; the single live row has variance 0 and rstd = 1 / sqrt(eps), i.e. y =
+ *           act(beta) up to rounding; n = 0 writes only zeros.  running_mean == running_var == NULL (track_running_stats=False):
+ *           nothing is updated.
+ * training == 0: the running statistics ARE the statistics (both required, LN_ERR_ARG otherwise) and are never written, by the forward
+ *           or by the backward call:  a = gamma / sqrt(running_var + eps),  b = beta - running_mean * a  (rstd and b formed in fp64 and
+ *           rounded once); mean_rstd holds (running means, rstds).  One launch, no sums; `workspace` is not touched (it may be NULL) by
+ *           the forward call.  The backward call always needs the workspace, in either mode (its sums for grad_gamma / grad_beta).
+ * backward: training: grad_x = gy' gamma rstd + x c2 + c3,  grad_gamma = (ds - db mean) rstd,  grad_beta = db  (the GroupNorm formula
+ *           at groups == channels);  evaluation: grad_x = gy' a, grad_gamma / grad_beta the same expressions with the running mean.
+ *           gy' = grad_y masked by fl(fl(x a) + b) > 0 with ReLU.  `training` must be what the forward call was given.
+ * gamma, beta, running_mean, running_var, grad_gamma, grad_beta and rows_device may be NULL.  Limits, workspace and the next_workspace
+ * alternation as for GroupNorm: float32, channels % 4 == 0, channels <= 1024 (LN_ERR_UNSUPPORTED), m >= 1, x / y / grad tensors 16-byte
+ * aligned (LN_ERR_ARG); a rejected call launches nothing. */
+size_t ln_batch_norm_workspace_bytes(int channels);
+int ln_batch_norm_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int m, int channels,
+                          float eps, double momentum, int training, int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace,
+                          size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, const int* rows_device, void* stream);
+int ln_batch_norm_backward(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd, const float* scale_shift, int m,
+                           int channels, int training, int relu, float* grad_x, float* grad_gamma, float* grad_beta, void* workspace,
+                           size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, const int* rows_device, void* stream);
+
 /* ---- max-centring of the gathered simplex rows in the DeformSlice head ------------------------------------------
  * Replaces the torch broadcasting at lattice_modules.py:525-529 (`rowified -= gamma * max_vals + beta`, max over the
  * d+1 vertices of a simplex) and its autograd backward, whose two reductions over the N points dominate it.

@@ -182,6 +182,10 @@ class CapturedNetworkStep:
          after a replay `p.grad` holds that step's gradients; the optimizer runs outside the graph, or inside with `optimizer=`.
          Training loop: `with torch.cuda.stream(cap.stream): for ...: cap.launch(); optimizer.step()` (see launch()).
 
+    BatchNorm blocks (BatchNormLatticeModule, BnReluConv) run in this mode too: their kernels read the same device counter.  Their
+    state moves as under any torch CUDA graph: the eager calibration step(s) and the 2-3 warm-up iterations each advance the running
+    statistics and `num_batches_tracked` once, and so does every replay (a model in training mode; evaluation mode writes neither).
+
     `step` must read its inputs (positions, values, targets) from tensors that stay alive — overwrite them in place to feed another
     cloud of the same size — set `p.grad = None` itself is NOT needed (done here), and must not synchronise."""
 

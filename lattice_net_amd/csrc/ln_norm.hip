@@ -350,3 +350,230 @@ extern "C" int ln_group_norm_backward_rows(const float* x, const float* grad_y, 
               int(next_workspace_bytes / sizeof(double)), rows_device);
     return ln_check_launch("ln_group_norm_backward");
 }
+
+// ---- BatchNorm (+ fused ReLU) over the same [M, C] layout: GroupNorm with one channel per group, plus running statistics ----------
+// Training: k_gn_stats gives the fp64 channel sums exactly as for GroupNorm (same summation, same bounds), k_bn_apply turns them into
+// scale / shift and moves the running statistics on the device; the backward is k_gn_backward_apply at groups == channels.
+// Evaluation: the statistics are the running ones, constants of the step: one launch forward; backward dx = gy' * a, and the
+// parameter gradients from the same k_gn_stats sums.
+
+// the two fp64 sums of channel `col` over the accumulator replicas, added in replica order (the order of ln_gn_channel_affine), eight
+// loads in flight at a time
+__device__ __forceinline__ void ln_bn_channel_sums(const double* __restrict__ acc, int c, int col, double& s0, double& s1) {
+    s0 = 0.0;
+    s1 = 0.0;
+    for (int r0 = 0; r0 < LN_GN_REPLICAS; r0 += 8) {
+        double v0[8], v1[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            v0[r] = acc[(size_t)(r0 + r) * 2 * c + 2 * col];
+            v1[r] = acc[(size_t)(r0 + r) * 2 * c + 2 * col + 1];
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            s0 += v0[r];
+            s1 += v1[r];
+        }
+    }
+}
+
+// y = act(x * a[c] + b[c]) over the first m rows, zeros in the rows from m to m_tensor
+__device__ __forceinline__ void ln_bn_apply_rows(const float* __restrict__ x, const float* s_a, const float* s_b, int m, int m_tensor, int c,
+                                                 int relu, float* __restrict__ y) {
+    const long long total4 = (long long)m * c / 4;  // c % 4 == 0 checked by the host
+    const long long tensor4 = (long long)m_tensor * c / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = total4 + (long long)blockIdx.x * 256 + threadIdx.x; i < tensor4; i += stride)
+        reinterpret_cast<float4*>(y)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
+        const int col = int((i * 4) % c);
+        float4 v = reinterpret_cast<const float4*>(x)[i];
+        v.x = v.x * s_a[col] + s_b[col];
+        v.y = v.y * s_a[col + 1] + s_b[col + 1];
+        v.z = v.z * s_a[col + 2] + s_b[col + 2];
+        v.w = v.w * s_a[col + 3] + s_b[col + 3];
+        if (relu) {
+            v.x = fmaxf(v.x, 0.f);
+            v.y = fmaxf(v.y, 0.f);
+            v.z = fmaxf(v.z, 0.f);
+            v.w = fmaxf(v.w, 0.f);
+        }
+        reinterpret_cast<float4*>(y)[i] = v;
+    }
+}
+
+// Training forward.  Every workgroup rebuilds a = gamma * rstd, b = beta - mean * a from the fp64 channel sums (biased variance, clamped
+// at 0; n = live rows); block 0 publishes mean_rstd / scale_shift and, with n >= 2, moves the running statistics (unbiased variance),
+// each formed in fp64 and rounded once.  With n < 2 the running statistics keep their bits.
+__global__ void __launch_bounds__(256)
+    k_bn_apply(const float* __restrict__ x, const double* __restrict__ acc, const float* __restrict__ gamma, const float* __restrict__ beta,
+               float* __restrict__ running_mean, float* __restrict__ running_var, int m, int c, float eps, double momentum, int relu,
+               float* __restrict__ y, float* __restrict__ mean_rstd, float* __restrict__ scale_shift, double* __restrict__ zero_next,
+               int zero_count, const int* __restrict__ rows_dev) {
+    __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
+    const int m_tensor = m;
+    if (rows_dev) m = max(0, min(m, *rows_dev));  // rows beyond the lattice: excluded from the statistics, written as zeros
+    if (zero_next && blockIdx.x == 0)  // the accumulators of the NEXT call (nobody is using them now: stream order)
+        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
+    const double cnt = m < 1 ? 1.0 : (double)m;  // (an empty lattice under a static row bound: all sums are zero)
+    for (int col = threadIdx.x; col < c; col += 256) {
+        double s, ss;
+        ln_bn_channel_sums(acc, c, col, s, ss);
+        const double mean = s / cnt;
+        double var = ss / cnt - mean * mean;  // (fp64 sums of fp32 data: the cancellation costs 2^-53 mean^2 / var)
+        if (var < 0.0) var = 0.0;
+        const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+        const float a = (gamma ? gamma[col] : 1.f) * rstd;
+        const float b = (float)((beta ? (double)beta[col] : 0.0) - mean * (double)a);
+        s_a[col] = a;
+        s_b[col] = b;
+        if (blockIdx.x == 0) {
+            mean_rstd[col] = (float)mean;
+            mean_rstd[c + col] = rstd;
+            scale_shift[col] = a;
+            scale_shift[c + col] = b;
+            if (running_mean && m >= 2) {  // (one row has no unbiased variance: nothing moves)
+                running_mean[col] = (float)((1.0 - momentum) * (double)running_mean[col] + momentum * mean);
+                running_var[col] = (float)((1.0 - momentum) * (double)running_var[col] + momentum * (var * (cnt / (cnt - 1.0))));
+            }
+        }
+    }
+    __syncthreads();
+    ln_bn_apply_rows(x, s_a, s_b, m, m_tensor, c, relu, y);
+}
+
+// Evaluation forward: a = gamma / sqrt(running_var + eps) (rstd formed in fp64, rounded once), b = beta - running_mean * a (fp64, rounded
+// once).  Reads the running statistics, never writes them.
+__global__ void __launch_bounds__(256)
+    k_bn_apply_eval(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                    const float* __restrict__ running_mean, const float* __restrict__ running_var, int m, int c, float eps, int relu,
+                    float* __restrict__ y, float* __restrict__ mean_rstd, float* __restrict__ scale_shift, double* __restrict__ zero_next,
+                    int zero_count, const int* __restrict__ rows_dev) {
+    __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
+    const int m_tensor = m;
+    if (rows_dev) m = max(0, min(m, *rows_dev));
+    if (zero_next && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
+    for (int col = threadIdx.x; col < c; col += 256) {
+        const float mean = running_mean[col];
+        const float rstd = (float)(1.0 / sqrt((double)running_var[col] + (double)eps));
+        const float a = (gamma ? gamma[col] : 1.f) * rstd;
+        const float b = (float)((beta ? (double)beta[col] : 0.0) - (double)mean * (double)a);
+        s_a[col] = a;
+        s_b[col] = b;
+        if (blockIdx.x == 0) {
+            mean_rstd[col] = mean;
+            mean_rstd[c + col] = rstd;
+            scale_shift[col] = a;
+            scale_shift[c + col] = b;
+        }
+    }
+    __syncthreads();
+    ln_bn_apply_rows(x, s_a, s_b, m, m_tensor, c, relu, y);
+}
+
+// Evaluation backward: dx = gy' * a;  block 0 writes dgamma = (ds - db * running_mean) * rstd, dbeta = db in fp64 from the k_gn_stats
+// sums (acc == nullptr: no parameter gradient is wanted and no sums were taken).
+__global__ void __launch_bounds__(256)
+    k_bn_backward_eval(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
+                       const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m, int c, int relu,
+                       float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta, double* __restrict__ zero_next,
+                       int zero_count, const int* __restrict__ rows_dev) {
+    __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
+    const int m_tensor = m;
+    if (rows_dev) m = max(0, min(m, *rows_dev));
+    if (zero_next && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
+    for (int col = threadIdx.x; col < c; col += 256) {
+        s_a[col] = scale_shift[col];
+        s_b[col] = scale_shift[c + col];
+        if (acc && blockIdx.x == 0) {
+            double ds, db;
+            ln_bn_channel_sums(acc, c, col, ds, db);
+            if (dgamma) dgamma[col] = (float)((ds - db * (double)mean_rstd[col]) * (double)mean_rstd[c + col]);
+            if (dbeta) dbeta[col] = (float)db;
+        }
+    }
+    __syncthreads();
+    const long long total4 = (long long)m * c / 4;
+    const long long tensor4 = (long long)m_tensor * c / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = total4 + (long long)blockIdx.x * 256 + threadIdx.x; i < tensor4; i += stride)
+        reinterpret_cast<float4*>(dx)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
+        const int col = int((i * 4) % c);
+        float4 g = reinterpret_cast<const float4*>(gy)[i];
+        if (relu) {
+            const float4 xv = reinterpret_cast<const float4*>(x)[i];
+            if (!(xv.x * s_a[col] + s_b[col] > 0.f)) g.x = 0.f;
+            if (!(xv.y * s_a[col + 1] + s_b[col + 1] > 0.f)) g.y = 0.f;
+            if (!(xv.z * s_a[col + 2] + s_b[col + 2] > 0.f)) g.z = 0.f;
+            if (!(xv.w * s_a[col + 3] + s_b[col + 3] > 0.f)) g.w = 0.f;
+        }
+        reinterpret_cast<float4*>(dx)[i] = make_float4(g.x * s_a[col], g.y * s_a[col + 1], g.z * s_a[col + 2], g.w * s_a[col + 3]);
+    }
+}
+
+extern "C" size_t ln_batch_norm_workspace_bytes(int channels) { return ln_group_norm_workspace_bytes(channels); }
+
+extern "C" int ln_batch_norm_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int m,
+                                     int channels, float eps, double momentum, int training, int relu, float* y, float* mean_rstd,
+                                     float* scale_shift, void* workspace, size_t workspace_bytes, void* next_workspace,
+                                     size_t next_workspace_bytes, const int* rows_device, void* stream) {
+    int rc = ln_gn_check("ln_batch_norm_forward", m, channels, channels);
+    if (rc) return rc;
+    LN_REQUIRE(x && y && mean_rstd && scale_shift, LN_ERR_ARG, "ln_batch_norm_forward: null buffer");
+    LN_REQUIRE(!running_mean == !running_var, LN_ERR_ARG, "ln_batch_norm_forward: running_mean and running_var come together or not at all");
+    LN_REQUIRE(training || running_mean, LN_ERR_ARG, "ln_batch_norm_forward: evaluation mode needs the running statistics");
+    LN_REQUIRE(!training || (workspace && workspace_bytes >= ln_batch_norm_workspace_bytes(channels)), LN_ERR_ARG,
+               "ln_batch_norm_forward: null or too small workspace");
+    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(next_workspace) & 7) == 0,
+               LN_ERR_ARG, "ln_batch_norm_forward: x / y must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    double* zero_next = static_cast<double*>(next_workspace);
+    const int zero_count = int(next_workspace_bytes / sizeof(double));
+    if (!training) {  // the running statistics are the statistics: no sums, `workspace` is not touched
+        LN_LAUNCH("k_bn_apply_eval", k_bn_apply_eval, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, gamma, beta,
+                  (const float*)running_mean, (const float*)running_var, m, channels, eps, relu, y, mean_rstd, scale_shift, zero_next, zero_count,
+                  rows_device);
+        return ln_check_launch("ln_batch_norm_forward");
+    }
+    double* acc = static_cast<double*>(workspace);
+    if (!next_workspace && ln_zero_async(acc, ln_batch_norm_workspace_bytes(channels), st) != LN_OK)
+        return ln_check_launch("ln_batch_norm_forward(memset)");
+    LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, 0, m,
+              channels, acc, rows_device);
+    LN_LAUNCH("k_bn_apply", k_bn_apply, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, (const double*)acc, gamma, beta, running_mean,
+              running_var, m, channels, eps, momentum, relu, y, mean_rstd, scale_shift, zero_next, zero_count, rows_device);
+    return ln_check_launch("ln_batch_norm_forward");
+}
+
+extern "C" int ln_batch_norm_backward(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd, const float* scale_shift,
+                                      int m, int channels, int training, int relu, float* grad_x, float* grad_gamma, float* grad_beta,
+                                      void* workspace, size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes,
+                                      const int* rows_device, void* stream) {
+    int rc = ln_gn_check("ln_batch_norm_backward", m, channels, channels);
+    if (rc) return rc;
+    LN_REQUIRE(x && grad_y && mean_rstd && scale_shift && grad_x && workspace && workspace_bytes >= ln_batch_norm_workspace_bytes(channels),
+               LN_ERR_ARG, "ln_batch_norm_backward: null buffer or workspace too small");
+    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(next_workspace)) & 7) == 0,
+               LN_ERR_ARG, "ln_batch_norm_backward: x / grad_y / grad_x must be 16-byte aligned");
+    if (training)  // GroupNorm with one channel per group: the same sums, the same formula (the arguments were checked above)
+        return ln_group_norm_backward_rows(x, grad_y, gamma, mean_rstd, scale_shift, m, channels, channels, relu, grad_x, grad_gamma, grad_beta,
+                                           workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device, stream);
+    hipStream_t st = (hipStream_t)stream;
+    double* acc = static_cast<double*>(workspace);
+    const bool sums = grad_gamma || grad_beta;  // (without parameter gradients dx = gy' * a needs no sum: `workspace` stays as it is)
+    if (sums) {
+        if (!next_workspace && ln_zero_async(acc, ln_batch_norm_workspace_bytes(channels), st) != LN_OK)
+            return ln_check_launch("ln_batch_norm_backward(memset)");
+        LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, grad_y, scale_shift, relu, m, channels, acc,
+                  rows_device);
+    }
+    LN_LAUNCH("k_bn_backward_eval", k_bn_backward_eval, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, grad_y,
+              sums ? (const double*)acc : (const double*)nullptr, mean_rstd, scale_shift, m, channels, relu, grad_x, grad_gamma, grad_beta,
+              static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device);
+    return ln_check_launch("ln_batch_norm_backward");
+}

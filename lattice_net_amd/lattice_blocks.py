@@ -4,7 +4,7 @@
 These are compositions of the lattice operator modules (lattice_modules.py) with plain torch layers; they contain
 no kernels of their own.  Class names, constructor arguments and sub-module attribute names follow the reference so
 that model definitions and `state_dict` keys carry over (`...conv1.norm.gn.weight`, `...coarse.weight`, ...).
-Every pre-activation block is one `_PreActBlock`: optional GroupNorm -> activation -> optional channel dropout ->
+Every pre-activation block is one `_PreActBlock`: optional GroupNorm / BatchNorm -> activation -> optional channel dropout ->
 the wrapped operator; the named classes only choose the pieces.
 """
 from __future__ import annotations
@@ -38,18 +38,21 @@ class DropoutLattice(torch.nn.Module):  # mods:26-43: drops whole channels of th
         return self.dropout(lv.t()[None, :, :, None])[0, :, :, 0].t()
 
 
+# Eager mode (no static rows): True sends BatchNormLatticeModule through the HIP kernels too.  Off until tools/bench_norms.py has shown
+# them below torch.nn.BatchNorm1d (+ ReLU) on an MI355X; static-rows mode always takes the kernels.
+FUSED_BATCH_NORM = False
+
+
 class BatchNormLatticeModule(torch.nn.Module):  # mods:570-583
     def __init__(self, nr_params: int, affine: bool = True, device="cuda"):
         super().__init__()
         self.bn = torch.nn.BatchNorm1d(num_features=nr_params, momentum=0.1, affine=affine).to(device)
 
-    def forward(self, lattice_values, lattice_py):
+    def forward(self, lattice_values, lattice_py, fuse_relu: bool = False):
+        """`fuse_relu`: the values returned, and installed in the lattice, are relu(norm(x)) — one pass on the HIP path; on the torch
+        path torch.relu follows the norm, the same numbers as a separate nn.ReLU behind this module."""
         _require_2d(lattice_values)
-        if lattice_py is not None and lattice_py.rows_device() is not None:
-            # static-rows mode: the value matrix is taller than its lattice and torch's BatchNorm would count the padding rows
-            raise ValueError("BatchNormLatticeModule cannot run in static-rows mode (its statistics would include the padded rows); "
-                             "use GroupNorm blocks, or run eagerly (set_static_rows(None))")
-        lattice_values = self.bn(lattice_values)
+        lattice_values = batch_norm_rows(lattice_values, self.bn, fuse_relu, lattice_py.rows_device() if lattice_py is not None else None)
         lattice_py.set_values(lattice_values)
         return lattice_values, lattice_py
 
@@ -208,6 +211,75 @@ def max_centre_rows(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) ->
     return x - (gamma * x.max(1, keepdim=True)[0] + beta)
 
 
+class BatchNormFunction(torch.autograd.Function):
+    """BatchNorm (+ optional fused ReLU) over an [M, C] value matrix on the HIP kernels of csrc/ln_norm.hip (ln_batch_norm_forward /
+    _backward).  `stats`: (running_mean, running_var) or None — buffers, not inputs of the Function: a training call moves them in
+    place on the device, an evaluation call (`training` False; needs them) normalises with them and writes nothing."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stats, momentum, eps, training, relu, rows_dev=None):
+        lib = _lib.load()
+        x = x.contiguous()
+        m, c = x.shape
+        y = torch.empty_like(x)
+        mean_rstd = torch.empty((2 * c,), dtype=torch.float32, device=x.device)
+        scale_shift = torch.empty((2 * c,), dtype=torch.float32, device=x.device)
+        running_mean, running_var = stats if stats is not None else (None, None)
+        stream = _lib.stream_ptr(x.device)
+        if training:
+            ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_batch_norm_workspace_bytes(c))
+            ws_args = (_lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes)
+        else:
+            ws_args = (None, 0, None, 0)  # one launch, no sums: the accumulator pair keeps its state
+        _gn_check(lib.ln_batch_norm_forward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean), _lib.ptr(running_var), m, c,
+                                            float(eps), float(momentum), int(training), int(relu), _lib.ptr(y), _lib.ptr(mean_rstd),
+                                            _lib.ptr(scale_shift), *ws_args, _lib.ptr(rows_dev), stream), "ln_batch_norm_forward", x.device, stream)
+        ctx.rows_dev = rows_dev  # device-side row count of the lattice (static-rows mode), None otherwise
+        ctx.save_for_backward(x, weight, mean_rstd, scale_shift)
+        ctx.args = (bool(training), bool(relu), bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        lib = _lib.load()
+        x, weight, mean_rstd, scale_shift = ctx.saved_tensors
+        training, relu, has_bias = ctx.args
+        grad_y = grad_y.contiguous()
+        m, c = x.shape
+        grad_x = torch.empty_like(x)
+        grad_w = torch.empty((c,), dtype=torch.float32, device=x.device) if weight is not None else None
+        grad_b = torch.empty((c,), dtype=torch.float32, device=x.device) if has_bias else None
+        stream = _lib.stream_ptr(x.device)
+        ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_batch_norm_workspace_bytes(c))
+        _gn_check(lib.ln_batch_norm_backward(_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(weight), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), m, c,
+                                             int(training), int(relu), _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b), _lib.ptr(ws),
+                                             ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(ctx.rows_dev), stream),
+                  "ln_batch_norm_backward", x.device, stream)
+        return grad_x, grad_w, grad_b, None, None, None, None, None, None
+
+
+def batch_norm_rows(x: torch.Tensor, bn: torch.nn.BatchNorm1d, relu: bool = False, rows_dev=None) -> torch.Tensor:
+    """BatchNorm of an [M, C] matrix with the parameters and buffers of `bn` (statistics per channel over the rows); `bn.training` selects
+    batch or running statistics, and a module without running statistics always uses the batch's.  `rows_dev` as in group_norm_rows: with
+    it (static-rows mode) the HIP kernels are the only path; without it they run when FUSED_BATCH_NORM is set, torch otherwise.  A
+    training call moves bn.running_mean / running_var / num_batches_tracked on the device, without a host readback."""
+    native = x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.shape[1] <= 1024 and x.shape[0] > 0 and \
+        (bn.momentum is not None or bn.running_mean is None)
+    if native and (rows_dev is not None or FUSED_BATCH_NORM):
+        tracked = bn.running_mean is not None
+        training = bn.training or not tracked
+        y = BatchNormFunction.apply(x, bn.weight, bn.bias, (bn.running_mean, bn.running_var) if tracked else None,
+                                    bn.momentum if tracked else 0.0, bn.eps, training, relu, rows_dev)
+        if training and tracked and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)  # (behind the call: a refused call is no step)
+        return y
+    if rows_dev is not None:
+        raise ValueError("static-rows mode needs the HIP BatchNorm (float32 CUDA rows, channels % 4 == 0, <= 1024 channels, a momentum: "
+                         "momentum=None keeps a cumulative average the kernels do not)")
+    y = bn(x)
+    return torch.relu(y) if relu else y
+
+
 def group_norm_rows(x: torch.Tensor, gn: torch.nn.GroupNorm, relu: bool = False, rows_dev=None) -> torch.Tensor:
     """GroupNorm of an [M, C] matrix with the parameters of `gn` (statistics over rows x group channels).  `rows_dev`: device int
     holding the number of rows that count (Lattice.rows_device(): static-rows mode, where x is taller than its lattice)."""
@@ -281,7 +353,10 @@ class _PreActBlock(torch.nn.Module):
             if fuse:
                 pre_act = None
         elif self._norm_kind == "bn":
-            lv, ls = self.bn(lv, ls)
+            fuse = isinstance(pre_act, torch.nn.ReLU)  # (on the HIP path one pass; through torch the ReLU follows the norm)
+            lv, ls = self.bn(lv, ls, fuse_relu=fuse)
+            if fuse:
+                pre_act = None
         if pre_act is not None:
             lv = pre_act(lv)
         if self.with_dropout:
