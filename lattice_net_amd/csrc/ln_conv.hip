@@ -26,37 +26,8 @@
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-// fused backward of a same-lattice small-filter convolution (k_conv_backward_fused): vertices per workgroup, shapes it covers
-#define LN_BWD_MAX_SUBTILES 4
-#define LN_BWD_CUS 256
-static bool ln_bwd_fused_shape(int filter_extent, int val_dim, int nr_filters) {
-    return filter_extent == 9 && val_dim == 32 && nr_filters == 32;
-}
-// 64-vertex sub-tiles per workgroup (1..4).  A workgroup takes a whole CU, so the launch runs in rounds of 256 workgroups and a
-// round costs about T + 1: the T with the cheapest rounds(T) * (T + 1) wins, larger T on ties (fewer slabs) — one round at C3 (T = 3; a
-// 257th workgroup would run after all the others: twice the time), 3 rounds of T = 3 at 129 k vertices.
-static bool ln_conv_b3_enabled();
-#ifndef LN_BWD_B3_MAX_T
-#define LN_BWD_B3_MAX_T 3  // sub-tiles of the bf16x3 form: four fit the LDS since round 6 (unpadded staging) but need 148 registers of the 128 a
-                           // 1024-thread workgroup may have (20 spilled); the fp32 form at T = 4 was the slowest choice at 129 k vertices (65 us
-                           // against 55 for the bf16x3 form at T = 3: profiles/r6_kernel_stats_C4_one_in_flight.csv)
-#endif
-static int ln_bwd_subtiles(int m) {
-    const int max_t = ln_conv_b3_enabled() ? LN_BWD_B3_MAX_T : LN_BWD_MAX_SUBTILES;
-    const int s = (m + 63) / 64;
-    int best = 1, best_cost = 1 << 30;
-    for (int t = 1; t <= max_t; ++t) {
-        const int wgs = (s + t - 1) / t;
-        const int cost = ((wgs + LN_BWD_CUS - 1) / LN_BWD_CUS) * (t + 1);  // (+ 1: the bank staging and the slab epilogue of a workgroup — at 129 k
-                                                                           // vertices T = 2 / 3 run 4 / 3 rounds and measure 884 / 940 Mpoints/s)
-        if (cost <= best_cost) {
-            best = t;
-            best_cost = cost;
-        }
-    }
-    return best;
-}
-static int ln_bwd_workgroups(int m) { return (m + 64 * ln_bwd_subtiles(m) - 1) / (64 * ln_bwd_subtiles(m)); }
+#include "ln_conv_plan.h"
+#include <type_traits>
 
 // Phase stamps of the small-filter convolution (tools/kernel_timeline.py --conv; -DLN_STAMPS builds only)
 #ifdef LN_STAMPS
@@ -327,14 +298,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #ifndef LN_CONV_B3_DEEP
 #define LN_CONV_B3_DEEP(V) ((V) <= 96)
 #endif
-#ifndef LN_CONV_LDS_E
-#define LN_CONV_LDS_E 16  // filter extents up to 2 (d + 1) + 1 with d <= 6 keep their neighbour ids in LDS
-#endif
-// Waves per SIMD by gathered width (registers: 2 x V/4 row quarters + the staged bank slice + 4 NT accumulators; LDS: 36-48 KB bank
-// slice + 4 KB ids per workgroup): 3 up to 128 channels (<= 168 registers, 3 x 52 KB of LDS), 2 above (192 / 256 channels need
-// 174 / 220 registers: at 3 they spill, 1.77 ms instead of 0.63 at 256 x 256).  Measured at 46 k rows, 2 -> 3 waves: 64 x 64 37.7 -> 32.1 us,
-// 96 x 96 2 x 48.4 -> 2 x 40.8, 128 x 128 129 -> 122, 32 -> 64 20.7 -> 16.1.
-#define LN_CONV_B3_WAVES(V) ((V) <= 128 ? 3 : 2)
 // T sub-tiles of 64 rows per workgroup (256 T threads) share ONE staging of the slot's bank slice: T = 3 (one workgroup per CU, the
 // shape of k_conv_forward_b3) re-reads the bank from L2 and writes it to LDS a third as often as T = 1 (three workgroups per CU) —
 // at 46 k rows x 64 channels the bank traffic of T = 1 (727 workgroups x 9 slices of 24 KB = 157 MB) exceeds the gathered rows (107 MB).
@@ -1233,75 +1196,9 @@ __global__ void __launch_bounds__(256) ln_k_sum_partials(const float* __restrict
     reinterpret_cast<float4*>(out)[i] = acc;
 }
 
-// Split of the per-slot convolution over the filter slots: 1 (no split) while the vertex tiles alone fill the chip.
-#ifndef LN_CONV_SPLIT_TILES
-#define LN_CONV_SPLIT_TILES 512  // workgroups aimed at (two per CU)
-#endif
-template <int V>
-static int ln_conv_slots_per_split(int m, int E, int nr_filters) {
-    constexpr int NT_MAX = (V * 16 * 8 * 4 <= 32 * 1024) ? 8 : ((V * 16 * 4 * 4 <= 48 * 1024) ? 4 : 2);
-    const long long tiles = (long long)ln_div_up(m, 64) * ln_div_up(nr_filters, 16 * NT_MAX);
-    if (tiles * 2 > LN_CONV_SPLIT_TILES || E < 2) return E;
-    int nsplit = int((LN_CONV_SPLIT_TILES + tiles - 1) / tiles);
-    if (nsplit > E) nsplit = E;
-    return (E + nsplit - 1) / nsplit;  // slots per workgroup
-}
-#ifndef LN_CONV_WIDE_SPLIT_MIN_V
-#define LN_CONV_WIDE_SPLIT_MIN_V 128
-#endif
-#ifndef LN_CONV_B3_MIN_ROWS
-#define LN_CONV_B3_MIN_ROWS 4096
-#endif
-static size_t ln_conv_bank_bytes(int m, int E, int val_dim, int nr_filters);
-// Slot split of the WIDE form on mid-size lattices (0 / 1: not taken), from 128 gathered channels on where the 192-row workgroups of
-// the unsplit wide form would fill less than half the chip.
-// Measured at 11.4 k rows (level 2 of the SemanticKITTI network; tools/conv_time.py --coarse 1, us per call incl. bank split and
-// partial sum): 128 -> 128 46.9 -> 35.7, 256 -> 256 296 -> 109, 192 -> 192 191 -> 76, 256 -> 128 157 -> 55, 128 -> 64 32.2 -> 26.3.
-template <int V>
-static int ln_conv_wide_split(int m, int E, int nr_filters, bool have_bank) {
-    if (!have_bank || V % 32 != 0 || V < LN_CONV_WIDE_SPLIT_MIN_V || nr_filters % 32 != 0 || E < 3 || m < LN_CONV_B3_MIN_ROWS) return 0;
-    if ((long long)ln_div_up(m, 192) * ln_div_up(nr_filters, 128) >= LN_BWD_CUS / 2) return 0;  // the unsplit wide form already runs
-    // workgroups of the widest launch: the 128-column chunks go out together, a narrower rest as a launch of its own
-    const long long wgs = (long long)ln_div_up(m, 192) * (nr_filters >= 128 ? nr_filters / 128 : 1);
-    // rounds of one workgroup per CU x slots walked per workgroup; the smallest split among the cheapest (fewer partial slabs)
-    int best = 1;
-    long long best_cost = 1ll << 60;
-    for (int n = 2; n <= E; ++n) {
-        const long long cost = ((wgs * n + LN_BWD_CUS - 1) / LN_BWD_CUS) * ((E + n - 1) / n);
-        if (cost < best_cost) {
-            best = n;
-            best_cost = cost;
-        }
-    }
-    return best;
-}
-static int ln_conv_wide_split_rt(int m, int E, int val_dim, int nr_filters) {
-    const bool bank = ln_conv_bank_bytes(m, E, val_dim, nr_filters) > 0;
-    switch (val_dim) {
-        case 96: return ln_conv_wide_split<96>(m, E, nr_filters, bank);
-        case 128: return ln_conv_wide_split<128>(m, E, nr_filters, bank);
-        case 192: return ln_conv_wide_split<192>(m, E, nr_filters, bank);
-        case 256: return ln_conv_wide_split<256>(m, E, nr_filters, bank);
-        default: return 0;
-    }
-}
-static int ln_conv_slots_per_split_rt(int m, int E, int val_dim, int nr_filters) {
-    switch (val_dim) {
-        case 8: return ln_conv_slots_per_split<8>(m, E, nr_filters);
-        case 16: return ln_conv_slots_per_split<16>(m, E, nr_filters);
-        case 32: return ln_conv_slots_per_split<32>(m, E, nr_filters);
-        case 48: return ln_conv_slots_per_split<48>(m, E, nr_filters);
-        case 64: return ln_conv_slots_per_split<64>(m, E, nr_filters);
-        case 96: return ln_conv_slots_per_split<96>(m, E, nr_filters);
-        case 128: return ln_conv_slots_per_split<128>(m, E, nr_filters);
-        case 192: return ln_conv_slots_per_split<192>(m, E, nr_filters);
-        case 256: return ln_conv_slots_per_split<256>(m, E, nr_filters);
-        default: return E;
-    }
-}
-
-// bf16x3 path: channel counts that are multiples of 32, lattices large enough to be matrix-bound, LN_CONV_EXACT_F32=1 switches
-// it off (read once per process)
+// The dispatch rules (which form, how many column chunks, slot split, workspace layout) are ln_conv_plan.h's; below are the one
+// run-time switch, the size queries that read the plan's layout, and the executor that walks a plan.
+// LN_CONV_EXACT_F32=1 switches the bf16x3 path off (read once per process)
 static bool ln_conv_b3_enabled() {
     static int v = -1;
     if (v < 0) {
@@ -1310,179 +1207,22 @@ static bool ln_conv_b3_enabled() {
     }
     return v == 1;
 }
-static size_t ln_conv_bank_bytes(int m, int E, int val_dim, int nr_filters) {
-    if (val_dim % 32 != 0 || nr_filters % 16 != 0 || m < LN_CONV_B3_MIN_ROWS || E > LN_CONV_LDS_E || !ln_conv_b3_enabled()) return 0;
-    return (((size_t)E * val_dim * nr_filters * 3 * sizeof(unsigned short)) + 255) & ~size_t(255);
-}
-
-// shapes of the small-filter fast path, which needs no split bank
-static bool ln_conv_small_filter(int filter_extent, int val_dim, int nr_filters) {
-    return filter_extent == 9 && (size_t)filter_extent * val_dim * nr_filters * 4 <= 64 * 1024 && val_dim <= 32;
-}
+static bool ln_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" size_t ln_conv_bank_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters) {
-    if (m <= 0 || nr_filters % 16 != 0) return 0;
-    return ln_conv_small_filter(filter_extent, val_dim, nr_filters) ? 0 : ln_conv_bank_bytes(m, filter_extent, val_dim, nr_filters);
+    return ln_conv_bank_query(m, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
 }
 
 extern "C" size_t ln_conv_forward_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters) {
-    if (m <= 0 || nr_filters % 16 != 0) return 256;
-    int e_per = ln_conv_slots_per_split_rt(m, filter_extent, val_dim, nr_filters);
-    const int ws_ = ln_conv_wide_split_rt(m, filter_extent, val_dim, nr_filters);
-    if (ws_ > 1) e_per = (filter_extent + ws_ - 1) / ws_;
-    const int nsplit = (filter_extent + e_per - 1) / e_per;
-    // + the filter bank split into three bf16 parts (bf16x3 path of the per-slot kernel; not the small-filter fast path)
-    const size_t bank = ln_conv_small_filter(filter_extent, val_dim, nr_filters) ? 0 : ln_conv_bank_bytes(m, filter_extent, val_dim, nr_filters);
-    return bank + (nsplit > 1 ? (size_t)nsplit * m * nr_filters * sizeof(float) : 0) + 256;
+    return ln_conv_forward_query(m, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
 }
 
-// Sub-tiles per workgroup of the bf16x3 per-slot kernel: 3 (one 768-thread workgroup per CU) where the kernel runs at three waves per
-// SIMD and there are at least as many such workgroups as CUs.
-template <int V>
-static int ln_conv_b3_subtiles(int m, int chunks) {
-    if (LN_CONV_B3_WAVES(V) != 3) return 1;
-    return (long long)ln_div_up(m, 192) * chunks >= LN_BWD_CUS * 3 / 4 ? 3 : 1;
-}
-
-// LN_CONV_BANK_READY of the call in progress: the workspace already holds the split bank of this filter (written by an earlier call
-// with the same sizes and flags), so the k_conv_split_bank launches are skipped
-static thread_local bool g_ln_bank_ready = false;
 // ln_conv_row_partition: LnTable.row_regions of the space-ordered table the next convolutions of this thread run over (device memory,
 // read by the kernels; nullptr = none).  A placement hint only — ln_partition_tile is a bijection whatever the array holds.
 static thread_local const int* g_ln_row_partition = nullptr;
 extern "C" int ln_conv_row_partition(const int* row_starts) {
     g_ln_row_partition = row_starts;
     return LN_OK;
-}
-// slab sum waiting for a split launch to ride in (set by ln_conv_backward around its value-gradient convolution)
-static thread_local LnSlabSum g_ln_slab_job = {nullptr, 0, 0, nullptr};
-static LnSlabSum ln_take_slab_job() {
-    const LnSlabSum j = g_ln_slab_job;
-    g_ln_slab_job = LnSlabSum{nullptr, 0, 0, nullptr};
-    return j;
-}
-static int ln_slab_extra_blocks(const LnSlabSum& j, int planes) { return j.partial ? ln_div_up(j.total / 64, planes) : 0; }
-
-template <int V, bool FLIP, bool WT>
-static bool ln_conv_launch_v(int nr_filters, const int* nbr, const float* values, const float* filter, int m, int E, float* out,
-                             void* workspace, size_t workspace_bytes, hipStream_t st) {
-    const dim3 block(256);
-    constexpr int NT_MAX = (V * 16 * 8 * 4 <= 32 * 1024) ? 8 : ((V * 16 * 4 * 4 <= 48 * 1024) ? 4 : 2);
-    // workspace: [filter bank split into three bf16 parts (bf16x3 path)] [partial slabs of the slot split]
-    const bool ws_ok = workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0;
-    const size_t bank_bytes = ln_conv_bank_bytes(m, E, V, nr_filters);
-    const bool b3 = bank_bytes > 0 && ws_ok && workspace_bytes >= bank_bytes;
-    unsigned short* bank = b3 ? static_cast<unsigned short*>(workspace) : nullptr;
-    char* slab_ws = ws_ok ? static_cast<char*>(workspace) + (b3 ? bank_bytes : 0) : nullptr;
-    const size_t slab_bytes = ws_ok ? workspace_bytes - (b3 ? bank_bytes : 0) : 0;
-    int e_per = ln_conv_slots_per_split<V>(m, E, nr_filters);
-    int nsplit = (E + e_per - 1) / e_per;
-    // Mid-size lattices with wide rows (coarse levels of a U-net: 5-30 k rows x 128+ channels): too few 192-row workgroups for the wide
-    // form, and the 16-row kernels re-gather every row once per column chunk.  There the wide form runs with the slots split over
-    // gridDim.z (its workgroups then fill the chip) and the partial sums are added by the launch behind it.
-    const int wide_split = ln_conv_wide_split<V>(m, E, nr_filters, bank_bytes > 0 && ws_ok && workspace_bytes >= bank_bytes);
-    if (wide_split > 1) {
-        e_per = (E + wide_split - 1) / wide_split;
-        nsplit = (E + e_per - 1) / e_per;
-    }
-    if (nsplit > 1 && (!slab_ws || slab_bytes < (size_t)nsplit * m * nr_filters * sizeof(float))) {
-        e_per = E;  // no room for the partial slabs: one workgroup walks all slots
-        nsplit = 1;
-    }
-    const bool wide_mid = wide_split > 1 && nsplit > 1;
-    float* dst = nsplit > 1 ? reinterpret_cast<float*>(slab_ws) : out;
-    int f_off = 0;
-    size_t bank_off = 0;  // bf16 elements
-    // wide form (both operands by LDS-DMA, 32-row MFMA tiles, every output column in one pass over the gathered rows): column
-    // chunks of 128, then one narrower chunk
-    if constexpr (V % 32 == 0) {
-        // taken from 96 gathered channels on (below, the 16-row kernels' gathers are as fast: 64 x 64 27 vs 29 us at 46 k rows) and
-        // while the 192-row workgroups alone fill half the chip (no slot split in this form)
-        if (b3 && nr_filters % 32 == 0 && V >= 96 &&
-            (wide_mid || (nsplit == 1 && (long long)ln_div_up(m, 192) * ln_div_up(nr_filters, 128) >= LN_BWD_CUS / 2))) {
-#define LN_CONV_R32SK(NTC, RTT)                                                                                                     \
-    {                                                                                                                               \
-        const int cnt = (nr_filters - f_off) / (32 * NTC);                                                                          \
-        if (cnt > 0) {                                                                                                              \
-            if (!g_ln_bank_ready) {                                                                                                 \
-                const LnSlabSum job_ = ln_take_slab_job();                                                                          \
-                const int sx_ = ln_div_up(V * 32 * NTC, 256);                                                                       \
-                LN_LAUNCH("k_conv_split_bank", (k_conv_split_bank32<V, NTC, WT>), dim3(sx_ + ln_slab_extra_blocks(job_, E * cnt), E, cnt), block, 0, st, \
-                          filter, nr_filters, f_off, bank + bank_off, sx_, job_);                                                    \
-            }                                                                                                                       \
-            LN_LAUNCH("k_conv_mfma", (k_conv_rows32sk_b3<V, NTC, RTT, FLIP>), dim3(ln_div_up(m, 32 * RTT), cnt, nsplit),            \
-                      dim3(128 * RTT), 0, st, nbr, values, reinterpret_cast<const u32x4*>(bank + bank_off), m, E, dst, nr_filters, f_off, e_per); \
-            bank_off += (size_t)E * cnt * V * 32 * NTC * 3;                                                                         \
-            f_off += cnt * 32 * NTC;                                                                                                \
-        }                                                                                                                           \
-    }
-#define LN_CONV_R32(NTC, NTWW, CHH, RTT)                                                                                            \
-    {                                                                                                                               \
-        const int cnt = (nr_filters - f_off) / (32 * NTC);                                                                          \
-        if (cnt > 0) {                                                                                                              \
-            if (!g_ln_bank_ready) {                                                                                                 \
-                const LnSlabSum job_ = ln_take_slab_job();                                                                          \
-                const int sx_ = ln_div_up(V * 32 * NTC, 256);                                                                       \
-                LN_LAUNCH("k_conv_split_bank", (k_conv_split_bank32<V, NTC, WT>), dim3(sx_ + ln_slab_extra_blocks(job_, E * cnt), E, cnt), block, 0, st, \
-                          filter, nr_filters, f_off, bank + bank_off, sx_, job_);                                                    \
-            }                                                                                                                       \
-            LN_LAUNCH("k_conv_mfma", (k_conv_rows32_b3<V, NTWW, CHH, RTT, FLIP>), dim3(ln_div_up(m, 32 * RTT), cnt, nsplit),        \
-                      dim3(64 * RTT * CHH), 0, st, nbr, values, reinterpret_cast<const u32x4*>(bank + bank_off), m, E, dst, nr_filters, f_off, e_per); \
-            bank_off += (size_t)E * cnt * V * 32 * NTC * 3;                                                                         \
-            f_off += cnt * 32 * NTC;                                                                                                \
-        }                                                                                                                           \
-    }
-            // 96 columns (three tiles: no even split of the columns over a pair of waves) take the split-K pairs: 96 -> 96 62.5 -> 54.1 us,
-            // 128 -> 96 80.7 -> 69.1 us at 46.5 k rows; at 128 / 64 columns the column-split pairs are faster (80 vs 85, 50.6 vs 52 us:
-            // the pair's partial sums cost a pass through LDS at the end)
-            if ((nr_filters - f_off) % 128 == 96) {
-                LN_CONV_R32(4, 2, 2, 6) LN_CONV_R32SK(3, 6)
-            }
-            LN_CONV_R32(4, 2, 2, 6) LN_CONV_R32(3, 3, 1, 4) LN_CONV_R32(2, 1, 2, 6) LN_CONV_R32(1, 1, 1, 4)
-#undef LN_CONV_R32
-#undef LN_CONV_R32SK
-        }
-    }
-    // all chunks of the widest size go out as ONE launch (gridDim.y = their count), then at most one launch per narrower size
-#define LN_CONV_CHUNKS(NTC)                                                                                                         \
-    if constexpr (NT_MAX >= NTC) {                                                                                                  \
-        /* (256 gathered channels x 32 columns spills in the bf16x3 form: those lattices take 16 columns per workgroup) */          \
-        const int cnt = (b3 && V >= 256 && NTC > 1) ? 0 : (nr_filters - f_off) / (16 * NTC);                                        \
-        if (cnt > 0) {                                                                                                              \
-            bool done_b3 = false;                                                                                                   \
-            if constexpr (V % 32 == 0 && V * 16 * NTC * 6 <= 64 * 1024 && (V < 256 || NTC == 1)) { /* 256 x 32 columns spills */      \
-                if (b3) {                                                                                                           \
-                    if (!g_ln_bank_ready) {                                                                                         \
-                        const LnSlabSum job_ = ln_take_slab_job();                                                                  \
-                        const int sx_ = ln_div_up(V * 16 * NTC, 256);                                                               \
-                        LN_LAUNCH("k_conv_split_bank", (k_conv_split_bank<V, NTC, WT>), dim3(sx_ + ln_slab_extra_blocks(job_, E * cnt), E, cnt), block, 0, \
-                                  st, filter, nr_filters, f_off, bank + bank_off, sx_, job_);                                        \
-                    }                                                                                                               \
-                    if (ln_conv_b3_subtiles<V>(m, cnt * nsplit) == 3) {                                                             \
-                        if constexpr (LN_CONV_B3_WAVES(V) == 3)                                                                     \
-                            LN_LAUNCH("k_conv_mfma", (k_conv_mfma_b3<V, NTC, FLIP, 3>), dim3(ln_div_up(m, 192), cnt, nsplit), dim3(768), 0, st, nbr, \
-                                      values, reinterpret_cast<const u32x4*>(bank + bank_off), m, E, dst, nr_filters, f_off, e_per); \
-                    } else {                                                                                                        \
-                        LN_LAUNCH("k_conv_mfma", (k_conv_mfma_b3<V, NTC, FLIP, 1>), dim3(ln_div_up(m, 64), cnt, nsplit), block, 0, st, nbr, values, \
-                                  reinterpret_cast<const u32x4*>(bank + bank_off), m, E, dst, nr_filters, f_off, e_per);            \
-                    }                                                                                                               \
-                    bank_off += (size_t)E * cnt * V * 16 * NTC * 3;                                                                 \
-                    done_b3 = true;                                                                                                 \
-                }                                                                                                                   \
-            }                                                                                                                       \
-            if (!done_b3)                                                                                                           \
-                LN_LAUNCH("k_conv_mfma", (k_conv_mfma<V, NTC, FLIP, WT>), dim3(ln_div_up(m, 64), cnt, nsplit), block, 0, st, nbr, values, filter, \
-                          m, E, dst, nr_filters, f_off, e_per);                                                                     \
-            f_off += cnt * 16 * NTC;                                                                                                \
-        }                                                                                                                           \
-    }
-    LN_CONV_CHUNKS(8) LN_CONV_CHUNKS(4) LN_CONV_CHUNKS(2) LN_CONV_CHUNKS(1)
-#undef LN_CONV_CHUNKS
-    if (nsplit > 1) {
-        const long long total4 = (long long)m * nr_filters / 4;
-        LN_LAUNCH("k_conv_sum_partials", ln_k_sum_partials, dim3(ln_div_up(total4, 256)), block, 0, st, (const float*)dst, nsplit, total4, out);
-    }
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1643,76 +1383,220 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         }
 }
 
+// what the launches of one convolution call share
 template <bool FLIP, bool WT>
-static int ln_conv_dispatch(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent, int val_dim,
-                            int nr_filters, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
-    bool done = false;
-    if (filter_extent == 9 && (reinterpret_cast<uintptr_t>(filter) & 15) == 0) {  // d = 3 small-filter fast path
-        if constexpr (!FLIP && !WT) {  // V = F = 32 forward on the bf16 matrix cores
-            if (val_dim == 32 && nr_filters == 32 && m >= LN_CONV_B3_MIN_ROWS && ln_conv_b3_enabled() &&
-                (reinterpret_cast<uintptr_t>(values_neigh) & 15) == 0) {
-                const int t = min(ln_bwd_subtiles(m), 3);
-                const dim3 grid_t(ln_div_up(m, 64 * t)), block_t(256 * t);
-                if (t == 1) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<1>), grid_t, block_t, 0, st, nbr, values_neigh, filter, m, out, g_ln_row_partition);
-                else if (t == 2) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<2>), grid_t, block_t, 0, st, nbr, values_neigh, filter, m, out, g_ln_row_partition);
-                else LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<3>), grid_t, block_t, 0, st, nbr, values_neigh, filter, m, out, g_ln_row_partition);
-                return ln_check_launch("ln_conv_forward");
+struct LnConvCall {
+    const int* nbr;
+    const float *values, *filter;
+    int m, E, V, F;
+    float* out;
+    unsigned short* bank;  // workspace: [split bank][partial slabs]
+    float* dst;            // the slabs with a slot split, else out
+    int e_per;
+    LnSlabSum sum;         // rides in the launch that has carries_sum
+    hipStream_t st;
+};
+
+// small-filter fast path; with `partial`, the workgroups behind the first conv_blocks add the filter gradient's slabs (ln_conv_backward)
+template <bool FLIP, bool WT>
+static void ln_conv_launch_full(int V, int NT, dim3 grid, hipStream_t st, const int* nbr, const float* values, const float* filter, int m,
+                                float* out, int conv_blocks, const float* partial, int chunks, int total, float* grad_filter) {
+    auto go = [&](auto v, auto nt) {
+        constexpr int VV = decltype(v)::value, NN = decltype(nt)::value;
+        static_assert(ln_conv_full_shape(VV, 16 * NN), "not a small-filter shape");
+        LN_LAUNCH("k_conv_mfma", (k_conv_mfma_full<VV, NN, 9, FLIP, WT>), grid, dim3(256), 0, st, nbr, values, filter, m, out, conv_blocks, partial,
+                  chunks, total, grad_filter);
+    };
+    using std::integral_constant;
+    switch (V * 16 + NT) {
+        case 32 * 16 + 2: go(integral_constant<int, 32>{}, integral_constant<int, 2>{}); break;
+        case 32 * 16 + 1: go(integral_constant<int, 32>{}, integral_constant<int, 1>{}); break;
+        case 16 * 16 + 1: go(integral_constant<int, 16>{}, integral_constant<int, 1>{}); break;
+        case 16 * 16 + 2: go(integral_constant<int, 16>{}, integral_constant<int, 2>{}); break;
+        case 16 * 16 + 4: go(integral_constant<int, 16>{}, integral_constant<int, 4>{}); break;
+        case 8 * 16 + 1: go(integral_constant<int, 8>{}, integral_constant<int, 1>{}); break;
+        case 8 * 16 + 2: go(integral_constant<int, 8>{}, integral_constant<int, 2>{}); break;
+        case 8 * 16 + 4: go(integral_constant<int, 8>{}, integral_constant<int, 4>{}); break;
+        case 8 * 16 + 8: go(integral_constant<int, 8>{}, integral_constant<int, 8>{}); break;
+        default: break;  // (the plan names no other shape: ln_conv_full_shape)
+    }
+}
+
+// One launch of the per-slot forms: (V, NT) of the plan entry -> the instantiation, under the predicates the plan chose it by.
+template <bool FLIP, bool WT>
+struct LnConvEntry {  // what the cases below share
+    const LnConvLaunch& l;
+    const LnConvCall<FLIP, WT>& c;
+    dim3 grid() const { return dim3(l.grid[0], l.grid[1], l.grid[2]); }
+    unsigned short* bank() const { return c.bank + l.bank_off; }
+    const u32x4* frags() const { return reinterpret_cast<const u32x4*>(bank()); }
+    LnSlabSum ride() const { return l.carries_sum ? c.sum : LnSlabSum{nullptr, 0, 0, nullptr}; }
+};
+// wide form, column chunks of 32 NT
+template <int V, int NT, bool FLIP, bool WT>
+static void ln_conv_run_wide(const LnConvEntry<FLIP, WT>& e) {
+    const LnConvLaunch& l = e.l;
+    const LnConvCall<FLIP, WT>& c = e.c;
+    if constexpr (ln_conv_wide_built(V, NT)) {
+        if (l.kernel == LN_K_SPLIT_BANK32) {
+            LN_LAUNCH("k_conv_split_bank", (k_conv_split_bank32<V, NT, WT>), e.grid(), dim3(l.block), 0, c.st, c.filter, c.F, l.f_off, e.bank(), l.split_x,
+                      e.ride());
+            return;
+        }
+        if constexpr (NT == 3) {
+            if (l.kernel == LN_K_ROWS32SK) {
+                LN_LAUNCH("k_conv_mfma", (k_conv_rows32sk_b3<V, NT, LN_CONV_R32SK_RT, FLIP>), e.grid(), dim3(l.block), 0, c.st, c.nbr, c.values, e.frags(),
+                          c.m, c.E, c.dst, c.F, l.f_off, c.e_per);
+                return;
             }
         }
-        const dim3 grid(ln_div_up(m, 64)), block(256);
-#define LN_CONV_FULL(VV, NN)                                                                                                        \
-    if (!done && val_dim == VV && nr_filters == 16 * NN) {                                                                          \
-        LN_LAUNCH("k_conv_mfma", (k_conv_mfma_full<VV, NN, 9, FLIP, WT>), grid, block, 0, st, nbr, values_neigh, filter, m, out,  \
-                  (int)grid.x, (const float*)nullptr, 0, 0, (float*)nullptr);                                                       \
-        done = true;                                                                                                                \
+        LN_LAUNCH("k_conv_mfma", (k_conv_rows32_b3<V, ln_conv_r32_ntw(NT), ln_conv_r32_ch(NT), ln_conv_r32_rt(NT), FLIP>), e.grid(), dim3(l.block), 0, c.st,
+                  c.nbr, c.values, e.frags(), c.m, c.E, c.dst, c.F, l.f_off, c.e_per);
     }
-        LN_CONV_FULL(32, 2) LN_CONV_FULL(32, 1) LN_CONV_FULL(16, 1) LN_CONV_FULL(16, 2) LN_CONV_FULL(16, 4) LN_CONV_FULL(8, 1)
-        LN_CONV_FULL(8, 2) LN_CONV_FULL(8, 4) LN_CONV_FULL(8, 8)
-#undef LN_CONV_FULL
+}
+// 16-row form, column chunks of 16 NT
+template <int V, int NT, bool FLIP, bool WT>
+static void ln_conv_run_chunk(const LnConvEntry<FLIP, WT>& e) {
+    const LnConvLaunch& l = e.l;
+    const LnConvCall<FLIP, WT>& c = e.c;
+    if constexpr (ln_conv_chunk_fits(V, NT)) {
+        if constexpr (ln_conv_chunk_b3(V, NT)) {
+            if (l.kernel == LN_K_SPLIT_BANK) {
+                LN_LAUNCH("k_conv_split_bank", (k_conv_split_bank<V, NT, WT>), e.grid(), dim3(l.block), 0, c.st, c.filter, c.F, l.f_off, e.bank(), l.split_x,
+                          e.ride());
+                return;
+            }
+            if (l.kernel == LN_K_MFMA_B3) {
+                if (l.t == 3) {
+                    if constexpr (ln_conv_b3_three_subtiles(V))
+                        LN_LAUNCH("k_conv_mfma", (k_conv_mfma_b3<V, NT, FLIP, 3>), e.grid(), dim3(l.block), 0, c.st, c.nbr, c.values, e.frags(), c.m, c.E,
+                                  c.dst, c.F, l.f_off, c.e_per);
+                } else {
+                    LN_LAUNCH("k_conv_mfma", (k_conv_mfma_b3<V, NT, FLIP, 1>), e.grid(), dim3(l.block), 0, c.st, c.nbr, c.values, e.frags(), c.m, c.E, c.dst,
+                              c.F, l.f_off, c.e_per);
+                }
+                return;
+            }
+        }
+        LN_LAUNCH("k_conv_mfma", (k_conv_mfma<V, NT, FLIP, WT>), e.grid(), dim3(l.block), 0, c.st, c.nbr, c.values, c.filter, c.m, c.E, c.dst, c.F, l.f_off,
+                  c.e_per);
     }
-    if (!done && nr_filters % 16 == 0 && ((reinterpret_cast<uintptr_t>(values_neigh) | reinterpret_cast<uintptr_t>(filter)) & 15) == 0) {
-        const int nf = nr_filters;
-        switch (val_dim) {
-            case 8: done = ln_conv_launch_v<8, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 16: done = ln_conv_launch_v<16, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 32: done = ln_conv_launch_v<32, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 48: done = ln_conv_launch_v<48, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 64: done = ln_conv_launch_v<64, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 96: done = ln_conv_launch_v<96, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 128: done = ln_conv_launch_v<128, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 192: done = ln_conv_launch_v<192, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
-            case 256: done = ln_conv_launch_v<256, FLIP, WT>(nf, nbr, values_neigh, filter, m, filter_extent, out, ws, ws_bytes, st); break;
+}
+
+template <int V, bool FLIP, bool WT>
+static void ln_conv_run_v(const LnConvLaunch& l, const LnConvCall<FLIP, WT>& c) {
+    const LnConvEntry<FLIP, WT> e = {l, c};
+    if (l.kernel == LN_K_SPLIT_BANK32 || l.kernel == LN_K_ROWS32 || l.kernel == LN_K_ROWS32SK) {
+        switch (l.nt) {
+            case 4: ln_conv_run_wide<V, 4>(e); break;
+            case 3: ln_conv_run_wide<V, 3>(e); break;
+            case 2: ln_conv_run_wide<V, 2>(e); break;
+            case 1: ln_conv_run_wide<V, 1>(e); break;
+            default: break;
+        }
+    } else {
+        switch (l.nt) {
+            case 8: ln_conv_run_chunk<V, 8>(e); break;
+            case 4: ln_conv_run_chunk<V, 4>(e); break;
+            case 2: ln_conv_run_chunk<V, 2>(e); break;
+            case 1: ln_conv_run_chunk<V, 1>(e); break;
             default: break;
         }
     }
-    if (!done) {
-        const long long work = (long long)m * nr_filters;
-        LN_LAUNCH("k_conv_generic", k_conv_generic, dim3(ln_div_up(work, 256)), dim3(256), 0, st, nbr, values_neigh, filter, work,
-                  filter_extent, val_dim, nr_filters, FLIP ? 1 : 0, WT ? 1 : 0, out);
+}
+
+// Walks a plan: every entry to the instantiation it names.
+template <bool FLIP, bool WT>
+static void ln_conv_run(const LnConvPlan& p, const LnConvCall<FLIP, WT>& c) {
+    for (int k = 0; k < p.n; ++k) {
+        const LnConvLaunch& l = p.launch[k];
+        const dim3 grid(l.grid[0], l.grid[1], l.grid[2]), block(l.block);
+        switch (l.kernel) {
+            case LN_K_FORWARD_B3:
+                if constexpr (!FLIP && !WT) {
+                    if (l.t == 1) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<1>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, g_ln_row_partition);
+                    else if (l.t == 2) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<2>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, g_ln_row_partition);
+                    else LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<3>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, g_ln_row_partition);
+                }
+                break;
+            case LN_K_FULL:
+                ln_conv_launch_full<FLIP, WT>(c.V, l.nt, grid, c.st, c.nbr, c.values, c.filter, c.m, c.out, l.grid[0], nullptr, 0, 0, nullptr);
+                break;
+            case LN_K_SUM_PARTIALS:
+                LN_LAUNCH("k_conv_sum_partials", ln_k_sum_partials, grid, block, 0, c.st, (const float*)c.dst, p.nsplit, (long long)c.m * c.F / 4, c.out);
+                break;
+            case LN_K_GENERIC:
+                LN_LAUNCH("k_conv_generic", k_conv_generic, grid, block, 0, c.st, c.nbr, c.values, c.filter, (long long)c.m * c.F, c.E, c.V, c.F,
+                          FLIP ? 1 : 0, WT ? 1 : 0, c.out);
+                break;
+            default:
+                switch (c.V) {
+                    case 8: ln_conv_run_v<8>(l, c); break;
+                    case 16: ln_conv_run_v<16>(l, c); break;
+                    case 32: ln_conv_run_v<32>(l, c); break;
+                    case 48: ln_conv_run_v<48>(l, c); break;
+                    case 64: ln_conv_run_v<64>(l, c); break;
+                    case 96: ln_conv_run_v<96>(l, c); break;
+                    case 128: ln_conv_run_v<128>(l, c); break;
+                    case 192: ln_conv_run_v<192>(l, c); break;
+                    case 256: ln_conv_run_v<256>(l, c); break;
+                    default: break;
+                }
+        }
     }
-    return ln_check_launch("ln_conv_forward");
+}
+
+template <bool FLIP, bool WT>
+static void ln_conv_plan_and_run(LnConvPlanIn in, const int* nbr, const float* values, const float* filter, float* out, void* ws,
+                                 const LnSlabSum& sum, bool* sum_left, hipStream_t st) {
+    in.flip = FLIP;
+    in.wt = WT;
+    const LnConvPlan p = ln_conv_plan(in);
+    char* slabs = static_cast<char*>(ws) + p.bank_bytes;
+    ln_conv_run<FLIP, WT>(p, LnConvCall<FLIP, WT>{nbr, values, filter, in.m, in.E, in.V, in.F, out, static_cast<unsigned short*>(ws),
+                                                 p.nsplit > 1 ? reinterpret_cast<float*>(slabs) : out, p.e_per, sum, st});
+    *sum_left = p.sum_left;
+}
+
+// The one entry to the forward convolution.  `sum`: the slab sum of a filter gradient launched just before (partial == nullptr: none).
+// A bank split of this convolution carries it where there is one; otherwise it goes out here as a launch of its own, behind the
+// convolution's, whatever became of the call.
+static int ln_conv_forward_riding(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent, int val_dim,
+                                  int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, void* stream,
+                                  const LnSlabSum& sum) {
+    hipStream_t st = (hipStream_t)stream;
+    bool sum_left = sum.partial != nullptr;
+    const int rc = [&]() -> int {
+        LN_REQUIRE(m >= 0 && filter_extent >= 1 && val_dim >= 1 && nr_filters >= 1, LN_ERR_ARG, "ln_conv_forward: bad sizes");
+        LN_REQUIRE(m == 0 || (nbr && values_neigh && filter && out), LN_ERR_ARG, "ln_conv_forward: null buffer");
+        LN_REQUIRE((flags & ~7) == 0, LN_ERR_ARG, "ln_conv_forward: unknown flags %d", flags);
+        if (m == 0) return LN_OK;
+        LnConvPlanIn in = {};
+        in.m = m, in.E = filter_extent, in.V = val_dim, in.F = nr_filters;
+        in.b3_enabled = ln_conv_b3_enabled();
+        in.values_aligned = ln_aligned16(values_neigh);
+        in.filter_aligned = ln_aligned16(filter);
+        in.ws_aligned = workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0;
+        in.ws_bytes = workspace_bytes;
+        // the workspace already holds the split bank of this filter (written by an earlier call with the same sizes and flags)
+        in.bank_ready = (flags & LN_CONV_BANK_READY) != 0 && workspace != nullptr;
+        in.riding_total = sum.partial ? sum.total : 0;
+        switch (flags & 3) {
+            case 0: ln_conv_plan_and_run<false, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
+            case LN_CONV_FLIP_NEIGHBOURS: ln_conv_plan_and_run<true, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
+            case LN_CONV_TRANSPOSED_FILTER: ln_conv_plan_and_run<false, true>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
+            default: ln_conv_plan_and_run<true, true>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
+        }
+        return ln_check_launch("ln_conv_forward");
+    }();
+    if (sum_left) (void)ln_reduce_slabs_async(sum.partial, sum.nslabs, sum.total, sum.out, st);
+    return rc;
 }
 
 extern "C" int ln_conv_forward_ws(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent, int val_dim,
                                   int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    LN_REQUIRE(m >= 0 && filter_extent >= 1 && val_dim >= 1 && nr_filters >= 1, LN_ERR_ARG, "ln_conv_forward: bad sizes");
-    LN_REQUIRE(m == 0 || (nbr && values_neigh && filter && out), LN_ERR_ARG, "ln_conv_forward: null buffer");
-    LN_REQUIRE((flags & ~7) == 0, LN_ERR_ARG, "ln_conv_forward: unknown flags %d", flags);
-    if (m == 0) return LN_OK;
-    hipStream_t st = (hipStream_t)stream;
-    void* ws = workspace;
-    const size_t wb = workspace_bytes;
-    struct BankReady {  // (scoped: the flag never outlives the call)
-        explicit BankReady(bool on) { g_ln_bank_ready = on; }
-        ~BankReady() { g_ln_bank_ready = false; }
-    } bank_ready((flags & LN_CONV_BANK_READY) != 0 && workspace != nullptr);
-    flags &= 3;
-    switch (flags) {
-        case 0: return ln_conv_dispatch<false, false>(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, out, ws, wb, st);
-        case LN_CONV_FLIP_NEIGHBOURS: return ln_conv_dispatch<true, false>(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, out, ws, wb, st);
-        case LN_CONV_TRANSPOSED_FILTER: return ln_conv_dispatch<false, true>(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, out, ws, wb, st);
-        default: return ln_conv_dispatch<true, true>(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, out, ws, wb, st);
-    }
+    return ln_conv_forward_riding(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, flags, out, workspace, workspace_bytes, stream,
+                                  LnSlabSum{nullptr, 0, 0, nullptr});
 }
 
 extern "C" int ln_conv_forward(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent,
@@ -1726,9 +1610,6 @@ extern "C" int ln_conv_forward(const int* nbr, const float* values_neigh, const 
 //          the 4 waves are combined through LDS and the workgroup writes one partial [V,F] slab.
 // Stage 2: deterministic sum of the slabs.
 // ------------------------------------------------------------------------------------------
-#ifndef LN_GF_ROWS
-#define LN_GF_ROWS 320   // lattice vertices per workgroup (one slab each)
-#endif
 #define LN_GF_SUB 64     // vertices staged in LDS at a time (25 KiB of LDS -> 6 workgroups per CU)
 
 // Stage 1.  grid = (row chunks, E).  A workgroup walks its chunk in sub-tiles of LN_GF_SUB vertices: the
@@ -1910,14 +1791,8 @@ int ln_reduce_slabs_async(const float* partial, int nslabs, int total, float* ou
 // M = 46.5 k, V = F = 128.)
 // ------------------------------------------------------------------------------------------
 typedef short gf_short4 __attribute__((ext_vector_type(4)));
-#ifndef LN_GFB_SUB
-#define LN_GFB_SUB 64
-#endif
 #ifndef LN_GFB_WAVES
 #define LN_GFB_WAVES 2
-#endif
-#ifndef LN_GFB_EG
-#define LN_GFB_EG 3   // slots per workgroup: E = 9 as three groups (gridDim.y); the gradient rows are split three times instead of nine
 #endif
 // WV x WF waves, each owning (VT / WV) x (FT / WF) tiles of 16 x 16 per slot.  2 x 2 waves on a 64 x 64 block (two workgroups per CU)
 // is the round-4 shape; at 128 x 128 the block is the whole [V, F] face on 4 x 4 waves (one 1024-thread workgroup per CU): every
@@ -2092,118 +1967,54 @@ __global__ void __launch_bounds__(64 * WV * WF, (WV * WF) > 8 ? 1 : LN_GFB_WAVES
     }
 }
 
-// rows per workgroup of the bf16x3 filter gradient: as few as fill the chip (>= 512 workgroups over chunks x slot groups x sub-blocks) while the
-// slabs the chunks write (and k_reduce_slabs4 reads back) stay under LN_GFB_SLAB_BYTES; a multiple of the 64-row sub-tile
-#define LN_GFB_SLAB_BYTES (24ll << 20)
-static bool ln_gfb_block(int val_dim, int nr_filters, int* vs, int* fs) {
-    // (whole faces of 128 x 64, 64 x 128 and 96 x 96 on 4 x 2 / 2 x 4 / 3 x 2 waves measured the same as their 64 x 64 / 32 x 96
-    // sub-blocks — 65 vs 66 us, 71 vs 71 us at 46 k rows —, and 96 x 96 on 2 x 2 waves spills: only 128 x 128 takes the whole face)
-    static const int cand[7][2] = {{128, 128}, {64, 64}, {32, 96}, {96, 32}, {64, 32}, {32, 64}, {32, 32}};
-    for (auto& c : cand)
-        if (val_dim % c[0] == 0 && nr_filters % c[1] == 0) {
-            *vs = c[0];
-            *fs = c[1];
-            return true;
-        }
-    return false;
-}
-static int ln_gfb_rows(int m, int filter_extent, int val_dim, int nr_filters) {
-    int vs = 0, fs = 0;
-    if (filter_extent != 9 || !ln_gfb_block(val_dim, nr_filters, &vs, &fs)) return 0;  // (the kernel is instantiated for E = 9: d = 3)
-    const long long z = (long long)(val_dim / vs) * (nr_filters / fs) * (filter_extent / LN_GFB_EG);  // workgroups per row chunk
-    const long long slab = (long long)filter_extent * val_dim * nr_filters * 4;
-    const bool one_per_cu = vs * fs > 64 * 96;                              // blocks on more than eight waves take a whole CU
-    long long chunks = ((one_per_cu ? 256 : 512) + z - 1) / z;              // (else two workgroups per CU) ...
-    const long long budget = one_per_cu ? 2 * LN_GFB_SLAB_BYTES : LN_GFB_SLAB_BYTES;
-    const long long cap = budget / slab > 0 ? budget / slab : 1;
-    if (chunks > cap) chunks = cap;                                         // ... unless the slabs would cost more than the products
-    long long rows = ((m + chunks - 1) / chunks + LN_GFB_SUB - 1) / LN_GFB_SUB * LN_GFB_SUB;
-    if (rows < LN_GFB_SUB) rows = LN_GFB_SUB;
-    return int(rows);
-}
-static bool ln_gfb_enabled(int m, int filter_extent, int val_dim, int nr_filters) {
-    int vs, fs;
-    return filter_extent == 9 && m >= LN_CONV_B3_MIN_ROWS && ln_conv_b3_enabled() && ln_gfb_block(val_dim, nr_filters, &vs, &fs);
-}
-
-// Any multiple of 16 in both dimensions: the [V, F] block of a slot is covered by sub-blocks of {64, 32, 16} x {64, 32, 16}.
-static bool ln_gf_mfma_supported(int val_dim, int nr_filters) { return val_dim % 16 == 0 && nr_filters % 16 == 0; }
-
 extern "C" size_t ln_conv_grad_filter_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters) {
-    if (!ln_gf_mfma_supported(val_dim, nr_filters) || m <= 0) return 256;
-    // one [E, V, F] slab per row chunk; the fused backward of a same-lattice convolution (ln_conv_backward) has its own chunking
-    int chunks = ln_bwd_fused_shape(filter_extent, val_dim, nr_filters) ? max(ln_div_up(m, LN_GF_ROWS), ln_bwd_workgroups(m))
-                                                                        : ln_div_up(m, LN_GF_ROWS);
-    const int rows_b3 = ln_gfb_rows(m, filter_extent, val_dim, nr_filters);  // (whichever of the two forms runs)
-    if (rows_b3 > 0) chunks = max(chunks, ln_div_up(m, rows_b3));
-    return (size_t)chunks * filter_extent * val_dim * nr_filters * sizeof(float) + 256;
+    return ln_gf_query(m, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
 }
 
-// stage 1 of the MFMA filter gradient: per-row-chunk partial blocks -> slabs [chunk][E*V*F]; returns the chunk count
-static int ln_gf_launch_partials(const int* nbr, const float* values_neigh, const float* grad_out, int m, int filter_extent, int val_dim,
-                                 int nr_filters, float* partial, hipStream_t st) {
-    const dim3 block(256);
-    if (ln_gfb_enabled(m, filter_extent, val_dim, nr_filters)) {  // bf16 matrix cores, gradient rows split once for all nine slots
-        int vs = 0, fs = 0;
-        ln_gfb_block(val_dim, nr_filters, &vs, &fs);
-        const int rows = ln_gfb_rows(m, filter_extent, val_dim, nr_filters);
-        const int chunks_b3 = ln_div_up(m, rows);
-        const dim3 grid(chunks_b3, filter_extent / LN_GFB_EG, (val_dim / vs) * (nr_filters / fs));
-        const size_t lds = (size_t)3 * LN_GFB_SUB * ((vs + 16) + (fs + 16)) * sizeof(unsigned short);
-#define LN_GFB_CASE(A, B, WVV, WFF)                                                                                                    \
-    if (vs == 16 * A && fs == 16 * B) {                                                                                                \
-        static bool attr_set = false;                                                                                                  \
-        if (!attr_set && lds > 64 * 1024) {                                                                                            \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grad_filter_b3<A, B, 9, WVV, WFF>),                             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                           \
-            attr_set = true;                                                                                                           \
-        }                                                                                                                              \
-        LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_b3<A, B, 9, WVV, WFF>), grid, dim3(64 * WVV * WFF), lds, st, nbr, values_neigh, grad_out, \
-                  m, rows, partial, val_dim, nr_filters);                                                                              \
+template <int A, int B>
+static void ln_gfb_launch(const LnGfPlan& p, const int* nbr, const float* values_neigh, const float* grad_out, int m, int val_dim, int nr_filters,
+                          float* partial, hipStream_t st) {
+    constexpr int WV = ln_gfb_wv(16 * A, 16 * B), WF = ln_gfb_wf(16 * A, 16 * B);
+    static bool attr_set = false;
+    if (!attr_set && p.lds > 64 * 1024) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grad_filter_b3<A, B, 9, WV, WF>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)p.lds);
+        attr_set = true;
     }
-#ifndef LN_GFB_W128F
-#define LN_GFB_W128F 2  // waves across the filters of a 128 x 128 block: 4 x 2 waves (512 threads, 248 registers; measured 101 us at 46 k rows
-                        // against 118 for 4 x 4 waves, whose 128-register budget spills 13 dwords, and 132 for 64 x 64 sub-blocks)
-#endif
-        LN_GFB_CASE(8, 8, 4, LN_GFB_W128F) 
-        LN_GFB_CASE(4, 4, 2, 2) LN_GFB_CASE(2, 6, 2, 2) LN_GFB_CASE(6, 2, 2, 2) LN_GFB_CASE(4, 2, 2, 2) LN_GFB_CASE(2, 4, 2, 2) LN_GFB_CASE(2, 2, 2, 2)
-#undef LN_GFB_CASE
-        return chunks_b3;
-    }
-    const int chunks = ln_div_up(m, LN_GF_ROWS);
-    // uniform tiling (both dimensions multiples of the widest tile that divides them): ONE launch, gridDim.z = sub-blocks
-    for (int t = 4; t >= 1; t >>= 1) {
-        if (val_dim % (16 * t) == 0 && nr_filters % (16 * t) == 0) {
-            const dim3 grid(chunks, filter_extent, (val_dim / (16 * t)) * (nr_filters / (16 * t)));
-            if (t == 4)
-                LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_mfma<4, 4>), grid, block, 0, st, nbr, values_neigh, grad_out, m, filter_extent, partial,
-                          val_dim, 0, nr_filters, 0);
-            else if (t == 2)
-                LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_mfma<2, 2>), grid, block, 0, st, nbr, values_neigh, grad_out, m, filter_extent, partial,
-                          val_dim, 0, nr_filters, 0);
-            else
-                LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_mfma<1, 1>), grid, block, 0, st, nbr, values_neigh, grad_out, m, filter_extent, partial,
-                          val_dim, 0, nr_filters, 0);
-            return chunks;
+    LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_b3<A, B, 9, WV, WF>), dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(p.block), p.lds, st, nbr,
+              values_neigh, grad_out, m, p.rows, partial, val_dim, nr_filters);
+}
+
+// stage 1 of the MFMA filter gradient: per-row-chunk partial blocks -> slabs [chunk][E*V*F] (p.chunks of them)
+static void ln_gf_launch_partials(const LnGfPlan& p, const int* nbr, const float* values_neigh, const float* grad_out, int m, int filter_extent,
+                                  int val_dim, int nr_filters, float* partial, hipStream_t st) {
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
+    if (p.form == LN_GF_B3) {
+        switch (p.vs * 1000 + p.fs) {
+            case 128128: ln_gfb_launch<8, 8>(p, nbr, values_neigh, grad_out, m, val_dim, nr_filters, partial, st); break;
+            case 64064: ln_gfb_launch<4, 4>(p, nbr, values_neigh, grad_out, m, val_dim, nr_filters, partial, st); break;
+            case 32096: ln_gfb_launch<2, 6>(p, nbr, values_neigh, grad_out, m, val_dim, nr_filters, partial, st); break;
+            case 96032: ln_gfb_launch<6, 2>(p, nbr, values_neigh, grad_out, m, val_dim, nr_filters, partial, st); break;
+            case 64032: ln_gfb_launch<4, 2>(p, nbr, values_neigh, grad_out, m, val_dim, nr_filters, partial, st); break;
+            case 32064: ln_gfb_launch<2, 4>(p, nbr, values_neigh, grad_out, m, val_dim, nr_filters, partial, st); break;
+            default: ln_gfb_launch<2, 2>(p, nbr, values_neigh, grad_out, m, val_dim, nr_filters, partial, st); break;
         }
+    } else if (p.tile == 4) {
+        LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_mfma<4, 4>), grid, block, 0, st, nbr, values_neigh, grad_out, m, filter_extent, partial,
+                  val_dim, 0, nr_filters, 0);
+    } else if (p.tile == 2) {
+        LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_mfma<2, 2>), grid, block, 0, st, nbr, values_neigh, grad_out, m, filter_extent, partial,
+                  val_dim, 0, nr_filters, 0);
+    } else {
+        LN_LAUNCH("k_grad_filter_mfma", (k_grad_filter_mfma<1, 1>), grid, block, 0, st, nbr, values_neigh, grad_out, m, filter_extent, partial,
+                  val_dim, 0, nr_filters, 0);
     }
-    return chunks;  // unreachable: both dimensions are multiples of 16 (ln_gf_mfma_supported)
 }
 
+// `deferred` (ln_conv_backward, ln_linear_backward): where the slab sum can ride in a bank split it is not launched but handed back,
+// for the convolution behind it to carry (ln_conv_forward_riding)
 static int ln_conv_grad_filter_impl(const int* nbr, const float* values_neigh, const float* grad_out, int m, int filter_extent, int val_dim,
-                                    int nr_filters, float* grad_filter, void* workspace, size_t workspace_bytes, void* stream, bool defer_sum);
-
-extern "C" int ln_conv_grad_filter(const int* nbr, const float* values_neigh, const float* grad_out, int m, int filter_extent,
-                                   int val_dim, int nr_filters, float* grad_filter, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
-    return ln_conv_grad_filter_impl(nbr, values_neigh, grad_out, m, filter_extent, val_dim, nr_filters, grad_filter, workspace, workspace_bytes,
-                                    stream, false);
-}
-
-// defer_sum: leave the slab sum as g_ln_slab_job for the next bank split of this thread to carry (ln_conv_backward; the caller
-// launches it itself if nothing took it)
-static int ln_conv_grad_filter_impl(const int* nbr, const float* values_neigh, const float* grad_out, int m, int filter_extent, int val_dim,
-                                    int nr_filters, float* grad_filter, void* workspace, size_t workspace_bytes, void* stream, bool defer_sum) {
+                                    int nr_filters, float* grad_filter, void* workspace, size_t workspace_bytes, void* stream, LnSlabSum* deferred) {
     LN_REQUIRE(m >= 0 && filter_extent >= 1 && val_dim >= 1 && nr_filters >= 1, LN_ERR_ARG, "ln_conv_grad_filter: bad sizes");
     LN_REQUIRE(grad_filter && (m == 0 || (nbr && values_neigh && grad_out)), LN_ERR_ARG, "ln_conv_grad_filter: null buffer");
     hipStream_t st = (hipStream_t)stream;
@@ -2212,23 +2023,30 @@ static int ln_conv_grad_filter_impl(const int* nbr, const float* values_neigh, c
         (void)ln_zero_async(grad_filter, (size_t)total * sizeof(float), st);
         return ln_check_launch("ln_conv_grad_filter");
     }
-    if (ln_gf_mfma_supported(val_dim, nr_filters)) {
-        LN_REQUIRE(workspace && workspace_bytes >= ln_conv_grad_filter_workspace_bytes(m, filter_extent, val_dim, nr_filters),
-                   LN_ERR_WORKSPACE, "ln_conv_grad_filter: workspace too small");
-        LN_REQUIRE((reinterpret_cast<uintptr_t>(values_neigh) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_out) & 15) == 0, LN_ERR_ARG,
-                   "ln_conv_grad_filter: values / grad_out must be 16-byte aligned");
-        float* partial = static_cast<float*>(workspace);
-        const int chunks = ln_gf_launch_partials(nbr, values_neigh, grad_out, m, filter_extent, val_dim, nr_filters, partial, st);
-        // slabs are laid out [chunk][e][V*F]; summing over chunks with stride E*V*F
-        if (defer_sum && total % 64 == 0 && ((reinterpret_cast<uintptr_t>(grad_filter) | reinterpret_cast<uintptr_t>(partial)) & 15) == 0)
-            g_ln_slab_job = LnSlabSum{partial, chunks, total, grad_filter};
-        else
-            (void)ln_reduce_slabs_async(partial, chunks, total, grad_filter, st);
-    } else {
-        LN_LAUNCH("k_grad_filter_generic", k_grad_filter_generic, dim3(ln_div_up(total, 256)), dim3(256), 0, st, nbr, values_neigh, grad_out, m,
-                           filter_extent, val_dim, nr_filters, grad_filter);
+    const LnGfPlan p = ln_gf_plan(m, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
+    if (p.form == LN_GF_GENERIC) {
+        LN_LAUNCH("k_grad_filter_generic", k_grad_filter_generic, dim3(p.grid[0]), dim3(p.block), 0, st, nbr, values_neigh, grad_out, m,
+                  filter_extent, val_dim, nr_filters, grad_filter);
+        return ln_check_launch("ln_conv_grad_filter");
     }
+    LN_REQUIRE(workspace && workspace_bytes >= ln_conv_grad_filter_workspace_bytes(m, filter_extent, val_dim, nr_filters), LN_ERR_WORKSPACE,
+               "ln_conv_grad_filter: workspace too small");
+    LN_REQUIRE(ln_aligned16(values_neigh) && ln_aligned16(grad_out), LN_ERR_ARG, "ln_conv_grad_filter: values / grad_out must be 16-byte aligned");
+    float* partial = static_cast<float*>(workspace);
+    ln_gf_launch_partials(p, nbr, values_neigh, grad_out, m, filter_extent, val_dim, nr_filters, partial, st);
+    // slabs are laid out [chunk][e][V*F]; summing over chunks with stride E*V*F
+    if (deferred && total % 64 == 0 && ln_aligned16(grad_filter) && ln_aligned16(partial))
+        *deferred = LnSlabSum{partial, p.chunks, total, grad_filter};
+    else
+        (void)ln_reduce_slabs_async(partial, p.chunks, total, grad_filter, st);
     return ln_check_launch("ln_conv_grad_filter");
+}
+
+extern "C" int ln_conv_grad_filter(const int* nbr, const float* values_neigh, const float* grad_out, int m, int filter_extent,
+                                   int val_dim, int nr_filters, float* grad_filter, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    return ln_conv_grad_filter_impl(nbr, values_neigh, grad_out, m, filter_extent, val_dim, nr_filters, grad_filter, workspace, workspace_bytes,
+                                    stream, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2670,67 +2488,58 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
 // Both gradients of out = conv(values_neigh; nbr_q, filter[E*V, F]):
 //   grad_filter[E*V, F] = im2row(values_neigh; nbr_q)^T @ grad_out            (ln_conv_grad_filter)
 //   grad_values[mn, V]  = conv(grad_out; nbr_n, filter, FLIP | TRANSPOSED)     (ln_conv_forward)
-// For the small-filter shapes (whole bank in LDS) the slab sum of the filter gradient rides in the convolution launch.
+// The form is ln_conv_backward_plan's.  For the small-filter shapes (whole bank in LDS) the slab sum of the filter gradient rides in
+// the convolution launch.
+template <int T>
+static void ln_bwd_launch_fused(const LnBwdPlan& p, const int* nbr, const float* values, const float* grad_out, const float* filter, int m,
+                                float* grad_values, float* partial, hipStream_t st) {
+    if constexpr (T <= LN_BWD_B3_MAX_T) {  // bf16 matrix cores, exactly split operands
+        if (p.form == LN_BWD_FUSED_B3) {
+            LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused_b3<T>), dim3(p.grid), dim3(p.block), 0, st, nbr, values, grad_out, filter, m,
+                      grad_values, partial, g_ln_row_partition);
+            return;
+        }
+    }
+    LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused<32, 32, 9, T>), dim3(p.grid), dim3(p.block), 0, st, nbr, values, grad_out, filter, m,
+              grad_values, partial);
+}
+
 extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter, int mq,
                                 int mn, int filter_extent, int val_dim, int nr_filters, float* grad_values, float* grad_filter,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    bool fused = false;
-    const int V = nr_filters, F = val_dim;  // roles in the value-gradient convolution: V channels in, F channels out
-    if (filter_extent == 9 && mq > 0 && mn > 0 && ln_gf_mfma_supported(val_dim, nr_filters) && nbr_q && nbr_n && values_neigh && grad_out &&
-        filter && grad_values && grad_filter && workspace &&
-        workspace_bytes >= ln_conv_grad_filter_workspace_bytes(mq, filter_extent, val_dim, nr_filters) &&
-        ((reinterpret_cast<uintptr_t>(values_neigh) | reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(filter)) & 15) == 0) {
-        float* partial = static_cast<float*>(workspace);
-        const int total = filter_extent * val_dim * nr_filters;
-        const int bwd_t = ln_bwd_subtiles(mn);
-        if (nbr_q == nbr_n && mq == mn && ln_bwd_fused_shape(filter_extent, val_dim, nr_filters)) {
-            // same lattice on both sides: one gather per (vertex, slot) serves both gradients
-            const int wgs = ln_div_up(mn, 64 * bwd_t);
-#define LN_BWD_FUSED(TT)                                                                                                               \
-    case TT:                                                                                                                           \
-        if constexpr (TT <= LN_BWD_B3_MAX_T) { /* bf16 matrix cores, exactly split operands */                                         \
-            if (ln_conv_b3_enabled()) {                                                                                                \
-                LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused_b3<TT>), dim3(wgs), dim3(256 * TT), 0, st, nbr_n, values_neigh, grad_out, \
-                          filter, mn, grad_values, partial, g_ln_row_partition);                                                       \
-                break;                                                                                                                 \
-            }                                                                                                                          \
-        }                                                                                                                              \
-        LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused<32, 32, 9, TT>), dim3(wgs), dim3(256 * TT), 0, st, nbr_n, values_neigh, grad_out, \
-                  filter, mn, grad_values, partial);                                                                                   \
-        break;
-            switch (bwd_t) { LN_BWD_FUSED(1) LN_BWD_FUSED(2) LN_BWD_FUSED(3) LN_BWD_FUSED(4) }
-#undef LN_BWD_FUSED
-            (void)ln_reduce_slabs_async(partial, wgs, total, grad_filter, st);
-            return ln_check_launch("ln_conv_backward");
+    const LnBwdPlan p = ln_conv_backward_plan(LnBwdPlanIn{
+        mq, mn, filter_extent, val_dim, nr_filters, nbr_q == nbr_n,
+        nbr_q && nbr_n && values_neigh && grad_out && filter && grad_values && grad_filter, workspace ? workspace_bytes : 0,
+        ln_aligned16(values_neigh) && ln_aligned16(grad_out) && ln_aligned16(filter), ln_conv_b3_enabled()});
+    float* partial = static_cast<float*>(workspace);
+    const int total = filter_extent * val_dim * nr_filters;
+    if (p.form == LN_BWD_FUSED_B3 || p.form == LN_BWD_FUSED_F32) {
+        switch (p.t) {
+            case 1: ln_bwd_launch_fused<1>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
+            case 2: ln_bwd_launch_fused<2>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
+            case 3: ln_bwd_launch_fused<3>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
+            default: ln_bwd_launch_fused<4>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
         }
-        const int conv_blocks = ln_div_up(mn, 64);
-        const dim3 grid(conv_blocks + ln_div_up(total, 16)), block(256);
-#define LN_BWD_FULL(VV, NN)                                                                                                            \
-    if (!fused && V == VV && F == 16 * NN) {                                                                                           \
-        const int chunks = ln_gf_launch_partials(nbr_q, values_neigh, grad_out, mq, filter_extent, val_dim, nr_filters, partial, st);  \
-        LN_LAUNCH("k_conv_mfma", (k_conv_mfma_full<VV, NN, 9, true, true>), grid, block, 0, st, nbr_n, grad_out, filter, mn, grad_values, \
-                  conv_blocks, (const float*)partial, chunks, total, grad_filter);                                                      \
-        fused = true;                                                                                                                  \
+        (void)ln_reduce_slabs_async(partial, p.grid, total, grad_filter, st);
+        return ln_check_launch("ln_conv_backward");
     }
-        LN_BWD_FULL(32, 2) LN_BWD_FULL(32, 1) LN_BWD_FULL(16, 1) LN_BWD_FULL(16, 2) LN_BWD_FULL(16, 4) LN_BWD_FULL(8, 1) LN_BWD_FULL(8, 2)
-        LN_BWD_FULL(8, 4) LN_BWD_FULL(8, 8)
-#undef LN_BWD_FULL
+    if (p.form == LN_BWD_FULL_SUM) {
+        const LnGfPlan gf = ln_gf_plan(mq, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
+        ln_gf_launch_partials(gf, nbr_q, values_neigh, grad_out, mq, filter_extent, val_dim, nr_filters, partial, st);
+        ln_conv_launch_full<true, true>(nr_filters, val_dim / 16, dim3(p.grid), st, nbr_n, grad_out, filter, mn, grad_values, p.conv_blocks,
+                                        (const float*)partial, gf.chunks, total, grad_filter);
+        return ln_check_launch("ln_conv_backward");
     }
-    if (fused) return ln_check_launch("ln_conv_backward");
+    LnSlabSum sum = {nullptr, 0, 0, nullptr};
     int rc = ln_conv_grad_filter_impl(nbr_q, values_neigh, grad_out, mq, filter_extent, val_dim, nr_filters, grad_filter, workspace, workspace_bytes,
-                                      stream, true);
-    if (rc) {
-        (void)ln_take_slab_job();
-        return rc;
-    }
+                                      stream, &sum);
+    if (rc) return rc;
     // the value-gradient convolution may split over the filter slots: its partial slabs go behind the filter gradient's
-    size_t gf_bytes = (ln_conv_grad_filter_workspace_bytes(mq, filter_extent, val_dim, nr_filters) + 255) & ~size_t(255);
+    const size_t gf_bytes = ln_round256(ln_conv_grad_filter_workspace_bytes(mq, filter_extent, val_dim, nr_filters));
     char* conv_ws = (workspace && workspace_bytes > gf_bytes) ? static_cast<char*>(workspace) + gf_bytes : nullptr;
-    rc = ln_conv_forward_ws(nbr_n, grad_out, filter, mn, filter_extent, nr_filters, val_dim, LN_CONV_FLIP_NEIGHBOURS | LN_CONV_TRANSPOSED_FILTER,
-                            grad_values, conv_ws, conv_ws ? workspace_bytes - gf_bytes : 0, stream);
-    const LnSlabSum left = ln_take_slab_job();  // no bank split in that convolution (fp32 form, small filter): the sum as a launch of its own
-    if (left.partial) (void)ln_reduce_slabs_async(left.partial, left.nslabs, left.total, left.out, st);
+    rc = ln_conv_forward_riding(nbr_n, grad_out, filter, mn, filter_extent, nr_filters, val_dim, LN_CONV_FLIP_NEIGHBOURS | LN_CONV_TRANSPOSED_FILTER,
+                                grad_values, conv_ws, conv_ws ? workspace_bytes - gf_bytes : 0, stream, sum);
     return rc ? rc : ln_check_launch("ln_conv_backward");
 }
 
@@ -2739,8 +2548,7 @@ extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float*
 // grad_x = grad_y w as a plain-bank convolution — in that order, so that the slab sum of the first rides in the bank split of the
 // second (as in ln_conv_backward).  grad_x may be NULL.  workspace: ln_linear_backward_workspace_bytes.
 extern "C" size_t ln_linear_backward_workspace_bytes(int rows, int cin, int cout) {
-    const size_t gf = (ln_conv_grad_filter_workspace_bytes(rows, 1, cout, cin) + 255) & ~size_t(255);
-    return gf + ln_conv_forward_workspace_bytes(rows, 1, cout, cin) + 256;
+    return ln_linear_backward_query(rows, cin, cout, ln_conv_b3_enabled());
 }
 
 extern "C" int ln_linear_backward(const int* ident, const float* x, const float* grad_y, const float* w, int rows, int cin, int cout,
@@ -2748,18 +2556,13 @@ extern "C" int ln_linear_backward(const int* ident, const float* x, const float*
     LN_REQUIRE(rows >= 0 && cin >= 1 && cout >= 1 && grad_w, LN_ERR_ARG, "ln_linear_backward: bad sizes / null output");
     LN_REQUIRE(workspace && workspace_bytes >= ln_linear_backward_workspace_bytes(rows, cin, cout), LN_ERR_WORKSPACE,
                "ln_linear_backward: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t gf_bytes = (ln_conv_grad_filter_workspace_bytes(rows, 1, cout, cin) + 255) & ~size_t(255);
-    int rc = ln_conv_grad_filter_impl(ident, grad_y, x, rows, 1, cout, cin, grad_w, workspace, gf_bytes, stream, grad_x != nullptr);
-    if (rc) {
-        (void)ln_take_slab_job();
-        return rc;
-    }
-    if (grad_x && rows > 0) {
-        char* conv_ws = static_cast<char*>(workspace) + gf_bytes;
-        rc = ln_conv_forward_ws(ident, grad_y, w, rows, 1, cout, cin, 0, grad_x, conv_ws, workspace_bytes - gf_bytes, stream);
-    }
-    const LnSlabSum left = ln_take_slab_job();
-    if (left.partial) (void)ln_reduce_slabs_async(left.partial, left.nslabs, left.total, left.out, st);
+    const size_t gf_bytes = ln_round256(ln_conv_grad_filter_workspace_bytes(rows, 1, cout, cin));
+    const bool conv = grad_x && rows > 0;
+    LnSlabSum sum = {nullptr, 0, 0, nullptr};
+    int rc = ln_conv_grad_filter_impl(ident, grad_y, x, rows, 1, cout, cin, grad_w, workspace, gf_bytes, stream, conv ? &sum : nullptr);
+    if (rc) return rc;
+    if (conv)
+        rc = ln_conv_forward_riding(ident, grad_y, w, rows, 1, cout, cin, 0, grad_x, static_cast<char*>(workspace) + gf_bytes,
+                                    workspace_bytes - gf_bytes, stream, sum);
     return rc ? rc : ln_check_launch("ln_linear_backward");
 }
