@@ -104,7 +104,7 @@ typedef struct LnTable {
     int batch_key_step;            /* (pos_dim + 1) x the quotient distance between clouds; halved per coarser level so that the
                                       level-crossing neighbour search (keys x 2^(lvl difference)) stays inside a cloud */
     int* row_regions;              /* NULL, or LN_XCD_GROUPS + 1 device ints a bucketed build over a space-ordered table fills: the first row
-                                      of each of the 8 top-level kd regions and the row count — the argument of ln_conv_row_partition */
+                                      of each of the 8 top-level kd regions and the row count — the `row_partition` argument of the convolutions */
 } LnTable;
 
 /* Adjacency "group -> the tokens that touch it" in CSR form, cut into segments of at most 16
@@ -168,11 +168,6 @@ int ln_arena_init(int* arena, long long words, long long minus_begin, long long 
 /* Buckets (runs of consecutive slots, one workgroup of the bucketed build each) of a table that hashes into `capacity` slots: what a
  * host needs to lay out LnTable.slot_map. */
 int ln_table_bucket_count(int capacity);
-/* How many builds / scans the CALLING THREAD keeps in flight on this GPU (1 = one at a time, the default).  A speed hint for the builds
- * it issues afterwards: with several in flight the bucket pass of a build over small buckets runs on 512-thread workgroups, which finish
- * a bucket later but pack beside the other scans' kernels (ln_table.hip).  No effect on results.  (The reference has no counterpart: its
- * build is one stream's work, Lattice.cu:196-241.) */
-int ln_build_concurrency(int scans_in_flight);
 
 /* Scratch needed by ln_build_splat / ln_distribute / ln_coarsen for `tokens` insertions. */
 size_t ln_build_workspace_bytes(long long tokens, int capacity);
@@ -201,6 +196,10 @@ size_t ln_build_workspace_bytes(long long tokens, int capacity);
 #define LN_BUILD_SORTED_CSR 16    /* rewrite every token list of `csr` in ascending token order behind the build: the order tokens arrive in
                                      differs from run to run, and with it the last bits of every fp32 sum over them.  With LnCsr.dense & 2
                                      in the reduces: run-to-run identical splat values / slice and gather gradients */
+#define LN_BUILD_OVERLAPPED 32    /* the caller keeps several builds / scans in flight on this GPU.  A speed hint for this build: the bucket
+                                     pass of a build over small buckets then runs on 512-thread workgroups, which finish a bucket later but
+                                     pack beside the other scans' kernels (ln_table.hip).  No effect on results.  (The reference has no
+                                     counterpart: its build is one stream's work, Lattice.cu:196-241.) */
 int ln_build_splat(const LnTable* t, const float* positions_raw, const float* sigmas_host, int n, int* idx, float* w,
                    int flags, const LnCsr* csr, void* workspace, size_t workspace_bytes, float* clear_values,
                    long long clear_values_elems, void* stream);
@@ -315,23 +314,20 @@ int ln_conv_forward(const int* nbr, const float* values_neigh, const float* filt
 /* ln_conv_forward with scratch.  When the lattice has few vertices (coarse levels of a U-Net: fewer vertex tiles than CUs) the
  * contraction is split over the filter slots and the partial sums are added by a second launch; that needs
  * ln_conv_forward_workspace_bytes(m, filter_extent, val_dim, nr_filters) bytes of 16-byte aligned scratch (256 when no
- * split applies).  Without enough scratch it runs unsplit, exactly as ln_conv_forward. */
+ * split applies).  Without enough scratch it runs unsplit, exactly as ln_conv_forward.
+ * `row_partition` (may be NULL): work placement hint for the vertex-tiled kernels — LnTable.row_regions of the space-ordered table whose
+ * rows this call convolves over (device memory, 9 ints, read by the kernels at run time).  XCD x then works on the row tiles of kd
+ * region x, whose neighbour rows share its L2.  Purely a speed matter: any contents give correct results. */
 size_t ln_conv_bank_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters); /* the split-bank part (0: no split bank for these sizes) */
 size_t ln_conv_forward_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters);
 int ln_conv_forward_ws(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent, int val_dim,
-                       int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, void* stream);
+                       int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, const int* row_partition, void* stream);
 /* grad_filter = rowified^T @ grad_out (lattice_funcs.py:302) without the rowified tensor.
  * workspace: ln_conv_grad_filter_workspace_bytes(). */
 size_t ln_conv_grad_filter_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters);
 int ln_conv_grad_filter(const int* nbr, const float* values_neigh, const float* grad_out, int m, int filter_extent,
                         int val_dim, int nr_filters, float* grad_filter, void* workspace, size_t workspace_bytes,
                         void* stream);
-
-/* Work placement hint for the vertex-tiled convolution kernels (ln_conv_forward*, ln_conv_backward) of the CALLING THREAD: `row_starts`
- * = LnTable.row_regions of the space-ordered table whose rows the following calls convolve over (device memory, 9 ints, read by the
- * kernels at run time), or NULL to reset.  XCD x then works on the row tiles of kd region x, whose neighbour rows share its L2.
- * Purely a speed matter: any contents give correct results. */
-int ln_conv_row_partition(const int* row_starts);
 
 /* slice_with_precomputation (LatticeGPU.cuh:2552-2595). */
 int ln_slice_forward(const float* values, const int* idx, const float* w, int n, int pos_dim, int val_dim, float* out,
@@ -383,10 +379,13 @@ int ln_slice_classify_backward(const float* grad_logits, const float* values, co
  * grad_filter as ln_conv_grad_filter(nbr_q, values_neigh, grad_out, mq, ..), grad_values[mn, val_dim] as
  * ln_conv_forward(nbr_n, grad_out, filter, mn, E, nr_filters, val_dim, FLIP | TRANSPOSED_FILTER) where nbr_n is the
  * neighbour list with the query / neighbour roles swapped.  For the small-filter shapes the slab sum of the filter
- * gradient runs inside the value-gradient launch.  workspace: ln_conv_grad_filter_workspace_bytes(mq, ..). */
+ * gradient runs inside the value-gradient launch.  workspace: ln_conv_backward_workspace_bytes (with less, down to
+ * ln_conv_grad_filter_workspace_bytes(mq, ..), the value-gradient convolution runs without bank or slot split).  `row_partition` (may be
+ * NULL) as for ln_conv_forward_ws: the table of the rows when both sides are the same lattice. */
+size_t ln_conv_backward_workspace_bytes(int mq, int mn, int filter_extent, int val_dim, int nr_filters);
 int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter, int mq, int mn,
                      int filter_extent, int val_dim, int nr_filters, float* grad_values, float* grad_filter, void* workspace,
-                     size_t workspace_bytes, void* stream);
+                     size_t workspace_bytes, const int* row_partition, void* stream);
 
 /* Half-precision feature path of the scatters and the slice (C5: "features fp16, accumulate fp32"): the segment reduce with
  * fp16 source rows (fp32 weights, fp32 accumulation into an fp32 dst) — plain and fused with the neighbour traversal — and the

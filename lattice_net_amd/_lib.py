@@ -20,6 +20,7 @@ LN_BUILD_CLEAR_FIRST = 2
 LN_BUILD_ATOMIC_PATH = 4
 LN_BUILD_CANONICAL_ROWS = 8
 LN_BUILD_SORTED_CSR = 16
+LN_BUILD_OVERLAPPED = 32
 LN_NOT_VISITED = -2
 LN_CONV_FLIP_NEIGHBOURS = 1
 LN_CONV_TRANSPOSED_FILTER = 2
@@ -91,7 +92,6 @@ SIGNATURES = {
     "ln_table_clear": (_i, [_T, _vp, _ll, _vp]),
     "ln_build_workspace_bytes": (_sz, [_ll, _i]),
     "ln_table_bucket_count": (_i, [_i]),
-    "ln_build_concurrency": (_i, [_i]),
     "ln_build_splat": (_i, [_T, _vp, _vp, _i, _vp, _vp, _i, _CSR, _vp, _sz, _vp, _ll, _vp]),
     "ln_rehash": (_i, [_T, _vp]),
     "ln_canonicalize": (_i, [_T, _vp, _ll, _CSR, _vp, _sz, _vp]),
@@ -113,13 +113,12 @@ SIGNATURES = {
     "ln_conv_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ln_conv_forward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ln_conv_bank_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ln_conv_forward_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ln_conv_forward_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "ln_conv_grad_filter_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ln_conv_grad_filter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ln_slice_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ln_slice_forward_prepare_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
     "ln_slice_forward_ordered": (_i, [_T, _CSR, _vp, _vp, _vp, _i, _i, _vp, _vp, _ll, _vp]),
-    "ln_conv_row_partition": (_i, [_vp]),
     "ln_slice_no_precomputation": (_i, [_T, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ln_slice_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ln_gather_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -129,7 +128,8 @@ SIGNATURES = {
     "ln_splat_accumulate_and_neighbours_f16": (_i, [_CSR, _vp, _ll, _vp, _vp, _i, _i, _i, _vp, _T, _i, _vp, _vp]),
     "ln_slice_forward_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ln_slice_forward_f16_prepare_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
-    "ln_conv_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ln_conv_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ln_conv_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "ln_conv_forward_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ln_conv_grad_filter_f16_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ln_conv_grad_filter_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

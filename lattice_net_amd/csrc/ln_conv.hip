@@ -1217,14 +1217,6 @@ extern "C" size_t ln_conv_forward_workspace_bytes(int m, int filter_extent, int 
     return ln_conv_forward_query(m, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
 }
 
-// ln_conv_row_partition: LnTable.row_regions of the space-ordered table the next convolutions of this thread run over (device memory,
-// read by the kernels; nullptr = none).  A placement hint only — ln_partition_tile is a bijection whatever the array holds.
-static thread_local const int* g_ln_row_partition = nullptr;
-extern "C" int ln_conv_row_partition(const int* row_starts) {
-    g_ln_row_partition = row_starts;
-    return LN_OK;
-}
-
 // ------------------------------------------------------------------------------------------
 // Forward of the V = F = 32, E = 9 convolution on the bf16 matrix cores with exactly 3-way split operands, in the workgroup shape of
 // the fused backward (T sub-tiles of 64 vertices per workgroup, one workgroup per CU and round: the bank is split and staged once per
@@ -1394,6 +1386,8 @@ struct LnConvCall {
     float* dst;            // the slabs with a slot split, else out
     int e_per;
     LnSlabSum sum;         // rides in the launch that has carries_sum
+    const int* row_partition;  // LnTable.row_regions of the space-ordered table the rows belong to (device memory, read by the kernels;
+                               // nullptr = none).  A placement hint only: ln_partition_tile is a bijection whatever the array holds
     hipStream_t st;
 };
 
@@ -1514,9 +1508,9 @@ static void ln_conv_run(const LnConvPlan& p, const LnConvCall<FLIP, WT>& c) {
         switch (l.kernel) {
             case LN_K_FORWARD_B3:
                 if constexpr (!FLIP && !WT) {
-                    if (l.t == 1) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<1>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, g_ln_row_partition);
-                    else if (l.t == 2) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<2>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, g_ln_row_partition);
-                    else LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<3>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, g_ln_row_partition);
+                    if (l.t == 1) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<1>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, c.row_partition);
+                    else if (l.t == 2) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<2>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, c.row_partition);
+                    else LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<3>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, c.row_partition);
                 }
                 break;
             case LN_K_FULL:
@@ -1548,13 +1542,13 @@ static void ln_conv_run(const LnConvPlan& p, const LnConvCall<FLIP, WT>& c) {
 
 template <bool FLIP, bool WT>
 static void ln_conv_plan_and_run(LnConvPlanIn in, const int* nbr, const float* values, const float* filter, float* out, void* ws,
-                                 const LnSlabSum& sum, bool* sum_left, hipStream_t st) {
+                                 const LnSlabSum& sum, bool* sum_left, const int* row_partition, hipStream_t st) {
     in.flip = FLIP;
     in.wt = WT;
     const LnConvPlan p = ln_conv_plan(in);
     char* slabs = static_cast<char*>(ws) + p.bank_bytes;
     ln_conv_run<FLIP, WT>(p, LnConvCall<FLIP, WT>{nbr, values, filter, in.m, in.E, in.V, in.F, out, static_cast<unsigned short*>(ws),
-                                                 p.nsplit > 1 ? reinterpret_cast<float*>(slabs) : out, p.e_per, sum, st});
+                                                 p.nsplit > 1 ? reinterpret_cast<float*>(slabs) : out, p.e_per, sum, row_partition, st});
     *sum_left = p.sum_left;
 }
 
@@ -1562,8 +1556,8 @@ static void ln_conv_plan_and_run(LnConvPlanIn in, const int* nbr, const float* v
 // A bank split of this convolution carries it where there is one; otherwise it goes out here as a launch of its own, behind the
 // convolution's, whatever became of the call.
 static int ln_conv_forward_riding(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent, int val_dim,
-                                  int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, void* stream,
-                                  const LnSlabSum& sum) {
+                                  int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, const int* row_partition,
+                                  void* stream, const LnSlabSum& sum) {
     hipStream_t st = (hipStream_t)stream;
     bool sum_left = sum.partial != nullptr;
     const int rc = [&]() -> int {
@@ -1582,10 +1576,10 @@ static int ln_conv_forward_riding(const int* nbr, const float* values_neigh, con
         in.bank_ready = (flags & LN_CONV_BANK_READY) != 0 && workspace != nullptr;
         in.riding_total = sum.partial ? sum.total : 0;
         switch (flags & 3) {
-            case 0: ln_conv_plan_and_run<false, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
-            case LN_CONV_FLIP_NEIGHBOURS: ln_conv_plan_and_run<true, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
-            case LN_CONV_TRANSPOSED_FILTER: ln_conv_plan_and_run<false, true>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
-            default: ln_conv_plan_and_run<true, true>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, st); break;
+            case 0: ln_conv_plan_and_run<false, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, row_partition, st); break;
+            case LN_CONV_FLIP_NEIGHBOURS: ln_conv_plan_and_run<true, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, row_partition, st); break;
+            case LN_CONV_TRANSPOSED_FILTER: ln_conv_plan_and_run<false, true>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, row_partition, st); break;
+            default: ln_conv_plan_and_run<true, true>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, row_partition, st); break;
         }
         return ln_check_launch("ln_conv_forward");
     }();
@@ -1594,14 +1588,15 @@ static int ln_conv_forward_riding(const int* nbr, const float* values_neigh, con
 }
 
 extern "C" int ln_conv_forward_ws(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent, int val_dim,
-                                  int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    return ln_conv_forward_riding(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, flags, out, workspace, workspace_bytes, stream,
-                                  LnSlabSum{nullptr, 0, 0, nullptr});
+                                  int nr_filters, int flags, float* out, void* workspace, size_t workspace_bytes, const int* row_partition,
+                                  void* stream) {
+    return ln_conv_forward_riding(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, flags, out, workspace, workspace_bytes,
+                                  row_partition, stream, LnSlabSum{nullptr, 0, 0, nullptr});
 }
 
 extern "C" int ln_conv_forward(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent,
                                int val_dim, int nr_filters, int flags, float* out, void* stream) {
-    return ln_conv_forward_ws(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, flags, out, nullptr, 0, stream);
+    return ln_conv_forward_ws(nbr, values_neigh, filter, m, filter_extent, val_dim, nr_filters, flags, out, nullptr, 0, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2492,11 +2487,11 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
 // the convolution launch.
 template <int T>
 static void ln_bwd_launch_fused(const LnBwdPlan& p, const int* nbr, const float* values, const float* grad_out, const float* filter, int m,
-                                float* grad_values, float* partial, hipStream_t st) {
+                                float* grad_values, float* partial, const int* row_partition, hipStream_t st) {
     if constexpr (T <= LN_BWD_B3_MAX_T) {  // bf16 matrix cores, exactly split operands
         if (p.form == LN_BWD_FUSED_B3) {
             LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused_b3<T>), dim3(p.grid), dim3(p.block), 0, st, nbr, values, grad_out, filter, m,
-                      grad_values, partial, g_ln_row_partition);
+                      grad_values, partial, row_partition);
             return;
         }
     }
@@ -2504,9 +2499,13 @@ static void ln_bwd_launch_fused(const LnBwdPlan& p, const int* nbr, const float*
               grad_values, partial);
 }
 
+extern "C" size_t ln_conv_backward_workspace_bytes(int mq, int mn, int filter_extent, int val_dim, int nr_filters) {
+    return ln_conv_backward_query(mq, mn, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
+}
+
 extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter, int mq,
                                 int mn, int filter_extent, int val_dim, int nr_filters, float* grad_values, float* grad_filter,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+                                void* workspace, size_t workspace_bytes, const int* row_partition, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const LnBwdPlan p = ln_conv_backward_plan(LnBwdPlanIn{
         mq, mn, filter_extent, val_dim, nr_filters, nbr_q == nbr_n,
@@ -2516,10 +2515,10 @@ extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float*
     const int total = filter_extent * val_dim * nr_filters;
     if (p.form == LN_BWD_FUSED_B3 || p.form == LN_BWD_FUSED_F32) {
         switch (p.t) {
-            case 1: ln_bwd_launch_fused<1>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
-            case 2: ln_bwd_launch_fused<2>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
-            case 3: ln_bwd_launch_fused<3>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
-            default: ln_bwd_launch_fused<4>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, st); break;
+            case 1: ln_bwd_launch_fused<1>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, row_partition, st); break;
+            case 2: ln_bwd_launch_fused<2>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, row_partition, st); break;
+            case 3: ln_bwd_launch_fused<3>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, row_partition, st); break;
+            default: ln_bwd_launch_fused<4>(p, nbr_n, values_neigh, grad_out, filter, mn, grad_values, partial, row_partition, st); break;
         }
         (void)ln_reduce_slabs_async(partial, p.grid, total, grad_filter, st);
         return ln_check_launch("ln_conv_backward");
@@ -2536,10 +2535,10 @@ extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float*
                                       stream, &sum);
     if (rc) return rc;
     // the value-gradient convolution may split over the filter slots: its partial slabs go behind the filter gradient's
-    const size_t gf_bytes = ln_round256(ln_conv_grad_filter_workspace_bytes(mq, filter_extent, val_dim, nr_filters));
+    const size_t gf_bytes = ln_bwd_gf_bytes(mq, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
     char* conv_ws = (workspace && workspace_bytes > gf_bytes) ? static_cast<char*>(workspace) + gf_bytes : nullptr;
     rc = ln_conv_forward_riding(nbr_n, grad_out, filter, mn, filter_extent, nr_filters, val_dim, LN_CONV_FLIP_NEIGHBOURS | LN_CONV_TRANSPOSED_FILTER,
-                                grad_values, conv_ws, conv_ws ? workspace_bytes - gf_bytes : 0, stream, sum);
+                                grad_values, conv_ws, conv_ws ? workspace_bytes - gf_bytes : 0, row_partition, stream, sum);
     return rc ? rc : ln_check_launch("ln_conv_backward");
 }
 
@@ -2556,13 +2555,13 @@ extern "C" int ln_linear_backward(const int* ident, const float* x, const float*
     LN_REQUIRE(rows >= 0 && cin >= 1 && cout >= 1 && grad_w, LN_ERR_ARG, "ln_linear_backward: bad sizes / null output");
     LN_REQUIRE(workspace && workspace_bytes >= ln_linear_backward_workspace_bytes(rows, cin, cout), LN_ERR_WORKSPACE,
                "ln_linear_backward: workspace too small");
-    const size_t gf_bytes = ln_round256(ln_conv_grad_filter_workspace_bytes(rows, 1, cout, cin));
+    const size_t gf_bytes = ln_bwd_gf_bytes(rows, 1, cout, cin, ln_conv_b3_enabled());
     const bool conv = grad_x && rows > 0;
     LnSlabSum sum = {nullptr, 0, 0, nullptr};
     int rc = ln_conv_grad_filter_impl(ident, grad_y, x, rows, 1, cout, cin, grad_w, workspace, gf_bytes, stream, conv ? &sum : nullptr);
     if (rc) return rc;
     if (conv)
         rc = ln_conv_forward_riding(ident, grad_y, w, rows, 1, cout, cin, 0, grad_x, static_cast<char*>(workspace) + gf_bytes,
-                                    workspace_bytes - gf_bytes, stream, sum);
+                                    workspace_bytes - gf_bytes, nullptr, stream, sum);
     return rc ? rc : ln_check_launch("ln_linear_backward");
 }

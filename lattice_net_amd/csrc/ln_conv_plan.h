@@ -364,9 +364,19 @@ constexpr size_t ln_gf_query(int m, int E, int V, int F, bool b3_enabled) {
     return (size_t)chunks * E * V * F * sizeof(float) + 256;
 }
 constexpr size_t ln_round256(size_t b) { return (b + 255) & ~size_t(255); }
+// Both backward calls lay their workspace out as [filter gradient's slabs, rounded to 256][workspace of the value-gradient
+// convolution]: the split point, read by the queries below and by the calls themselves
+constexpr size_t ln_bwd_gf_bytes(int m, int E, int V, int F, bool b3_enabled) { return ln_round256(ln_gf_query(m, E, V, F, b3_enabled)); }
 // ln_linear_backward_workspace_bytes: [filter gradient's slabs][workspace of the grad_x convolution]
 constexpr size_t ln_linear_backward_query(int rows, int cin, int cout, bool b3_enabled) {
-    return ln_round256(ln_gf_query(rows, 1, cout, cin, b3_enabled)) + ln_conv_forward_query(rows, 1, cout, cin, b3_enabled) + 256;
+    return ln_bwd_gf_bytes(rows, 1, cout, cin, b3_enabled) + ln_conv_forward_query(rows, 1, cout, cin, b3_enabled) + 256;
+}
+// ln_conv_backward_workspace_bytes: [filter gradient's slabs][workspace of the value-gradient convolution over (mn, E, F -> V)]; the
+// second part (and the rounding in front of it) only where that convolution takes a bank or splits its slots.  (The byte counts are
+// part of the ABI: what hosts allocated before this query existed.)
+constexpr size_t ln_conv_backward_query(int mq, int mn, int E, int V, int F, bool b3_enabled) {
+    const size_t conv = ln_conv_forward_query(mn, E, F, V, b3_enabled);
+    return conv > 256 ? ln_bwd_gf_bytes(mq, E, V, F, b3_enabled) + conv : ln_gf_query(mq, E, V, F, b3_enabled);
 }
 
 enum LnGfForm : uint8_t {

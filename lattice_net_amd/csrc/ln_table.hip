@@ -575,12 +575,6 @@ __global__ void __launch_bounds__(TH)
 #ifndef LN_BKT_NARROW_TOKENS
 #define LN_BKT_NARROW_TOKENS 4096  // tokens per bucket up to which overlapping builds take 512-thread bucket workgroups
 #endif
-// ln_build_concurrency: how many builds / scans the caller keeps in flight on this GPU (thread-local, 1 = one at a time)
-static thread_local int g_ln_build_concurrency = 1;
-extern "C" int ln_build_concurrency(int scans_in_flight) {
-    g_ln_build_concurrency = scans_in_flight > 1 ? scans_in_flight : 1;
-    return LN_OK;
-}
 #define LN_BKT_LDS_LIMIT (150 * 1024)  // dynamic LDS one k_bucket_rows workgroup may ask for (160 KB per CU minus its static arrays)
 #define LN_BKT_LDS_PER_SLOT (sizeof(unsigned long long) + 7 * sizeof(int))
 #define LN_BKT_LDS_EXTRA 32  // alignment of the compacted token list + its padding to a multiple of four entries
@@ -879,7 +873,7 @@ __global__ void __launch_bounds__(TH)
     }
     const int placed = s_run_tok;
     const int new_here = s_run_new;
-    if (t.row_regions && tid == 0 && slot_ordered) {  // first row of each kd region (the argument of ln_conv_row_partition)
+    if (t.row_regions && tid == 0 && slot_ordered) {  // first row of each kd region (the row_partition argument of the convolutions)
         const int bpr = nbk / LN_XCD_GROUPS;
         if (b % bpr == 0) t.row_regions[b / bpr] = base_row;
         if (b == nbk - 1) t.row_regions[LN_XCD_GROUPS] = base_row + new_here;
@@ -1368,8 +1362,8 @@ static int ln_build_points(const LnTable* t, const float* positions_raw, const f
             // on 512 threads), but one such workgroup takes half a CU's wave slots; with several scans in flight the narrower workgroups
             // pack beside the other scans' kernels: C3 1407 -> 1441 Mpoints/s, C4 (3 100 tokens per bucket) 947 -> 980, C2 with 16 clouds
             // per step 494 -> 508 — C5, 7 500 tokens per bucket, 1421 -> 1401 (LN_BKT_THREADS=512 builds, one box).  The caller says
-            // whether builds overlap with other work (ln_build_concurrency); alone, and on big buckets, 1024 stays.
-            const bool narrow = g_ln_build_concurrency > 1 && tokens <= (long long)LN_BKT_NARROW_TOKENS * nbk;
+            // whether builds overlap with other work (LN_BUILD_OVERLAPPED); alone, and on big buckets, 1024 stays.
+            const bool narrow = (flags & LN_BUILD_OVERLAPPED) && tokens <= (long long)LN_BKT_NARROW_TOKENS * nbk;
             if (narrow)
                 LN_LAUNCH("k_bucket_rows", (k_bucket_rows<D, 512>), dim3(nbk), dim3(512), lds, st, *t, sb, nbk, ws.capb, t->slot_cnt,
                       ws.part_tok, ws.part_pk, ws.part_slot, ws.part_pos, dropped_idx, *csr, ws.pub);

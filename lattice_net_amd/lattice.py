@@ -114,7 +114,7 @@ def set_slot_order(order: str) -> str:
 
 
 # How many scans the caller keeps in flight on this GPU (own lattice and stream each: bench.py's throughput mode, a data loader that
-# builds ahead).  Passed to the library with every build (ln_build_concurrency): overlapping builds over small buckets take narrower
+# builds ahead).  Above 1 every build carries LN_BUILD_OVERLAPPED: overlapping builds over small buckets take narrower
 # bucket-pass workgroups.  A speed hint only; a captured graph keeps what was set when it was captured.
 _SCANS_IN_FLIGHT = [max(1, int(os.environ.get("LATTICE_SCANS_IN_FLIGHT", "1")))]
 
@@ -280,7 +280,8 @@ class _TableStorage:
         if self.planes is None or _SLOT_ORDER[0] != "space":
             self.slot_map, self.slot_map_sb_max = None, 0
             return
-        key = (self.plane_values, self.leaf_shares, self.hashed())
+        # (the device as the table's own tensors report it: a map is device memory, and `self.device` may come without an index)
+        key = (self.plane_values, self.leaf_shares, self.hashed(), self.slot_keys.device.index)
         hit = _SLOT_MAPS.get(key)
         if hit is None:
             hit = _make_slot_map(self.plane_values, self.leaf_shares, self.hashed(), self.device)
@@ -708,8 +709,9 @@ class Lattice:
                 flags |= _lib.LN_BUILD_CANONICAL_ROWS
             if _DETERMINISTIC[0]:
                 flags |= _lib.LN_BUILD_SORTED_CSR
+            if _SCANS_IN_FLIGHT[0] > 1:
+                flags |= _lib.LN_BUILD_OVERLAPPED
             cv, cn = _lib.ptr(clear_vals), clear_elems
-            lib.ln_build_concurrency(_SCANS_IN_FLIGHT[0])  # (thread-local in the library: an assignment)
             ht.arm_count_readback()  # t is ht's cached struct: the sequence number travels in it
             if distributed is None:
                 rc = lib.ln_build_splat(C.byref(t), _lib.ptr(positions_raw), self._sigmas_host(), n, _lib.ptr(idx), _lib.ptr(w), flags,
@@ -1050,7 +1052,7 @@ class Lattice:
 
     def _row_partition(self):
         """Device pointer of LnTable.row_regions when the rows of this lattice follow space (bucketed build over space-ordered slots),
-        else None: the argument of ln_conv_row_partition for convolutions whose output rows are this lattice's."""
+        else None: the `row_partition` argument of convolutions whose output rows are this lattice's."""
         st = self.m_hash_table._storage
         if st is None or not st.rows_follow_space or st.row_regions is None:
             return None
@@ -1115,16 +1117,9 @@ class Lattice:
                     ws, flags = hit[1], flags | _lib.LN_CONV_BANK_READY
             if ws is None and wsb > 256:
                 ws = torch.empty((wsb,), dtype=torch.uint8, device=self._dev())
-            part = self._row_partition()
-            if part is not None:
-                lib.ln_conv_row_partition(part)
-            try:
-                _lib.check(lib.ln_conv_forward_ws(_lib.ptr(nbr), _lib.ptr(vals), _lib.ptr(filter_bank), m, filter_extent, v, nr_filters, flags,
-                                                  _lib.ptr(out), _lib.ptr(ws), 0 if ws is None else ws.numel(), self._stream()),
-                           "ln_conv_forward")
-            finally:
-                if part is not None:
-                    lib.ln_conv_row_partition(None)
+            _lib.check(lib.ln_conv_forward_ws(_lib.ptr(nbr), _lib.ptr(vals), _lib.ptr(filter_bank), m, filter_extent, v, nr_filters, flags,
+                                              _lib.ptr(out), _lib.ptr(ws), 0 if ws is None else ws.numel(), self._row_partition(),
+                                              self._stream()), "ln_conv_forward")
             if key is not None and not (flags & _lib.LN_CONV_BANK_READY):
                 try:
                     _BANK_ENTRIES[filter_bank] = (key, ws)
@@ -1161,12 +1156,8 @@ class Lattice:
         if filter_bank.dtype != grad_out.dtype or nb.values().dtype != grad_out.dtype:
             raise ValueError("grad_out, filter bank and lattice values must share one dtype (float32 or float16)")
         gf = torch.empty((E * v, f), dtype=torch.float32, device=dev)
-        ws_bytes = lib.ln_conv_grad_filter_f16_workspace_bytes(mq, E, v, f) if half else lib.ln_conv_grad_filter_workspace_bytes(mq, E, v, f)
-        ws_bytes = int(ws_bytes)
-        if not half:  # + the slot-split partials of the value-gradient convolution (behind the filter gradient's slabs)
-            conv_ws = int(lib.ln_conv_forward_workspace_bytes(int(nb.nr_lattice_vertices()), E, f, v))
-            if conv_ws > 256:
-                ws_bytes = ((ws_bytes + 255) // 256) * 256 + conv_ws
+        ws_bytes = int(lib.ln_conv_grad_filter_f16_workspace_bytes(mq, E, v, f) if half else
+                       lib.ln_conv_backward_workspace_bytes(mq, int(nb.nr_lattice_vertices()), E, v, f))
         ws = torch.empty((max(ws_bytes, 256),), dtype=torch.uint8, device=dev)
         # ---- value gradient on the main stream: the query and neighbour roles swap (funcs:307-313, 380-387)
         nbr_n = nb.neighbours(q, dilation, False)
@@ -1183,14 +1174,8 @@ class Lattice:
         # both kernels already fill the chip and the event hand-offs cost more than the overlap.  What does pay is
         # putting the slab sum of the filter gradient into the value-gradient launch: ln_conv_backward.)
         part = nb._row_partition() if q.m_hash_table._storage is nb.m_hash_table._storage else None
-        if part is not None:
-            lib.ln_conv_row_partition(part)
-        try:
-            _lib.check(lib.ln_conv_backward(_lib.ptr(nbr_q), _lib.ptr(nbr_n), _lib.ptr(nb.values()), _lib.ptr(grad_out), _lib.ptr(filter_bank), mq,
-                                            mn, E, v, f, _lib.ptr(gvals), _lib.ptr(gf), _lib.ptr(ws), ws.numel(), main), "ln_conv_backward")
-        finally:
-            if part is not None:
-                lib.ln_conv_row_partition(None)
+        _lib.check(lib.ln_conv_backward(_lib.ptr(nbr_q), _lib.ptr(nbr_n), _lib.ptr(nb.values()), _lib.ptr(grad_out), _lib.ptr(filter_bank), mq,
+                                        mn, E, v, f, _lib.ptr(gvals), _lib.ptr(gf), _lib.ptr(ws), ws.numel(), part, main), "ln_conv_backward")
         return gvals, gf
 
     def convolve_im2row_grad_filter(self, grad_out: torch.Tensor, dilation: int, lattice_neighbours: Optional["Lattice"],
@@ -1592,7 +1577,7 @@ class Lattice:
     def set_region_planes(self, planes, leaf_shares=None):
         """kd split planes of key space (7 ints: 1 + 2 + 4 thresholds in heap order, see LnCsr.planes) or None.  With planes, the builds
         of this lattice file the CSR segments of every vertex under one of 8 compact regions and the scatter kernels let XCD r walk
-        region r; under set_slot_order("space") (the default) the planes also order the SLOTS — and with them the rows — of the table
+        region r; under set_slot_order("space") (the default is "hash") the planes also order the SLOTS — and with them the rows — of the table
         by space, from the next build that starts with a clear on (LnTable.slot_map).  `leaf_shares` (8 floats, optional): the share
         of the vertices each region is expected to hold (balanced_region_planes(..., return_shares=True)): the slot run of a region is
         sized with it; without it the regions get equal runs, which suits planes that balance VERTICES."""

@@ -185,7 +185,7 @@ class LinearMfmaFunction(torch.autograd.Function):
         # with its workspace the convolution takes the bf16x3 kernel from 4096 rows on (widths that are multiples of 32 / 16)
         ws = _conv_workspace(lib, rows, cin, cout, x.device)
         _lib.check(lib.ln_conv_forward_ws(_lib.ptr(ident), _lib.ptr(x), _lib.ptr(w), rows, 1, cin, cout, 2, _lib.ptr(y), _lib.ptr(ws),
-                                          0 if ws is None else ws.numel(), _lib.stream_ptr(x.device)), "ln_conv_forward(1x1)")  # 2 = LN_CONV_TRANSPOSED_FILTER
+                                          0 if ws is None else ws.numel(), None, _lib.stream_ptr(x.device)), "ln_conv_forward(1x1)")  # 2 = LN_CONV_TRANSPOSED_FILTER
         ctx.save_for_backward(x, w)
         return y
 

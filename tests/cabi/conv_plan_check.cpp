@@ -1,7 +1,7 @@
 // Host-only check of the convolution launch plans (lattice_net_amd/csrc/ln_conv_plan.h, the only project header included): built
 // with the host compiler under -fsanitize=address,undefined by tests/test_conv_plan.py.  Walks a grid of shapes around every
 // boundary of the dispatch and checks each plan's invariants; prints the size queries (`Q ...` lines) for the test to compare with
-// the library's C ABI.  argv[1]: 1 = bf16x3 path enabled (the library's default), 0 = LN_CONV_EXACT_F32=1.
+// the library's C ABI (the last three: ln_conv_backward's at mn = m, m / 2 + 1, 2 m).  argv[1]: 1 = bf16x3 path enabled (the library's default), 0 = LN_CONV_EXACT_F32=1.
 #include "ln_conv_plan.h"
 
 #include <stdio.h>
@@ -93,8 +93,10 @@ int main(int argc, char** argv) {
             for (int V : cs)
                 for (int F : cs) {
                     const size_t q = ln_conv_forward_query(m, E, V, F, b3);
-                    printf("Q %d %d %d %d %zu %zu %zu %zu\n", m, E, V, F, q, ln_conv_bank_query(m, E, V, F, b3), ln_gf_query(m, E, V, F, b3),
-                           E == 1 ? ln_linear_backward_query(m, F, V, b3) : (size_t)0);
+                    const int mns[3] = {m, m / 2 + 1, 2 * m};  // rows of the neighbour side of a backward whose query side has m
+                    printf("Q %d %d %d %d %zu %zu %zu %zu %zu %zu %zu\n", m, E, V, F, q, ln_conv_bank_query(m, E, V, F, b3), ln_gf_query(m, E, V, F, b3),
+                           E == 1 ? ln_linear_backward_query(m, F, V, b3) : (size_t)0, ln_conv_backward_query(m, mns[0], E, V, F, b3),
+                           ln_conv_backward_query(m, mns[1], E, V, F, b3), ln_conv_backward_query(m, mns[2], E, V, F, b3));
                     for (int flags = 0; flags < 8; ++flags)
                         for (int riding = 0; riding <= 1; ++riding) {
                             LnConvPlanIn in = {m, E, V, F, (flags & 1) != 0, (flags & 2) != 0, b3, true, true, true, ~size_t(0) >> 1, (flags & 4) != 0,
@@ -147,6 +149,22 @@ int main(int argc, char** argv) {
                             } else if (bp.form == LN_BWD_FULL_SUM) {
                                 CHECK(ln_conv_full_shape(F, V) && bp.grid > bp.conv_blocks && (long long)bp.conv_blocks * 64 >= m);
                             }
+                        }
+                    // ln_conv_backward's own query: room for the filter gradient, the form of a generous workspace, and for the value-gradient
+                    // convolution (mn rows, F channels in, V out, flipped, transposed bank) the layout its own query gives it
+                    for (int mn : mns)
+                        for (int same = 0; same <= 1; ++same) {
+                            const size_t bq = ln_conv_backward_query(m, mn, E, V, F, b3), gfb = ln_bwd_gf_bytes(m, E, V, F, b3);
+                            CHECK(bq >= ln_gf_query(m, E, V, F, b3));
+                            const LnBwdPlan bp = ln_conv_backward_plan(LnBwdPlanIn{m, mn, E, V, F, same != 0, true, bq, true, b3});
+                            CHECK(bp.form == ln_conv_backward_plan(LnBwdPlanIn{m, mn, E, V, F, same != 0, true, 16 * bq, true, b3}).form);
+                            if (bp.form != LN_BWD_TWO_CALLS) continue;
+                            LnConvPlanIn vin = {mn, E, F, V, true, true, b3, true, true, bq > gfb, bq > gfb ? bq - gfb : 0, false, E * V * F / 64 * 64};
+                            const LnConvPlan behind = check_plan(vin);
+                            vin.ws_aligned = true;
+                            vin.ws_bytes = ln_conv_forward_query(mn, E, F, V, b3);
+                            const LnConvPlan queried = check_plan(vin);
+                            CHECK(behind.nsplit == queried.nsplit && behind.bank_bytes == queried.bank_bytes);
                         }
                 }
     printf("PLANS OK %ld\n", g_checked);

@@ -42,9 +42,12 @@ def test_plan_sizes_are_the_c_abi_queries(plan_check):
     b3 = os.environ.get("LN_CONV_EXACT_F32", "")[:1] != "1"  # (the library reads the switch once per process)
     rows = _run(plan_check, b3)
     assert len(rows) > 20000
-    for m, e, v, f, fwd, bank, gf, lin in rows:
+    for m, e, v, f, fwd, bank, gf, lin, *bwd in rows:
         assert lib.ln_conv_forward_workspace_bytes(m, e, v, f) == fwd, (m, e, v, f)
         assert lib.ln_conv_bank_workspace_bytes(m, e, v, f) == bank, (m, e, v, f)
         assert lib.ln_conv_grad_filter_workspace_bytes(m, e, v, f) == gf, (m, e, v, f)
         if e == 1:
             assert lib.ln_linear_backward_workspace_bytes(m, f, v) == lin, (m, v, f)
+        assert len(bwd) == 3
+        for mn, want in zip((m, m // 2 + 1, 2 * m), bwd):
+            assert lib.ln_conv_backward_workspace_bytes(m, mn, e, v, f) == want, (m, mn, e, v, f)

@@ -394,7 +394,7 @@ def test_cloud_far_beyond_the_static_bound_fills_the_shrunk_range_without_hangin
 @pytest.mark.parametrize("d,n,sigma,cap", [(3, 120000, 0.9, 100000), (3, 2500, 0.05, 60000), (2, 40000, 0.3, 30000), (5, 6000, 0.4, 80000),
                                            (3, 200000, 0.08, 5000000)])
 def test_bucket_pass_workgroup_size_is_invisible(d, n, sigma, cap, monkeypatch):
-    """ln_build_concurrency (lattice.set_scans_in_flight): with several scans in flight the bucket pass of a build over small buckets runs
+    """LN_BUILD_OVERLAPPED (lattice.set_scans_in_flight): with several scans in flight the bucket pass of a build over small buckets runs
     on 512-thread workgroups instead of 1024 (ln_table.hip: k_bucket_rows<D, TH>).  Rows are numbered bucket by bucket either way: indices,
     weights, keys, vertex count, the CSR's per-vertex token counts and the neighbour list must be identical bit for bit — and equal to the
     oracle's in the canonical numbering."""

@@ -355,7 +355,8 @@ def test_canonical_numbering_over_space_ordered_slots_is_the_oracles():
 
 def test_conv_row_partition_is_a_placement_hint_only():
     """The convolution kernels under arbitrary partition arrays (garbage, all zero, reversed): ln_partition_tile is a bijection whatever it
-    reads, so forward and both gradients come out bit-identical to the run without a partition."""
+    reads, so forward and both gradients come out bit-identical to the run without a partition.  The partition is an argument of the
+    call and of that call only: a call without one behind a call with a garbage one gives the bits of the reference run."""
     import lattice_net_amd as L
     from lattice_net_amd import _lib, synthetic
     n, v, f, sigma, cap = 40000, 32, 32, 0.9, 100000
@@ -370,21 +371,19 @@ def test_conv_row_partition_is_a_placement_hint_only():
     lib = L.load_library()
     st = lat.m_hash_table._storage
     good = st.row_regions.clone()
+    garbage = T(rng.integers(-10 ** 9, 10 ** 9, 16).astype(np.int32))
     parts = [None, good, torch.zeros(16, dtype=torch.int32, device=dev()), torch.arange(16, 0, -1, dtype=torch.int32, device=dev()) * 9000,
-             T(rng.integers(-10 ** 9, 10 ** 9, 16).astype(np.int32))]
+             garbage, None]  # (the last: no partition, right behind the calls under the garbage one)
     ref = None
     for part in parts:
         out = torch.empty((m, f), dtype=torch.float32, device=dev())
         gv = torch.empty((m, v), dtype=torch.float32, device=dev())
         gw = torch.empty((9 * v, f), dtype=torch.float32, device=dev())
         ws = torch.empty((int(lib.ln_conv_grad_filter_workspace_bytes(m, 9, v, f)) + 4096,), dtype=torch.uint8, device=dev())
-        lib.ln_conv_row_partition(_lib.ptr(part))
-        try:
-            _lib.check(lib.ln_conv_forward(_lib.ptr(nbr), _lib.ptr(values), _lib.ptr(W), m, 9, v, f, 0, _lib.ptr(out), _lib.stream_ptr(dev())))
-            _lib.check(lib.ln_conv_backward(_lib.ptr(nbr), _lib.ptr(nbr), _lib.ptr(values), _lib.ptr(G), _lib.ptr(W), m, m, 9, v, f, _lib.ptr(gv),
-                                            _lib.ptr(gw), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev())))
-        finally:
-            lib.ln_conv_row_partition(None)
+        _lib.check(lib.ln_conv_forward_ws(_lib.ptr(nbr), _lib.ptr(values), _lib.ptr(W), m, 9, v, f, 0, _lib.ptr(out), None, 0, _lib.ptr(part),
+                                          _lib.stream_ptr(dev())))
+        _lib.check(lib.ln_conv_backward(_lib.ptr(nbr), _lib.ptr(nbr), _lib.ptr(values), _lib.ptr(G), _lib.ptr(W), m, m, 9, v, f, _lib.ptr(gv),
+                                        _lib.ptr(gw), _lib.ptr(ws), ws.numel(), _lib.ptr(part), _lib.stream_ptr(dev())))
         torch.cuda.synchronize()
         got = (N(out), N(gv), N(gw))
         if ref is None:
@@ -394,6 +393,9 @@ def test_conv_row_partition_is_a_placement_hint_only():
             assert np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32))
             # (the filter gradient sums one slab per workgroup: the slab ORDER follows the tile map, so it agrees to rounding only)
             np.testing.assert_allclose(got[2], ref[2], rtol=1e-5, atol=1e-5 * float(np.abs(ref[2]).max()))
+    # the last run had no partition, as the reference run: the same tile map, hence the same slab order and the same bits — which a
+    # partition left over from the call before would have changed
+    assert np.array_equal(ref[2].view(np.uint32), got[2].view(np.uint32))
 
 
 def test_slot_order_switch_restores_hashed_slots():

@@ -284,7 +284,7 @@ def test_launch_thread_pinning_follows_the_numa_node_of_the_ranks_gpu(tmp_path, 
 
 
 def test_round6_switches_are_plain_host_state():
-    """Module-level switches of round 6 (no GPU needed to set them): the scans-in-flight hint handed to ln_build_concurrency with every
+    """Module-level switches of round 6 (no GPU needed to set them): the scans-in-flight hint that sets LN_BUILD_OVERLAPPED on every
     build, the slot order and the deterministic mode return the previous setting and reject nonsense."""
     import pytest
     from lattice_net_amd import lattice as LM

@@ -54,7 +54,7 @@ for v, f in ((32, 32), (64, 64), (128, 128)):
         ws = torch.empty((max(wsb, 256),), dtype=torch.uint8, device=dev)
         st = torch.cuda.current_stream().cuda_stream
         def run():
-            _lib.check(lib.ln_conv_forward_ws(_lib.ptr(nb2), _lib.ptr(vals), _lib.ptr(bank), m, 9, v, f, 0, _lib.ptr(out), _lib.ptr(ws), ws.numel(), C.c_void_p(st)), "conv")
+            _lib.check(lib.ln_conv_forward_ws(_lib.ptr(nb2), _lib.ptr(vals), _lib.ptr(bank), m, 9, v, f, 0, _lib.ptr(out), _lib.ptr(ws), ws.numel(), None, C.c_void_p(st)), "conv")
         kk = _profile(lib, run, 20)
         y = torch.empty_like(out); y[perm] = out
         if ref is None: ref = y

@@ -72,7 +72,7 @@ def run(tag, relabel):
     def once():
         _lib.check(lib.ln_conv_forward(_lib.ptr(nbr_l), _lib.ptr(vals_l), _lib.ptr(W), rows_new, 9, v, f, 0, _lib.ptr(out), st))
         _lib.check(lib.ln_conv_backward(_lib.ptr(nbr_l), _lib.ptr(nbr_l), _lib.ptr(vals_l), _lib.ptr(G), _lib.ptr(W), rows_new, rows_new, 9, v, f,
-                                        _lib.ptr(gv), _lib.ptr(gw), _lib.ptr(ws), ws.numel(), st))
+                                        _lib.ptr(gv), _lib.ptr(gw), _lib.ptr(ws), ws.numel(), None, st))
         _lib.check(lib.ln_slice_forward(_lib.ptr(out), _lib.ptr(idx_l), _lib.ptr(w), n, 3, f, _lib.ptr(sl), st))
 
     for _ in range(3):
