@@ -2,10 +2,15 @@
 // with the host compiler under -fsanitize=address,undefined by tests/test_conv_plan.py.  Walks a grid of shapes around every
 // boundary of the dispatch and checks each plan's invariants; prints the size queries (`Q ...` lines) for the test to compare with
 // the library's C ABI (the last three: ln_conv_backward's at mn = m, m / 2 + 1, 2 m).  argv[1]: 1 = bf16x3 path enabled (the library's default), 0 = LN_CONV_EXACT_F32=1.
+// `conv_plan_check plan <b3> mq mn E V F [mq mn E V F ...]`: no grid walk; per shape, what ln_conv_forward_ws (mq rows, V -> F) and
+// ln_conv_backward (two lists) launch with the queried workspace, aligned buffers and no bank left by an earlier call:
+//   PLAN mq mn E V F / FWD <kernel> nt t nsplit cols (one line per launch) / GF <form> vs fs tile / BWD <form> /
+//   VG <kernel> nt t nsplit cols (LN_BWD_TWO_CALLS: the value-gradient convolution over mn rows, F -> V, flipped, transposed bank)
 #include "ln_conv_plan.h"
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 static long g_checked = 0;
 static LnConvPlanIn g_in;
@@ -83,7 +88,42 @@ static LnConvPlan check_plan(const LnConvPlanIn& in) {
     return p;
 }
 
+static void print_launches(const char* tag, const LnConvPlan& p) {
+    static const char* const names[] = {"LN_K_FORWARD_B3", "LN_K_FULL", "LN_K_SPLIT_BANK32", "LN_K_ROWS32", "LN_K_ROWS32SK", "LN_K_SPLIT_BANK",
+                                        "LN_K_MFMA_B3", "LN_K_MFMA", "LN_K_SUM_PARTIALS", "LN_K_GENERIC"};
+    for (int k = 0; k < p.n; ++k)
+        printf("%s %s %d %d %d %d\n", tag, names[p.launch[k].kernel], p.launch[k].nt, p.launch[k].t, p.nsplit, p.launch[k].cols);
+}
+
+static int print_plans(int argc, char** argv) {
+    if (argc < 8 || (argc - 3) % 5 != 0) {
+        printf("usage: conv_plan_check plan <b3> mq mn E V F [mq mn E V F ...]\n");
+        return 2;
+    }
+    const bool b3 = argv[2][0] == '1';
+    static const char* const gf_names[] = {"LN_GF_GENERIC", "LN_GF_B3", "LN_GF_F32"};
+    static const char* const bwd_names[] = {"LN_BWD_FUSED_B3", "LN_BWD_FUSED_F32", "LN_BWD_FULL_SUM", "LN_BWD_TWO_CALLS"};
+    for (int a = 3; a < argc; a += 5) {
+        const int mq = atoi(argv[a]), mn = atoi(argv[a + 1]), E = atoi(argv[a + 2]), V = atoi(argv[a + 3]), F = atoi(argv[a + 4]);
+        if (mq < 1 || mn < 1 || E < 1 || V < 1 || F < 1) return 2;
+        printf("PLAN %d %d %d %d %d\n", mq, mn, E, V, F);
+        print_launches("FWD", check_plan(LnConvPlanIn{mq, E, V, F, false, false, b3, true, true, true, ln_conv_forward_query(mq, E, V, F, b3), false, 0}));
+        const LnGfPlan g = ln_gf_plan(mq, E, V, F, b3);
+        printf("GF %s %d %d %d\n", gf_names[g.form], g.vs, g.fs, g.tile);
+        // ln_conv_backward inside exactly its own query: the filter gradient's slabs in front, the value-gradient convolution's workspace behind
+        const size_t bq = ln_conv_backward_query(mq, mn, E, V, F, b3), gfb = ln_bwd_gf_bytes(mq, E, V, F, b3);
+        const LnBwdPlan bp = ln_conv_backward_plan(LnBwdPlanIn{mq, mn, E, V, F, false, true, bq, true, b3});
+        printf("BWD %s\n", bwd_names[bp.form]);
+        if (bp.form != LN_BWD_TWO_CALLS) continue;
+        const int total = E * V * F;  // the filter gradient's slab sum waits for a bank split to ride in (ln_conv_grad_filter_impl)
+        print_launches("VG", check_plan(LnConvPlanIn{mn, E, F, V, true, true, b3, true, true, bq > gfb, bq > gfb ? bq - gfb : 0, false,
+                                                     g.form != LN_GF_GENERIC && total % 64 == 0 ? total : 0}));
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && strcmp(argv[1], "plan") == 0) return print_plans(argc, argv);
     const bool b3 = argc < 2 || argv[1][0] == '1';
     const int ms[] = {1, 64, 65, 4095, 4096, 4500, 11400, 16384, 16385, 32768, 32769, 46500, 128000, 400000};
     const int es[] = {1, 7, 9, 11, 16, 17, 27};
