@@ -449,6 +449,32 @@ int ln_group_norm_backward_rows(const float* x, const float* grad_y, const float
                                 int channels, int groups, int relu, float* grad_x, float* grad_gamma, float* grad_beta, void* workspace,
                                 size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, const int* rows_device, void* stream);
 
+/* GroupNorm per cloud for a batch of clouds in one table (LnTable.batch_points).  In first-occurrence row order
+ * (LN_BUILD_CANONICAL_ROWS) the vertices of cloud s are the rows [row_starts[s], row_starts[s + 1]) of the value matrix: the points
+ * of a batch are cloud-major and clouds share no vertex.
+ * ln_cloud_row_starts writes row_starts[clouds + 1] (int32; row_starts[clouds] = min(*t->nr_filled, rows_upper, t->row_limit if
+ * set), a cloud without a vertex starts where the next one does) from the first key coordinate of every row, with no host readback,
+ * and *order_flag = 1 when some row's cloud is smaller than its predecessor's (the rows are not cloud-major: row_starts is not
+ * usable), 0 otherwise.  1 <= clouds <= 64 (LN_ERR_UNSUPPORTED); the clouds must keep within half of t->batch_key_step of the origin.
+ * ln_group_norm_forward_segments / _backward_segments: ln_group_norm_forward_rows / _backward_rows over `segments` row ranges of one
+ * matrix, each normalised with the statistics of its own rows: the same blocking of the rows, counted from the start of the range,
+ * the same summation, accumulator slab s for range s.  mean_rstd [segments, 2 * groups], scale_shift [segments, 2 * channels];
+ * grad_gamma / grad_beta are the sums over the ranges, added in fp64 in range order.  The rows that count end at min(m,
+ * row_starts[segments], *rows_device when given); the rows from there to m are written as zeros (y, grad_x).  An empty range writes
+ * nothing (its mean_rstd / scale_shift rows keep their contents) and adds nothing.  Limits and the next_workspace alternation as for
+ * ln_group_norm_forward; 1 <= segments <= 64; workspace = ln_group_norm_segments_workspace_bytes(channels, segments): `segments`
+ * accumulator slabs of ln_group_norm_workspace_bytes(channels), then segments x 2 channels doubles the backward call keeps its
+ * per-range parameter-gradient terms in. */
+int ln_cloud_row_starts(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream);
+size_t ln_group_norm_segments_workspace_bytes(int channels, int segments);
+int ln_group_norm_forward_segments(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps, int relu,
+                                   float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes, void* next_workspace,
+                                   size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream);
+int ln_group_norm_backward_segments(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd, const float* scale_shift,
+                                    int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma, float* grad_beta, void* workspace,
+                                    size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, const int* rows_device,
+                                    const int* row_starts, int segments, void* stream);
+
 /* BatchNorm (+ optional fused ReLU) of BatchNormLatticeModule / BnReluConv (lattice_modules.py:570-583, 988-1009: torch.nn.BatchNorm1d
  * on the [m, channels] values), with the device-side row count of the _rows calls above: n = min(m, *rows_device) rows count (n = m
  * when rows_device is NULL), rows beyond n are written as zeros (y, grad_x) and contribute to nothing.

@@ -159,6 +159,10 @@ SIGNATURES = {
     "ln_group_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ln_group_norm_forward_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_group_norm_backward_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "ln_cloud_row_starts": (_i, [_T, _i, _i, _vp, _vp, _vp]),
+    "ln_group_norm_segments_workspace_bytes": (_sz, [_i, _i]),
+    "ln_group_norm_forward_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
+    "ln_group_norm_backward_segments": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
     "ln_batch_norm_workspace_bytes": (_sz, [_i]),
     "ln_batch_norm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),

@@ -223,7 +223,8 @@ class CapturedNetworkStep:
                 raise ValueError(f"lattice level {k} has {self.levels[k]} vertices, more than its capacity allows as a row bound ({self.bounds[k]})")
         lattice.set_static_rows(bounds[0], coarse_bounds=bounds[1:])
         # this step's own GroupNorm accumulators (never shared with eager launches, never freed while the graph lives)
-        self._gn_entry = new_gn_workspace(lattice._dev())
+        # (sized for the clouds of a batch with per-cloud GroupNorm statistics: the calibration step has built the lattice)
+        self._gn_entry = new_gn_workspace(lattice._dev(), segments=lattice.cloud_segments())
 
         def guarded():
             reset_gn_workspaces()

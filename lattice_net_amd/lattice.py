@@ -144,6 +144,14 @@ def set_hash_capacity_policy(policy: str) -> str:
     return prev
 
 
+def cloud_point_ranges(nr_points: int, points_per_cloud: int, rows_per_point: int = 1):
+    """[0, n0 k, 2 n0 k, ..., nr_points k]: first row of every cloud of a batch in a matrix with k rows per point (and the end)."""
+    if points_per_cloud < 1 or nr_points < 0 or rows_per_point < 1:
+        raise ValueError("points_per_cloud >= 1, nr_points >= 0, rows_per_point >= 1")
+    clouds = -(-nr_points // points_per_cloud)
+    return [min(c * points_per_cloud, nr_points) * rows_per_point for c in range(clouds + 1)]
+
+
 def set_row_order(order: str) -> str:
     """Selects the vertex numbering of subsequent builds ("slot" or "canonical"); returns the previous setting."""
     if order not in ("slot", "canonical"):
@@ -264,6 +272,8 @@ class _TableStorage:
         self.version = 0
         self.nbr_cache = {}
         self.csr_cache = {}
+        self.batch_clouds = 0  # clouds of the batch the last build from positions inserted (Lattice.set_cloud_batch), 0: none
+        self.rows_first_occurrence = False  # that build numbered the rows by first occurrence (row order "canonical")
         self.replay = None  # [rebuild on the atomic path, then the work queued behind the build], see Lattice._build
         self.planes = None  # int32[8] device tensor (7 planes + padding): kd split of key space for the NEXT build that clears, None = no regions
         self.plane_values = None  # the same 7 ints on the host, and the calibrated share of the vertices each of the 8 leaves holds
@@ -310,6 +320,7 @@ class _TableStorage:
         s.version = 0
         s.nbr_cache = {}
         s.csr_cache = {}
+        s.batch_clouds, s.rows_first_occurrence = self.batch_clouds, self.rows_first_occurrence
         s.replay = None
         s.planes = self.planes
         s.plane_values, s.leaf_shares = self.plane_values, self.leaf_shares
@@ -339,6 +350,7 @@ class HashTable:
         self._val_dim_hint = 0
         self._static_rows = None  # capture-safe mode (Lattice.set_static_rows): fixed row bound instead of the host readback
         self._batch = (0, 0)  # (points per cloud, key step) of a batch of independent clouds in this table (Lattice.set_cloud_batch)
+        self._per_cloud_norm = False  # GroupNorm blocks take their statistics per cloud of the batch (set_cloud_batch(per_cloud_norm=True))
 
     def flush(self):
         """Issues a deferred begin_splat clear, if any (every reader of table state goes through this)."""
@@ -587,6 +599,7 @@ class Lattice:
         ht._pos_dim_hint, ht._val_dim_hint = oh.pos_dim(), oh.val_dim()
         ht._static_rows = oh._static_rows
         ht._batch = oh._batch
+        ht._per_cloud_norm = oh._per_cloud_norm
         ht._static_levels = getattr(oh, "_static_levels", None)
         ht.m_nr_filled_is_dirty = oh.m_nr_filled_is_dirty
         ht.m_nr_filled = oh.m_nr_filled
@@ -723,6 +736,8 @@ class Lattice:
                                        cv, cn, self._stream())
                 _lib.check(rc, "ln_distribute")
             st.touch()
+            st.batch_clouds = -(-n // ht._batch[0]) if ht._batch[0] else 0
+            st.rows_first_occurrence = bool(flags & _lib.LN_BUILD_CANONICAL_ROWS)
             st.rows_follow_space = bool(st.slot_map is not None and do_clear and not (flags & (_lib.LN_BUILD_ATOMIC_PATH | _lib.LN_BUILD_CANONICAL_ROWS)))
             ht.m_nr_filled_is_dirty = True
             if n > 0 and ht._static_rows is None:
@@ -1249,6 +1264,7 @@ class Lattice:
         bp, step = self.m_hash_table._batch
         # (a batch of clouds: the key step halves with every coarser level, so that fine key x 2^-1 lands in the same cloud's block)
         ht._batch = (bp, (step // (2 * (d + 1))) * (d + 1)) if bp else (0, 0)
+        ht._per_cloud_norm = self.m_hash_table._per_cloud_norm
         ht._storage = _TableStorage(capacity, d, dev, spare_row_width=self.val_dim())
         # [1, val_dim] zeros: a placeholder until the coarse values exist
         ht.m_values_tensor = ht._storage.fresh_row if ht._storage.fresh_row is not None else torch.zeros((1, self.val_dim()), dtype=torch.float32, device=dev)
@@ -1553,7 +1569,7 @@ class Lattice:
         # coarse_bounds[k]: bound of the lattice k + 1 levels coarser than this one (create_coarse_verts hands them down)
         ht._static_levels = None if coarse_bounds is None else {self.m_lvl + 1 + k: int(b) for k, b in enumerate(coarse_bounds)}
 
-    def set_cloud_batch(self, points_per_cloud: Optional[int], quotient_step: int = 1 << 13):
+    def set_cloud_batch(self, points_per_cloud: Optional[int], quotient_step: int = 1 << 13, per_cloud_norm: bool = False):
         """The multi-cloud launch form for small clouds.  From now on the positions handed to this lattice are a BATCH of independent
         clouds of `points_per_cloud` points each (cloud c = rows c * points_per_cloud ... of the positions tensor; None / 0 switches it
         off).  The lattice of cloud c is translated by c * quotient_step lattice cells along the first coordinate (a translation of the
@@ -1562,8 +1578,17 @@ class Lattice:
         backward, slice, gather, the scatters — runs over the whole batch in one launch with per-cloud results; filter gradients are the
         sum over the clouds.  The clouds must stay within quotient_step / 2 lattice cells of the origin on the first axis (a cell is
         ~0.8 (d + 1) sigma wide... see README 'Key range'; 8192 cells and 64 clouds fit the 2^20 cells of d <= 3).  Coarser levels
-        created from this lattice inherit the batch with the step halved per level.  GroupNorm-style statistics over the lattice values
-        would mix the clouds: this is for the operator path, not for the reference's batch-1 network semantics."""
+        created from this lattice inherit the batch with the step halved per level.
+
+        GroupNorm statistics over all rows of the value matrix would mix the clouds.  `per_cloud_norm=True` (needs
+        set_row_order("canonical"); coarser levels inherit it) makes the GroupNorm of the `Gn*` blocks and of GroupNormLatticeModule
+        take its statistics per cloud: in first-occurrence row order the vertices of cloud c are one contiguous row range
+        (cloud_row_starts()), and the kernels run the same GroupNorm over each range (ln_group_norm_forward_segments), in eager
+        mode and under set_static_rows.  At most 64 clouds.  A network of such blocks then computes, for every cloud, what a run on
+        that cloud alone computes, and parameter gradients that are the sum over the clouds.  Not covered: DistributeLatticeModule
+        and PointNetModule treat row 0 of the TABLE as the reference's "invalid" vertex, which in a batch is the first vertex of
+        cloud 0 only, so the full LNN on a batch still differs from single-cloud runs at those vertices; BatchNorm blocks
+        (statistics over the batch by definition) are unchanged.  With the default False nothing changes."""
         d = self.pos_dim() if self.m_hash_table.is_initialized() else len(self.m_sigmas)
         if not points_per_cloud:
             self.m_hash_table._batch = (0, 0)
@@ -1571,8 +1596,71 @@ class Lattice:
             if int(points_per_cloud) < 1 or int(quotient_step) < 2 or int(quotient_step) % (1 << 4):
                 raise ValueError("points_per_cloud >= 1 and a quotient_step that is a multiple of 16 (halved per coarser level)")
             self.m_hash_table._batch = (int(points_per_cloud), int(quotient_step) * (d + 1))
+        self.m_hash_table._per_cloud_norm = bool(per_cloud_norm) and bool(points_per_cloud)
         if self.m_hash_table.is_initialized():
             self.m_hash_table._storage.touch()
+
+    MAX_BATCH_CLOUDS = 64  # LN_GN_MAX_SEGMENTS of csrc/ln_norm.hip
+
+    def _cloud_batch_size(self) -> int:
+        """Clouds in the batch the last build of this table inserted.  Raises, without device work, where cloud_row_starts() has no
+        meaning: no batch, more than 64 clouds, a level not built from positions, rows not numbered by first occurrence."""
+        ht = self.m_hash_table
+        st = ht._storage
+        if not ht._batch[0]:
+            raise _lib.LatticeNetHipError("cloud_row_starts: no cloud batch is set (Lattice.set_cloud_batch)")
+        if st is None or not st.batch_clouds:
+            raise _lib.LatticeNetHipError("cloud_row_starts: this lattice level was not built from a batch of positions (splat, "
+                                          "distribute, just_create_verts, create_coarse_verts_naive)")
+        if not st.rows_first_occurrence:
+            raise _lib.LatticeNetHipError('cloud_row_starts: the rows of a cloud are one contiguous range only in first-occurrence row '
+                                          'order: call set_row_order("canonical") before the lattice is built')
+        if st.batch_clouds > Lattice.MAX_BATCH_CLOUDS:
+            raise _lib.LatticeNetHipError(f"cloud_row_starts: {st.batch_clouds} clouds in the batch, at most {Lattice.MAX_BATCH_CLOUDS}")
+        return st.batch_clouds
+
+    def _cloud_rows(self) -> torch.Tensor:
+        """int32 [B + 2] on the device: row_starts[0..B], then the order flag; cached with the table structure like the neighbour lists."""
+        clouds = self._cloud_batch_size()
+        ht = self.m_hash_table
+        st = ht._storage
+        rows_upper = self.nr_lattice_vertices()  # (first: an overflowed build is replayed here, which drops the caches)
+        key = ("cloud_rows", st.uid, st.version, clouds)
+        hit = st.nbr_cache.get(key)
+        if hit is not None:
+            return hit[0]
+        out = torch.empty((clouds + 2,), dtype=torch.int32, device=self._dev())
+        t = ht.c_table()
+        _lib.check(_lib.load().ln_cloud_row_starts(C.byref(t), rows_upper, clouds, _lib.ptr(out), out.data_ptr() + 4 * (clouds + 1),
+                                                   self._stream()), "ln_cloud_row_starts")
+        st.nbr_cache[key] = (out,)
+        return out
+
+    def cloud_row_starts(self) -> torch.Tensor:
+        """Device int32 [B + 1] for a batch of B clouds (set_cloud_batch) in first-occurrence row order: the vertices of cloud c are the
+        rows [out[c], out[c + 1]) of this lattice's value matrix, out[B] is the vertex count (a cloud without a vertex starts where the
+        next one does).  Written by a kernel from the device-side count (no host readback: usable under set_static_rows and inside a
+        stream capture) and cached with the table structure."""
+        return self._cloud_rows()[:-1]
+
+    def cloud_row_order_flag(self) -> torch.Tensor:
+        """Device int32 [1] next to cloud_row_starts(): non-zero when some row belongs to an earlier cloud than its predecessor — the rows
+        are not cloud-major (an incremental build into a filled table) and the ranges are not usable."""
+        return self._cloud_rows()[-1:]
+
+    def per_cloud_norm_row_starts(self) -> Optional[torch.Tensor]:
+        """cloud_row_starts() when this lattice holds a batch with per_cloud_norm on, else None: what the GroupNorm blocks pass on."""
+        return self.cloud_row_starts() if self.m_hash_table._per_cloud_norm else None
+
+    def cloud_segments(self) -> int:
+        """Row ranges a GroupNorm call over this lattice's values works on: the clouds of the batch with per_cloud_norm on, else 1."""
+        ht = self.m_hash_table
+        return max(1, ht._storage.batch_clouds) if (ht._per_cloud_norm and ht._storage is not None) else 1
+
+    def cloud_point_starts(self, nr_points: int, rows_per_point: int = 1) -> torch.Tensor:
+        """Row ranges of the clouds in a per-point (rows_per_point = 1) or per-token (pos_dim + 1) matrix of `nr_points` points: cloud c
+        owns the rows [c n0 k, (c + 1) n0 k), the last cloud what is left.  For group_norm_rows(..., row_starts=...)."""
+        return torch.tensor(cloud_point_ranges(nr_points, self.m_hash_table._batch[0], rows_per_point), dtype=torch.int32, device=self._dev())
 
     def set_region_planes(self, planes, leaf_shares=None):
         """kd split planes of key space (7 ints: 1 + 2 + 4 thresholds in heap order, see LnCsr.planes) or None.  With planes, the builds

@@ -61,10 +61,12 @@ _GN_WORKSPACES = {}
 _GN_PRIVATE = [None]  # accumulator pair of the captured step being warmed up / captured (use_gn_workspace)
 
 
-def new_gn_workspace(device, nbytes: int = 0):
-    """A zero-initialised accumulator pair for GroupNorm launches.  `nbytes` 0: large enough for the widest supported layer."""
+def new_gn_workspace(device, nbytes: int = 0, segments: int = 1):
+    """A zero-initialised accumulator pair for GroupNorm launches.  `nbytes` 0: large enough for the widest supported layer, over
+    `segments` row ranges (the clouds of a batch with per-cloud statistics: Lattice.cloud_segments())."""
     if nbytes <= 0:
-        nbytes = int(_lib.load().ln_group_norm_workspace_bytes(1024))
+        lib = _lib.load()
+        nbytes = int(lib.ln_group_norm_workspace_bytes(1024) if segments <= 1 else lib.ln_group_norm_segments_workspace_bytes(1024, segments))
     n = max(nbytes // 8, 1)
     return {"bufs": [torch.zeros((n,), dtype=torch.float64, device=device), torch.zeros((n,), dtype=torch.float64, device=device)],
             "dirty": [0, 0], "cur": 0}
@@ -169,6 +171,53 @@ class GroupNormReluFunction(torch.autograd.Function):
                                                   ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(ctx.rows_dev), stream),
                   "ln_group_norm_backward", x.device, stream)
         return grad_x, grad_w, grad_b, None, None, None, None
+
+
+class GroupNormSegmentsFunction(torch.autograd.Function):
+    """GroupNormReluFunction over row ranges: the rows [row_starts[s], row_starts[s + 1]) of x are normalised with the statistics of
+    that range alone (ln_group_norm_forward_segments / _backward_segments) — the clouds of a batch in one lattice
+    (Lattice.cloud_row_starts()).  `row_starts`: device int32 [B + 1], B <= 64; the rows from row_starts[B] on come out as zeros.  The
+    gradients of weight and bias are the sums over the ranges."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, relu, rows_dev, row_starts):
+        lib = _lib.load()
+        x = x.contiguous()
+        m, c = x.shape
+        segments = int(row_starts.numel()) - 1
+        y = torch.empty_like(x)
+        mean_rstd = torch.empty((segments, 2 * num_groups), dtype=torch.float32, device=x.device)
+        scale_shift = torch.empty((segments, 2 * c), dtype=torch.float32, device=x.device)
+        stream = _lib.stream_ptr(x.device)
+        ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_group_norm_segments_workspace_bytes(c, segments))
+        _gn_check(lib.ln_group_norm_forward_segments(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), m, c, num_groups, float(eps), int(relu),
+                                                     _lib.ptr(y), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), _lib.ptr(ws), ws.numel() * 8,
+                                                     _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev), _lib.ptr(row_starts), segments, stream),
+                  "ln_group_norm_forward_segments", x.device, stream)
+        ctx.rows_dev, ctx.row_starts = rows_dev, row_starts
+        ctx.save_for_backward(x, weight, mean_rstd, scale_shift)
+        ctx.args = (num_groups, bool(relu), bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        lib = _lib.load()
+        x, weight, mean_rstd, scale_shift = ctx.saved_tensors
+        num_groups, relu, has_bias = ctx.args
+        grad_y = grad_y.contiguous()
+        m, c = x.shape
+        segments = int(ctx.row_starts.numel()) - 1
+        grad_x = torch.empty_like(x)
+        grad_w = torch.empty((c,), dtype=torch.float32, device=x.device) if weight is not None else None
+        grad_b = torch.empty((c,), dtype=torch.float32, device=x.device) if has_bias else None
+        stream = _lib.stream_ptr(x.device)
+        ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_group_norm_segments_workspace_bytes(c, segments))
+        _gn_check(lib.ln_group_norm_backward_segments(_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(weight), _lib.ptr(mean_rstd), _lib.ptr(scale_shift),
+                                                      m, c, num_groups, int(relu), _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b),
+                                                      _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(ctx.rows_dev),
+                                                      _lib.ptr(ctx.row_starts), segments, stream),
+                  "ln_group_norm_backward_segments", x.device, stream)
+        return grad_x, grad_w, grad_b, None, None, None, None, None
 
 
 class MaxCentreFunction(torch.autograd.Function):
@@ -280,10 +329,19 @@ def batch_norm_rows(x: torch.Tensor, bn: torch.nn.BatchNorm1d, relu: bool = Fals
     return torch.relu(y) if relu else y
 
 
-def group_norm_rows(x: torch.Tensor, gn: torch.nn.GroupNorm, relu: bool = False, rows_dev=None) -> torch.Tensor:
+def group_norm_rows(x: torch.Tensor, gn: torch.nn.GroupNorm, relu: bool = False, rows_dev=None, row_starts=None) -> torch.Tensor:
     """GroupNorm of an [M, C] matrix with the parameters of `gn` (statistics over rows x group channels).  `rows_dev`: device int
-    holding the number of rows that count (Lattice.rows_device(): static-rows mode, where x is taller than its lattice)."""
-    if x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.shape[1] <= 1024 and x.shape[0] > 0:
+    holding the number of rows that count (Lattice.rows_device(): static-rows mode, where x is taller than its lattice).
+    `row_starts`: device int32 [B + 1], B <= 64 — the statistics are taken per row range [row_starts[s], row_starts[s + 1]) (the
+    clouds of a batch: Lattice.cloud_row_starts(), or cloud_point_starts() for per-point rows); only the HIP kernels do that."""
+    native = x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.shape[1] <= 1024 and x.shape[0] > 0
+    if row_starts is not None:
+        if not native or row_starts.dtype != torch.int32 or row_starts.device != x.device or not row_starts.is_contiguous() or \
+                not 2 <= row_starts.numel() <= 65:
+            raise ValueError("GroupNorm per row range needs the HIP GroupNorm (float32 CUDA rows, channels % 4 == 0, <= 1024 channels) and "
+                             "a contiguous int32 row_starts [B + 1], B <= 64, on the device of the rows")
+        return GroupNormSegmentsFunction.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, relu, rows_dev, row_starts)
+    if native:
         return GroupNormReluFunction.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, relu, rows_dev)
     if rows_dev is not None:
         raise ValueError("static-rows mode needs the HIP GroupNorm (float32 CUDA rows, channels % 4 == 0, <= 1024 channels)")
@@ -299,7 +357,11 @@ class GroupNormLatticeModule(torch.nn.Module):  # mods:585-616: 32 groups, or C/
 
     def forward(self, lattice_values, lattice_py, do_set_values: bool = True, fuse_relu: bool = False):
         _require_2d(lattice_values)
-        lattice_values = group_norm_rows(lattice_values, self.gn, fuse_relu, lattice_py.rows_device() if lattice_py is not None else None)
+        # a batch of clouds with per_cloud_norm: the statistics of every cloud over its own row range (asked of a Lattice only: any
+        # object with the lattice interface of the blocks may stand in for one)
+        starts = getattr(lattice_py, "per_cloud_norm_row_starts", None)
+        lattice_values = group_norm_rows(lattice_values, self.gn, fuse_relu, lattice_py.rows_device() if lattice_py is not None else None,
+                                         starts() if starts is not None else None)
         if do_set_values:
             lattice_py.set_values(lattice_values)
         return lattice_values, lattice_py
