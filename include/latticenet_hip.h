@@ -541,6 +541,15 @@ int ln_weight_norm_backward(const float* v, const float* g, const float* grad_w,
  * columns copied; rows of tokens with idx[t] <= 0 (no vertex, or vertex 0 = the "invalid" bucket) are zero. */
 int ln_distribute_centre(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts, long long tokens,
                          int width, int pos_dim, float* out, void* stream);
+/* The same for a batch of clouds in one table (LnTable.batch_points), where the reference's "invalid" vertex is the first vertex of
+ * EVERY cloud, not row 0 of the table.  row_starts: device int32 [clouds + 1], what ln_cloud_row_starts writes; 1 <= clouds <= 64
+ * (LN_ERR_UNSUPPORTED, nothing launched).  Token t belongs to cloud min(t / tokens_per_cloud, clouds - 1), tokens_per_cloud =
+ * LnTable.batch_points x (lattice pos_dim + 1) >= 1; its row is zero when idx[t] < 0 or idx[t] == row_starts[cloud of t], and gets the
+ * arithmetic of ln_distribute_centre otherwise.  One cloud with row_starts[0] = 0 is ln_distribute_centre.  No host readback, no
+ * allocation: safe inside a stream capture. */
+int ln_distribute_centre_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts, int clouds,
+                                float* out, void* stream);
 
 /* The vertex-side reduction of PointNetModule (lattice_modules.py:688-712: scatter_max, scatter_add of ones, index_select of the
  * winning tokens' barycentric weights, cat, masked_fill(nr_points < 4), keep mask of vertex 0) over the token adjacency `csr`:
@@ -552,6 +561,17 @@ size_t ln_pointnet_reduce_workspace_bytes(int rows, int channels);
 int ln_pointnet_reduce_forward(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
                                const float* bary, int bary_stride, int rows, int min_points, void* workspace, size_t workspace_bytes,
                                float* out, int* out_arg, void* stream);
+/* ln_pointnet_reduce_forward for a batch of clouds in one table: the same segment max, counts, min_points rule and workspace, but the
+ * decode step drops the invalid vertex of every cloud instead of row 0.  row_starts: device int32 [clouds + 1] (ln_cloud_row_starts),
+ * 1 <= clouds <= 64 (LN_ERR_UNSUPPORTED, nothing launched).  Row r is the invalid vertex of cloud c exactly when r == row_starts[c] and
+ * row_starts[c] < row_starts[c + 1]: a cloud without a vertex has none, row_starts[clouds] is none; a dropped row gets out = 0 and
+ * out_arg = -1.  No host readback, no allocation: safe inside a stream capture.
+ * ln_pointnet_reduce_backward serves both: it selects by out_arg[idx[t], c] == t, and out_arg is -1 on every dropped row, so the tokens
+ * of every cloud's invalid vertex get a zero gradient without a row_starts argument.  (It also skips the tokens of row 0 outright: with
+ * row_starts[0] == 0, as ln_cloud_row_starts writes it, row 0 is the invalid vertex of the first cloud that has a vertex.) */
+int ln_pointnet_reduce_forward_clouds(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
+                                      const float* bary, int bary_stride, int rows, int min_points, void* workspace, size_t workspace_bytes,
+                                      float* out, int* out_arg, const int* row_starts, int clouds, void* stream);
 int ln_pointnet_reduce_backward(const float* grad_out, int grad_stride, const int* out_arg, const int* splat_idx, long long tokens,
                                 int channels, float* grad_src, void* stream);
 

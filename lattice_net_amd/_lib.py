@@ -140,8 +140,10 @@ SIGNATURES = {
     "ln_weight_norm_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ln_weight_norm_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ln_distribute_centre": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp]),
+    "ln_distribute_centre_clouds": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _ll, _vp, _i, _vp, _vp]),
     "ln_pointnet_reduce_workspace_bytes": (_sz, [_i, _i]),
     "ln_pointnet_reduce_forward": (_i, [_CSR, _vp, _ll, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "ln_pointnet_reduce_forward_clouds": (_i, [_CSR, _vp, _ll, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp]),
     "ln_pointnet_reduce_backward": (_i, [_vp, _i, _vp, _vp, _ll, _i, _vp, _vp]),
     "ln_linear_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "ln_linear_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -223,8 +223,9 @@ class CapturedNetworkStep:
                 raise ValueError(f"lattice level {k} has {self.levels[k]} vertices, more than its capacity allows as a row bound ({self.bounds[k]})")
         lattice.set_static_rows(bounds[0], coarse_bounds=bounds[1:])
         # this step's own GroupNorm accumulators (never shared with eager launches, never freed while the graph lives)
-        # (sized for the clouds of a batch with per-cloud GroupNorm statistics: the calibration step has built the lattice)
-        self._gn_entry = new_gn_workspace(lattice._dev(), segments=lattice.cloud_segments())
+        # (sized for the clouds of a batch with per-cloud GroupNorm statistics: the calibration step has built the lattices — `lattice`
+        # itself, or the lattice a distribute made of it, which the trace saw)
+        self._gn_entry = new_gn_workspace(lattice._dev(), segments=max(lattice.cloud_segments(), Lattice.traced_cloud_segments()))
 
         def guarded():
             reset_gn_workspaces()

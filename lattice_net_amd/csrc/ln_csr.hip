@@ -868,6 +868,43 @@ __global__ void __launch_bounds__(256)
     out_arg[g] = arg;
 }
 
+// The decode step for a batch of clouds in one table: the dropped "invalid" vertex is the first vertex of EVERY cloud — row r with
+// r == row_starts[c] && row_starts[c] < row_starts[c + 1] for some cloud c (an empty cloud has none, row_starts[clouds] is none) —
+// instead of row 0.  The workgroup copies row_starts into LDS once and marks, from that copy, which of the <= 256 rows its 256
+// elements lie in are such vertices; the elements then test one LDS byte.
+__global__ void __launch_bounds__(256)
+    k_pointnet_reduce_decode_clouds(const unsigned long long* __restrict__ packed, const int* __restrict__ counts, const float* __restrict__ bary,
+                                    int bary_stride, long long work, int channels, int min_points, const int* __restrict__ row_starts,
+                                    int clouds, float* __restrict__ out, int* __restrict__ out_arg) {
+    __shared__ int s_start[LN_CLOUDS_MAX + 1];
+    __shared__ unsigned char s_invalid[256];
+    const long long g0 = (long long)blockIdx.x * 256;
+    const long long row0 = g0 / channels;  // first row of this workgroup; its last one is at most row0 + 255
+    if (threadIdx.x <= clouds) s_start[threadIdx.x] = row_starts[threadIdx.x];
+    s_invalid[threadIdx.x] = 0;
+    __syncthreads();
+    if (threadIdx.x < clouds) {
+        const long long r = s_start[threadIdx.x];
+        if (r < s_start[threadIdx.x + 1] && r >= row0 && r < row0 + 256) s_invalid[r - row0] = 1;
+    }
+    __syncthreads();
+    const long long g = g0 + threadIdx.x;
+    if (g >= work) return;
+    const long long row = g / channels;
+    const int c = int(g - row * channels);
+    const unsigned long long p = packed[g];
+    float mx = 0.f, bw = 0.f;
+    int arg = -1;
+    if (p != 0ull && !s_invalid[row - row0] && counts[row] >= min_points) {
+        mx = ln_ordered_to_float((unsigned int)(p >> 32));
+        arg = int(0xFFFFFFFFu - (unsigned int)(p & 0xFFFFFFFFull));
+        bw = bary[(size_t)arg * bary_stride];
+    }
+    out[row * 2 * channels + c] = mx;
+    out[row * 2 * channels + channels + c] = bw;
+    out_arg[g] = arg;
+}
+
 // gradient of the maxima wrt the per-token rows, token-major (every element written: no zero fill, no scatter):
 //   grad_src[t, c] = grad_out[row, c] if arg[row, c] == t else 0,   row = idx[t]
 // A thread owns VEC consecutive channels of one token (VEC = 4: 16-byte loads of the winners' ids and a 16-byte store).
@@ -910,26 +947,47 @@ extern "C" size_t ln_pointnet_reduce_workspace_bytes(int rows, int channels) {
     return (size_t)rows * channels * sizeof(unsigned long long) + (size_t)rows * sizeof(int) + 256;
 }
 
-extern "C" int ln_pointnet_reduce_forward(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
-                                          const float* bary, int bary_stride, int rows, int min_points, void* workspace,
-                                          size_t workspace_bytes, float* out, int* out_arg, void* stream) {
-    LN_REQUIRE(max_segments >= 0 && channels >= 1 && rows >= 0 && bary_stride >= 1, LN_ERR_ARG, "ln_pointnet_reduce_forward: bad sizes");
+// row_starts == NULL: row 0 is the invalid vertex; else the first vertex of each of the `clouds` row ranges
+static int ln_pointnet_reduce_run(const char* who, const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
+                                  const float* bary, int bary_stride, int rows, int min_points, void* workspace, size_t workspace_bytes,
+                                  const int* row_starts, int clouds, float* out, int* out_arg, hipStream_t st) {
+    LN_REQUIRE(max_segments >= 0 && channels >= 1 && rows >= 0 && bary_stride >= 1, LN_ERR_ARG, "%s: bad sizes", who);
     if (rows == 0) return LN_OK;
     LN_REQUIRE(csr && csr->grp_start && csr->csr_tok && csr->seg_desc && csr->seg_count && src && bary && workspace && out && out_arg,
-               LN_ERR_ARG, "ln_pointnet_reduce_forward: null buffer");
-    LN_REQUIRE(workspace_bytes >= ln_pointnet_reduce_workspace_bytes(rows, channels), LN_ERR_WORKSPACE,
-               "ln_pointnet_reduce_forward: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
+               LN_ERR_ARG, "%s: null buffer", who);
+    LN_REQUIRE(workspace_bytes >= ln_pointnet_reduce_workspace_bytes(rows, channels), LN_ERR_WORKSPACE, "%s: workspace too small", who);
     const long long work = (long long)rows * channels;
     unsigned long long* packed = static_cast<unsigned long long*>(workspace);
     int* counts = reinterpret_cast<int*>(packed + work);
     if (ln_zero_async(workspace, (size_t)work * sizeof(unsigned long long) + (size_t)rows * sizeof(int), st) != LN_OK)
-        return ln_check_launch("ln_pointnet_reduce_forward(memset)");
+        return ln_check_launch(who);
     if (max_segments > 0)
         ln_launch_segment_max(csr, grp_row, max_segments, src, channels, packed, counts, st);
-    LN_LAUNCH("k_pointnet_reduce_decode", k_pointnet_reduce_decode, dim3(ln_div_up(work, 256)), dim3(256), 0, st, packed, counts, bary, bary_stride,
-              work, channels, min_points, out, out_arg);
-    return ln_check_launch("ln_pointnet_reduce_forward");
+    if (row_starts)
+        LN_LAUNCH("k_pointnet_reduce_decode_clouds", k_pointnet_reduce_decode_clouds, dim3(ln_div_up(work, 256)), dim3(256), 0, st, packed, counts,
+                  bary, bary_stride, work, channels, min_points, row_starts, clouds, out, out_arg);
+    else
+        LN_LAUNCH("k_pointnet_reduce_decode", k_pointnet_reduce_decode, dim3(ln_div_up(work, 256)), dim3(256), 0, st, packed, counts, bary,
+                  bary_stride, work, channels, min_points, out, out_arg);
+    return ln_check_launch(who);
+}
+
+extern "C" int ln_pointnet_reduce_forward(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
+                                          const float* bary, int bary_stride, int rows, int min_points, void* workspace,
+                                          size_t workspace_bytes, float* out, int* out_arg, void* stream) {
+    return ln_pointnet_reduce_run("ln_pointnet_reduce_forward", csr, grp_row, max_segments, src, channels, bary, bary_stride, rows, min_points,
+                                  workspace, workspace_bytes, nullptr, 0, out, out_arg, (hipStream_t)stream);
+}
+
+extern "C" int ln_pointnet_reduce_forward_clouds(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
+                                                 const float* bary, int bary_stride, int rows, int min_points, void* workspace,
+                                                 size_t workspace_bytes, float* out, int* out_arg, const int* row_starts, int clouds,
+                                                 void* stream) {
+    LN_REQUIRE(clouds >= 1 && clouds <= LN_CLOUDS_MAX, LN_ERR_UNSUPPORTED, "ln_pointnet_reduce_forward_clouds: 1 <= clouds <= %d (got %d)",
+               LN_CLOUDS_MAX, clouds);
+    LN_REQUIRE(row_starts, LN_ERR_ARG, "ln_pointnet_reduce_forward_clouds: null row_starts");
+    return ln_pointnet_reduce_run("ln_pointnet_reduce_forward_clouds", csr, grp_row, max_segments, src, channels, bary, bary_stride, rows,
+                                  min_points, workspace, workspace_bytes, row_starts, clouds, out, out_arg, (hipStream_t)stream);
 }
 
 extern "C" int ln_pointnet_reduce_backward(const float* grad_out, int grad_stride, const int* arg, const int* splat_idx, long long tokens,

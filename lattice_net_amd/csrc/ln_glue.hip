@@ -153,6 +153,51 @@ extern "C" int ln_distribute_centre(const float* distributed, const int* splat_i
     return ln_check_launch("ln_distribute_centre");
 }
 
+// The same pass for a batch of clouds in one table (LnTable.batch_points): the "invalid" vertex of the reference is the first vertex of
+// EVERY cloud, row_starts[cloud] (ln_cloud_row_starts), not row 0 of the table.  Token t belongs to cloud min(t / tokens_per_cloud,
+// clouds - 1).  row_starts[cloud] is addressed from t alone, so its load is in flight beside idx[t] (a wave reads one or two of the at
+// most 64 ints: one cache line).  IDX: int when every element index fits 31 bits (32-bit divisions), else long long.
+// (Measured and dropped: row_starts in LDS behind a barrier, and cloud / boundary / first rows computed once per workgroup — both slower.)
+template <typename IDX>
+__global__ void __launch_bounds__(256)
+    k_distribute_centre_clouds(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
+                               const int* __restrict__ counts, long long tokens, int width, int pos_dim, long long tokens_per_cloud,
+                               const int* __restrict__ row_starts, int clouds, float* __restrict__ out) {
+    const long long i64 = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i64 >= tokens * width) return;
+    const IDX i = (IDX)i64;
+    const IDX t = i / (IDX)width;
+    const int c = int(i - t * (IDX)width);
+    const IDX cloud = t / (IDX)tokens_per_cloud;
+    const int first = row_starts[cloud < (IDX)(clouds - 1) ? (int)cloud : clouds - 1];
+    const int row = idx[t];
+    float x = 0.f;
+    if (row >= 0 && row != first) {
+        x = d[i64];
+        if (c < pos_dim) x -= sums[(size_t)row * pos_dim + c] / (float)max(counts[row], 1);
+    }
+    out[i64] = x;
+}
+
+extern "C" int ln_distribute_centre_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                           long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts,
+                                           int clouds, float* out, void* stream) {
+    LN_REQUIRE(tokens >= 0 && width >= 1 && pos_dim >= 0 && pos_dim <= width && tokens_per_cloud >= 1, LN_ERR_ARG,
+               "ln_distribute_centre_clouds: bad sizes");
+    LN_REQUIRE(clouds >= 1 && clouds <= LN_CLOUDS_MAX, LN_ERR_UNSUPPORTED, "ln_distribute_centre_clouds: 1 <= clouds <= %d (got %d)",
+               LN_CLOUDS_MAX, clouds);
+    if (tokens == 0) return LN_OK;
+    LN_REQUIRE(distributed && splat_idx && position_sums && counts && row_starts && out, LN_ERR_ARG, "ln_distribute_centre_clouds: null buffer");
+    const dim3 grid(ln_div_up(tokens * width, 256));
+    if (tokens * width <= 0x7fffffffll && tokens_per_cloud <= 0x7fffffffll)
+        LN_LAUNCH("k_distribute_centre_clouds", k_distribute_centre_clouds<int>, grid, dim3(256), 0, (hipStream_t)stream, distributed, splat_idx,
+                  position_sums, counts, tokens, width, pos_dim, tokens_per_cloud, row_starts, clouds, out);
+    else
+        LN_LAUNCH("k_distribute_centre_clouds", k_distribute_centre_clouds<long long>, grid, dim3(256), 0, (hipStream_t)stream, distributed,
+                  splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_cloud, row_starts, clouds, out);
+    return ln_check_launch("ln_distribute_centre_clouds");
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Mean negative log-likelihood of the training loop (ln_train.py:130 torch.nn.NLLLoss(ignore_index=...)) over log-probabilities
 // [n, C] and labels [n]:  loss = -sum_i [y_i != ignore] lp[i, y_i] / max(#{y_i != ignore}, 1).

@@ -351,6 +351,7 @@ class HashTable:
         self._static_rows = None  # capture-safe mode (Lattice.set_static_rows): fixed row bound instead of the host readback
         self._batch = (0, 0)  # (points per cloud, key step) of a batch of independent clouds in this table (Lattice.set_cloud_batch)
         self._per_cloud_norm = False  # GroupNorm blocks take their statistics per cloud of the batch (set_cloud_batch(per_cloud_norm=True))
+        self._per_cloud_invalid_vertex = False  # Distribute / PointNet drop the first vertex of every cloud (set_cloud_batch(per_cloud_invalid_vertex=True))
 
     def flush(self):
         """Issues a deferred begin_splat clear, if any (every reader of table state goes through this)."""
@@ -600,6 +601,7 @@ class Lattice:
         ht._static_rows = oh._static_rows
         ht._batch = oh._batch
         ht._per_cloud_norm = oh._per_cloud_norm
+        ht._per_cloud_invalid_vertex = oh._per_cloud_invalid_vertex
         ht._static_levels = getattr(oh, "_static_levels", None)
         ht.m_nr_filled_is_dirty = oh.m_nr_filled_is_dirty
         ht.m_nr_filled = oh.m_nr_filled
@@ -1265,6 +1267,7 @@ class Lattice:
         # (a batch of clouds: the key step halves with every coarser level, so that fine key x 2^-1 lands in the same cloud's block)
         ht._batch = (bp, (step // (2 * (d + 1))) * (d + 1)) if bp else (0, 0)
         ht._per_cloud_norm = self.m_hash_table._per_cloud_norm
+        ht._per_cloud_invalid_vertex = self.m_hash_table._per_cloud_invalid_vertex
         ht._storage = _TableStorage(capacity, d, dev, spare_row_width=self.val_dim())
         # [1, val_dim] zeros: a placeholder until the coarse values exist
         ht.m_values_tensor = ht._storage.fresh_row if ht._storage.fresh_row is not None else torch.zeros((1, self.val_dim()), dtype=torch.float32, device=dev)
@@ -1504,6 +1507,7 @@ class Lattice:
 
     # calibration of the static-rows mode for a whole network: every build made while a trace is open records (level, vertices)
     _level_trace = None
+    _level_trace_segments = 1  # largest cloud_segments() among the lattices built under the last trace
     # builds issued in static-rows mode while a log is open: (level, row bound, pinned report word) — what a captured step keeps
     # to check its replays (CapturedNetworkStep.check)
     _static_build_log = None
@@ -1526,6 +1530,7 @@ class Lattice:
     @staticmethod
     def start_level_trace():
         Lattice._level_trace = []
+        Lattice._level_trace_segments = 1
 
     @staticmethod
     def stop_level_trace():
@@ -1536,9 +1541,16 @@ class Lattice:
             out[lvl] = max(out.get(lvl, 0), nr)
         return out
 
+    @staticmethod
+    def traced_cloud_segments() -> int:
+        """Largest cloud_segments() among the lattices built since the last start_level_trace().  A network that starts with distribute
+        builds into a NEW lattice object: the one the caller holds never learns how many clouds the batch has."""
+        return Lattice._level_trace_segments
+
     def _trace_level(self):
         if Lattice._level_trace is not None:
             Lattice._level_trace.append((self.m_lvl, self.nr_lattice_vertices()))
+            Lattice._level_trace_segments = max(Lattice._level_trace_segments, self.cloud_segments())
 
     def set_static_rows(self, rows_bound, coarse_bounds=None):
         """Capture-safe mode for hipGraph / torch.cuda.graph capture of a whole step (extension; None switches it off).
@@ -1569,7 +1581,8 @@ class Lattice:
         # coarse_bounds[k]: bound of the lattice k + 1 levels coarser than this one (create_coarse_verts hands them down)
         ht._static_levels = None if coarse_bounds is None else {self.m_lvl + 1 + k: int(b) for k, b in enumerate(coarse_bounds)}
 
-    def set_cloud_batch(self, points_per_cloud: Optional[int], quotient_step: int = 1 << 13, per_cloud_norm: bool = False):
+    def set_cloud_batch(self, points_per_cloud: Optional[int], quotient_step: int = 1 << 13, per_cloud_norm: bool = False,
+                        per_cloud_invalid_vertex: bool = False):
         """The multi-cloud launch form for small clouds.  From now on the positions handed to this lattice are a BATCH of independent
         clouds of `points_per_cloud` points each (cloud c = rows c * points_per_cloud ... of the positions tensor; None / 0 switches it
         off).  The lattice of cloud c is translated by c * quotient_step lattice cells along the first coordinate (a translation of the
@@ -1585,10 +1598,20 @@ class Lattice:
         take its statistics per cloud: in first-occurrence row order the vertices of cloud c are one contiguous row range
         (cloud_row_starts()), and the kernels run the same GroupNorm over each range (ln_group_norm_forward_segments), in eager
         mode and under set_static_rows.  At most 64 clouds.  A network of such blocks then computes, for every cloud, what a run on
-        that cloud alone computes, and parameter gradients that are the sum over the clouds.  Not covered: DistributeLatticeModule
-        and PointNetModule treat row 0 of the TABLE as the reference's "invalid" vertex, which in a batch is the first vertex of
-        cloud 0 only, so the full LNN on a batch still differs from single-cloud runs at those vertices; BatchNorm blocks
-        (statistics over the batch by definition) are unchanged.  With the default False nothing changes."""
+        that cloud alone computes, and parameter gradients that are the sum over the clouds.
+
+        DistributeLatticeModule and PointNetModule treat row 0 of the table as the reference's "invalid" vertex: in canonical row order
+        the first vertex of point 0, whose tokens are zeroed and whose PointNet feature is dropped.  In a batch, row 0 is the first
+        vertex of cloud 0 only.  `per_cloud_invalid_vertex=True` (same conditions as per_cloud_norm: canonical rows, at most 64 clouds,
+        inherited by clones and coarser levels) makes both modules drop the first vertex of EVERY cloud, row cloud_row_starts()[c]
+        (ln_distribute_centre_clouds, ln_pointnet_reduce_forward_clouds), in eager mode, under set_static_rows and inside a capture.
+        With both switches on, models.LNN on a batch computes for every cloud what a run on that cloud alone computes.  Only the fused
+        HIP paths know the rule: where a module cannot take them (non-fp32 input, strided indices, gradients wanted through
+        `distributed`) it raises a ValueError.
+
+        Not covered: coarse levels built from keys (create_coarse_verts: cloud_row_starts() has no ranges for them), slot and space row
+        orders, more than 64 clouds; BatchNorm blocks (statistics over the batch by definition) are unchanged.  With the defaults
+        False nothing changes."""
         d = self.pos_dim() if self.m_hash_table.is_initialized() else len(self.m_sigmas)
         if not points_per_cloud:
             self.m_hash_table._batch = (0, 0)
@@ -1597,6 +1620,7 @@ class Lattice:
                 raise ValueError("points_per_cloud >= 1 and a quotient_step that is a multiple of 16 (halved per coarser level)")
             self.m_hash_table._batch = (int(points_per_cloud), int(quotient_step) * (d + 1))
         self.m_hash_table._per_cloud_norm = bool(per_cloud_norm) and bool(points_per_cloud)
+        self.m_hash_table._per_cloud_invalid_vertex = bool(per_cloud_invalid_vertex) and bool(points_per_cloud)
         if self.m_hash_table.is_initialized():
             self.m_hash_table._storage.touch()
 
@@ -1651,6 +1675,15 @@ class Lattice:
     def per_cloud_norm_row_starts(self) -> Optional[torch.Tensor]:
         """cloud_row_starts() when this lattice holds a batch with per_cloud_norm on, else None: what the GroupNorm blocks pass on."""
         return self.cloud_row_starts() if self.m_hash_table._per_cloud_norm else None
+
+    def points_per_cloud(self) -> int:
+        """Points of one cloud of the batch (set_cloud_batch), 0: no batch."""
+        return self.m_hash_table._batch[0]
+
+    def per_cloud_invalid_row_starts(self) -> Optional[torch.Tensor]:
+        """cloud_row_starts() when this lattice holds a batch with per_cloud_invalid_vertex on, else None: what DistributeLatticeModule
+        and PointNetModule pass on (the "invalid" vertex of cloud c is row out[c] when out[c] < out[c + 1])."""
+        return self.cloud_row_starts() if self.m_hash_table._per_cloud_invalid_vertex else None
 
     def cloud_segments(self) -> int:
         """Row ranges a GroupNorm call over this lattice's values works on: the clouds of the batch with per_cloud_norm on, else 1."""

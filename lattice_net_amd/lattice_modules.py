@@ -240,10 +240,19 @@ def _unit_weights(device, tokens: int) -> torch.Tensor:
     return bufs[-1][:tokens]
 
 
+def _invalid_row_starts(lattice):
+    """Row ranges of the clouds of a batch whose first vertices are the "invalid" vertices (Lattice.per_cloud_invalid_row_starts), or None:
+    row 0 of the table is (asked of a Lattice only: any object with the lattice interface of the modules may stand in for one)."""
+    starts = getattr(lattice, "per_cloud_invalid_row_starts", None)
+    return starts() if starts is not None else None
+
+
 class PointNetReduceFunction(torch.autograd.Function):
     """The vertex side of PointNetModule (lattice_modules.py:688-712): per-vertex max of the token features with the barycentric
-    weight of each winning token appended, vertices with fewer than four tokens and vertex 0 zeroed.  `distributed` [tokens, width]
-    holds the barycentric weight in its last column and takes no gradient (it comes from DistributeLattice)."""
+    weight of each winning token appended, vertices with fewer than four tokens and vertex 0 zeroed — on a batch of clouds with
+    per_cloud_invalid_vertex (Lattice.set_cloud_batch) the first vertex of every cloud instead of vertex 0.  `distributed` [tokens, width]
+    holds the barycentric weight in its last column and takes no gradient (it comes from DistributeLattice).  The backward call is the
+    same either way: it selects by the winners' token ids, which are -1 on every dropped row."""
 
     @staticmethod
     def forward(ctx, x, distributed, lattice, splatting_indices):
@@ -260,9 +269,14 @@ class PointNetReduceFunction(torch.autograd.Function):
         ws = torch.empty((lib.ln_pointnet_reduce_workspace_bytes(m, c),), dtype=torch.uint8, device=dev)
         out = torch.empty((m, 2 * c), dtype=torch.float32, device=dev)
         arg = torch.empty((m, c), dtype=torch.int32, device=dev)
-        _lib.check(lib.ln_pointnet_reduce_forward(C.byref(csr), _lib.ptr(grp_row), max_seg, _lib.ptr(x), c,
-                                                  distributed.data_ptr() + 4 * (width - 1), width, m, 4, _lib.ptr(ws), ws.numel(), _lib.ptr(out),
-                                                  _lib.ptr(arg), _lib.stream_ptr(dev)), "ln_pointnet_reduce_forward")
+        starts = _invalid_row_starts(lattice)
+        args = (C.byref(csr), _lib.ptr(grp_row), max_seg, _lib.ptr(x), c, distributed.data_ptr() + 4 * (width - 1), width, m, 4, _lib.ptr(ws),
+                ws.numel(), _lib.ptr(out), _lib.ptr(arg))
+        if starts is not None:
+            _lib.check(lib.ln_pointnet_reduce_forward_clouds(*args, _lib.ptr(starts), starts.numel() - 1, _lib.stream_ptr(dev)),
+                       "ln_pointnet_reduce_forward_clouds")
+        else:
+            _lib.check(lib.ln_pointnet_reduce_forward(*args, _lib.stream_ptr(dev)), "ln_pointnet_reduce_forward")
         ctx.save_for_backward(arg, splatting_indices)
         ctx.tokens, ctx.channels = tokens, c
         return out
@@ -294,6 +308,7 @@ class DistributeLatticeModule(torch.nn.Module):  # lattice_modules.py:52-96
         distributed_lattice = wrap.lattice
         pos_dim = positions.shape[1]
         nr_rows = distributed_lattice.nr_lattice_vertices()
+        starts = _invalid_row_starts(distributed_lattice)
         if "distribute" in FUSED_GLUE and distributed.is_cuda and distributed.dtype == torch.float32 and distributed.is_contiguous() and \
                 not distributed.requires_grad and splatting_indices.dtype == torch.int32 and splatting_indices.is_contiguous():
             # sums of the positions straight from the token rows, degrees, then ONE pass for mean / subtract / zeroing
@@ -302,10 +317,20 @@ class DistributeLatticeModule(torch.nn.Module):  # lattice_modules.py:52-96
             distributed_lattice._scatter_rows(distributed, splatting_indices, _unit_weights(distributed.device, tokens), sums, pos_dim, 1, width)
             counts = distributed_lattice.vertex_point_counts(splatting_indices)
             centred = torch.empty_like(distributed)
+            if starts is not None:  # a batch of clouds: the first vertex of every cloud is its "invalid" vertex
+                tokens_per_cloud = distributed_lattice.points_per_cloud() * (distributed_lattice.pos_dim() + 1)
+                _lib.check(_lib.load().ln_distribute_centre_clouds(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums),
+                                                                   _lib.ptr(counts), tokens, width, pos_dim, tokens_per_cloud, _lib.ptr(starts),
+                                                                   starts.numel() - 1, _lib.ptr(centred), _lib.stream_ptr(distributed.device)),
+                           "ln_distribute_centre_clouds")
+                return distributed_lattice, centred, splatting_indices, splatting_weights
             _lib.check(_lib.load().ln_distribute_centre(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums), _lib.ptr(counts), tokens,
                                                         width, pos_dim, _lib.ptr(centred), _lib.stream_ptr(distributed.device)),
                        "ln_distribute_centre")
             return distributed_lattice, centred, splatting_indices, splatting_weights
+        if starts is not None:
+            raise ValueError("per_cloud_invalid_vertex (Lattice.set_cloud_batch) needs the fused distribute kernel: \"distribute\" in "
+                             "FUSED_GLUE, float32 CUDA rows that are contiguous and take no gradient, contiguous int32 splat indices")
         distributed_positions = distributed[:, :pos_dim].contiguous()
         sums = torch.zeros((nr_rows, pos_dim), dtype=distributed.dtype, device=distributed.device)
         ones = torch.ones((splatting_indices.numel(),), dtype=distributed.dtype, device=distributed.device)
@@ -359,6 +384,10 @@ class PointNetModule(torch.nn.Module):  # lattice_modules.py:618-733 (the step r
             reduced = self.act(reduced)
             lattice_py.set_values(reduced)
             return reduced, lattice_py
+        if _invalid_row_starts(lattice_py) is not None:
+            raise ValueError("per_cloud_invalid_vertex (Lattice.set_cloud_batch) needs the fused PointNet reduction: \"pointnet\" in "
+                             "FUSED_GLUE, float32 CUDA features, a contiguous float32 `distributed` that takes no gradient, contiguous int32 "
+                             "splat indices")
         reduced, argmax = ScatterMaxLattice.apply(x, lattice_py, indices)               # mods:688
         nr_points = lattice_py.vertex_point_counts(indices).unsqueeze(1)                  # mods:692
         safe = torch.where(argmax >= 0, argmax, torch.zeros_like(argmax)).long()

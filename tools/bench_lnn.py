@@ -39,6 +39,12 @@ lattice_gpu: { hash_table_capacity: 5000000  nr_sigmas: 1  sigma_0: "0.08 3" }
 }
 
 
+def set_clouds(lattice, args):
+    """--clouds B: the scan is a batch of B clouds of n / B points in one lattice, GroupNorm statistics and the "invalid" vertex per cloud."""
+    if args.clouds > 1:
+        lattice.set_cloud_batch(args.n // args.clouds, per_cloud_norm=True, per_cloud_invalid_vertex=True)
+
+
 def make_graph_step(args, preset, cfg_text, net, opt, gen, dev, nll_loss_gather, first=None):
     """K scans per optimizer step, each captured once (forward + NLL + backward = one hipGraph) on its own stream."""
     from lattice_net_amd import CapturedNetworkStep
@@ -55,6 +61,7 @@ def make_graph_step(args, preset, cfg_text, net, opt, gen, dev, nll_loss_gather,
             f.write(cfg_text)
         lat = Lattice.create(f.name, "lattice")
         os.unlink(f.name)
+        set_clouds(lat, args)
         pos = torch.from_numpy(gen(args.n, k)).to(dev)
         vals = torch.zeros((args.n, 1), device=dev) if preset["values"] == 1 else torch.rand((args.n, preset["values"]), device=dev)
         target = torch.from_numpy(np.random.default_rng(k).integers(0, args.classes, args.n)).to(dev)
@@ -154,6 +161,8 @@ def main():
     ap.add_argument("--graph-optimizer", action="store_true", help="with --graph: capture the AdamW step (capturable=True) behind the backward pass")
     ap.add_argument("--in-flight", type=int, default=1, help="with --graph: scans per optimizer step, each with its own lattice, graph and "
                                                              "stream, replayed concurrently; their gradients are summed (batch of K scans)")
+    ap.add_argument("--clouds", type=int, default=1, help="run the network on a batch of B clouds of n / B points in one lattice "
+                                                          "(Lattice.set_cloud_batch with both per-cloud switches; canonical row order; B <= 64)")
     ap.add_argument("--host-profile", action="store_true", help="cProfile of the host side of the timed steps")
     ap.add_argument("--gc", type=int, default=0, help="1 = leave Python's cyclic garbage collector on during the timed steps; 2 = on, after gc.freeze()")
     args = ap.parse_args()
@@ -169,6 +178,12 @@ def main():
     mp = ModelParams.create(path)
     lattice = Lattice.create(path, "lattice")
     os.unlink(path)  # both readers are done with the temporary cfg
+    if args.clouds > 1:
+        if args.n % args.clouds or args.clouds > Lattice.MAX_BATCH_CLOUDS:
+            raise SystemExit(f"--clouds must divide --n ({args.n}) and be at most {Lattice.MAX_BATCH_CLOUDS}")
+        from lattice_net_amd.lattice import set_row_order
+        set_row_order("canonical")  # the rows of a cloud are one range only in first-occurrence order
+        set_clouds(lattice, args)
     path_cfg = preset["cfg"]
     net = LNN(args.classes, mp)
     gen = {"lidar": synthetic.lidar_cloud, "box": synthetic.box_surface_cloud, "planes": synthetic.planes_cloud}[preset["cloud"]]
