@@ -47,16 +47,18 @@ def _ordered(x):
     return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
 
 
-def pointnet_reduce(src, idx, bary, rows, min_points, row_starts=None):
+def pointnet_reduce(src, idx, bary, rows, min_points, row_starts=None, bary_stride=1):
     """(out [rows, 2C] float32, arg [rows, C] int32, counts [rows]): per row the maximum over its tokens of src[t, c] (equal values: the
-    smallest token) and the barycentric weight of the winning token; rows with fewer than min_points tokens and invalid rows (row 0 when
-    row_starts is None) are zero with arg = -1, and so are rows without a token."""
+    smallest token) and the barycentric weight bary[t * bary_stride] of the winning token t; rows with fewer than min_points tokens and
+    invalid rows (row 0 when row_starts is None) are zero with arg = -1, and so are rows without a token.  Tokens with idx outside
+    [0, rows) belong to no row."""
     src = np.asarray(src, dtype=np.float32)
     src = np.where(src == 0, np.float32(0), src)  # -0 and +0 are one value to the maximum: it is written as +0, ties go to the smallest token
     idx = np.asarray(idx, dtype=np.int64)
-    bary = np.asarray(bary, dtype=np.float32)
+    bary = np.asarray(bary, dtype=np.float32).reshape(-1)
     tokens, ch = src.shape
-    counts = np.bincount(idx[idx >= 0], minlength=rows)[:rows]
+    tok = np.flatnonzero((idx >= 0) & (idx < rows))
+    counts = np.bincount(idx[tok], minlength=rows)
     if row_starts is None:
         invalid = np.arange(rows) == 0
     else:
@@ -64,7 +66,6 @@ def pointnet_reduce(src, idx, bary, rows, min_points, row_starts=None):
     keep = (counts >= min_points) & ~invalid & (counts > 0)
     out = np.zeros((rows, 2 * ch), dtype=np.float32)
     arg = np.full((rows, ch), -1, dtype=np.int32)
-    tok = np.flatnonzero(idx >= 0)
     row_of = idx[tok]
     for c in range(ch):
         key = _ordered(src[tok, c]).astype(np.int64)
@@ -75,15 +76,20 @@ def pointnet_reduce(src, idx, bary, rows, min_points, row_starts=None):
         ok = keep[win_row]
         arg[win_row[ok], c] = win_tok[ok]
         out[win_row[ok], c] = src[win_tok[ok], c]
-        out[win_row[ok], ch + c] = bary[win_tok[ok]]
+        out[win_row[ok], ch + c] = bary[win_tok[ok] * bary_stride]
     return out, arg, counts
 
 
-def pointnet_reduce_backward(grad_out, arg, idx, tokens):
-    """grad_src[t, c] = grad_out[idx[t], c] if arg[idx[t], c] == t else 0 (grad_out [rows, >= C]: the first C columns are the maxima's)."""
+def pointnet_reduce_backward(grad_out, arg, idx, tokens, grad_stride=None):
+    """grad_src[t, c] = grad_out[idx[t], c] if arg[idx[t], c] == t else 0 (grad_out [rows, >= C]: the first C columns are the maxima's;
+    with grad_stride, grad_out is flat and row r starts at r * grad_stride)."""
     grad_out = np.asarray(grad_out, dtype=np.float32)
     idx = np.asarray(idx, dtype=np.int64)
     ch = arg.shape[1]
+    if grad_stride is not None:
+        flat = np.ascontiguousarray(grad_out).reshape(-1)
+        assert flat.size >= (arg.shape[0] - 1) * grad_stride + ch
+        grad_out = np.lib.stride_tricks.as_strided(flat, (arg.shape[0], ch), (4 * grad_stride, 4))
     g = np.zeros((tokens, ch), dtype=np.float32)
     t = np.flatnonzero(idx >= 0)
     won = arg[idx[t]] == t[:, None]
