@@ -4,8 +4,8 @@
 // the library's C ABI (the last three: ln_conv_backward's at mn = m, m / 2 + 1, 2 m).  argv[1]: 1 = bf16x3 path enabled (the library's default), 0 = LN_CONV_EXACT_F32=1.
 // `conv_plan_check plan <b3> mq mn E V F [mq mn E V F ...]`: no grid walk; per shape, what ln_conv_forward_ws (mq rows, V -> F) and
 // ln_conv_backward (two lists) launch with the queried workspace, aligned buffers and no bank left by an earlier call:
-//   PLAN mq mn E V F / FWD <kernel> nt t nsplit cols (one line per launch) / GF <form> vs fs tile / BWD <form> /
-//   VG <kernel> nt t nsplit cols (LN_BWD_TWO_CALLS: the value-gradient convolution over mn rows, F -> V, flipped, transposed bank)
+//   PLAN mq mn E V F / FWD <kernel> nt t nsplit cols e_per (one line per launch) / GF <form> vs fs tile / BWD <form> /
+//   VG <kernel> nt t nsplit cols e_per (LN_BWD_TWO_CALLS: the value-gradient convolution over mn rows, F -> V, flipped, transposed bank)
 #include "ln_conv_plan.h"
 
 #include <stdio.h>
@@ -92,7 +92,7 @@ static void print_launches(const char* tag, const LnConvPlan& p) {
     static const char* const names[] = {"LN_K_FORWARD_B3", "LN_K_FULL", "LN_K_SPLIT_BANK32", "LN_K_ROWS32", "LN_K_ROWS32SK", "LN_K_SPLIT_BANK",
                                         "LN_K_MFMA_B3", "LN_K_MFMA", "LN_K_SUM_PARTIALS", "LN_K_GENERIC"};
     for (int k = 0; k < p.n; ++k)
-        printf("%s %s %d %d %d %d\n", tag, names[p.launch[k].kernel], p.launch[k].nt, p.launch[k].t, p.nsplit, p.launch[k].cols);
+        printf("%s %s %d %d %d %d %d\n", tag, names[p.launch[k].kernel], p.launch[k].nt, p.launch[k].t, p.nsplit, p.launch[k].cols, p.e_per);
 }
 
 static int print_plans(int argc, char** argv) {

@@ -1,7 +1,7 @@
 """fp64 references and per-element bounds for the lattice convolution between TWO lattices (csrc/ln_conv.hip, csrc/ln_conv_f16.hip:
 coarsen and finefy, where the mq query rows and the mn gathered rows belong to different lattices).  Plain NumPy on the CPU, in the
 vocabulary of dense_reference.py: test_conv_reference.py checks this module without a GPU, test_gpu_conv_two_lattices.py holds the
-kernels to it.
+kernels to it at the filter extent E = 9, test_gpu_conv_filter_extents.py at E = 1, 5, 7, 11, 13, 15, 17 (every function here takes any E >= 1).
 
 The three products of one convolution out = conv(nbr_q, vals, W), vals [mn, V], W [E V, F], G = d loss / d out [mq, F]:
     forward      out[m, f]      = sum_e sum_v vals[nbr_q[m, e], v] W[e V + v, f]                      (mq rows)
@@ -30,17 +30,17 @@ def flip_slots(E):
 
 
 def _one_list(rows, into, E, rng, lo):
-    """[rows, E] int32, ids in [lo, into) or -1, drawn independently; planted by construction: row rows - 1 wholly absent (in the partial
-    last tile), rows 0 and rows - 2 without an absent neighbour, the id `lo` and the largest id into - 1, and the largest id HOT_ROWS
-    times in a row of slot 1 (across a 64-row tile boundary)."""
-    assert rows >= HOT_ROWS + 8 and into >= lo + 2 and E >= 2
+    """[rows, E] int32, ids in [lo, into) or -1, drawn independently; planted by construction at every extent E >= 1: row rows - 1
+    wholly absent (in the partial last tile), rows 0 and rows - 2 without an absent neighbour, the id `lo` and the largest id into - 1,
+    and the largest id HOT_ROWS times in a row of slot 1 (across a 64-row tile boundary; slot 0 at E = 1, where it is the only one)."""
+    assert rows >= HOT_ROWS + 8 and into >= lo + 2 and E >= 1
     n = rng.integers(lo - 1, into, (rows, E)).astype(np.int32)
     n[n == lo - 1] = -1
     for r in (0, rows - 2):
         n[r] = rng.integers(lo, into, E)
     n[1, 0] = lo
     n[2, E - 1] = into - 1
-    n[3:3 + HOT_ROWS, 1] = into - 1
+    n[3:3 + HOT_ROWS, min(1, E - 1)] = into - 1
     n[rows - 1] = -1
     return n
 
@@ -51,6 +51,26 @@ def two_lattice_lists(mq, mn, E, rng, row0_unreferenced=False):
     in neither list (the smallest id is 1), for the run that poisons row 0 of the gathered operand."""
     lo = 1 if row0_unreferenced else 0
     return _one_list(mq, mn, E, rng, lo), _one_list(mn, mq, E, rng, lo)
+
+
+def _one_permutation(rows, into, rng, lo):
+    """[rows, 1] int32: every id of [lo, into) at most once, the other rows absent (about one in eight, and all that the ids do not
+    reach); rows 0 and rows - 2 present, the ids `lo` and into - 1 named, row rows - 1 absent."""
+    assert rows >= 8 and into >= lo + 4
+    n = np.full((rows, 1), -1, np.int32)
+    at = rng.permutation(rows - 3) + 1                     # rows 1 .. rows - 3 in random order; rows 0 and rows - 2 taken below
+    ids = rng.permutation(np.arange(lo + 1, into - 1))     # the ids between the two ends
+    k = min(at.size - at.size // 8, ids.size)
+    n[at[:k], 0] = ids[:k]
+    n[0, 0], n[rows - 2, 0] = lo, into - 1
+    return n
+
+
+def permutation_lists(mq, mn, rng, row0_unreferenced=False):
+    """The E = 1 pair: one-column lists that are NOT the identity (the per-row linear layers pass the identity, the kernels trust
+    whatever ids they are given): an injective map with absent entries in each direction, drawn independently."""
+    lo = 1 if row0_unreferenced else 0
+    return _one_permutation(mq, mn, rng, lo), _one_permutation(mn, mq, rng, lo)
 
 
 def list_properties(nbr, into):

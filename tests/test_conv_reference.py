@@ -198,3 +198,63 @@ def test_exact_family_conditions():
     vals, W, G = C.operands("random", MQ, MN, E, V, F, rng, half=True)
     for x in (vals, W, G):
         assert np.array_equal(x, x.astype(np.float16).astype(np.float32))
+
+
+@pytest.mark.parametrize("extent", [1, 5, 7, 11, 13, 15, 17])
+@pytest.mark.parametrize("unreferenced", [False, True])
+def test_lists_hold_every_planted_case_at_every_extent(extent, unreferenced):
+    """What the lists plant at E = 9 they plant at every extent from 1 on (at E = 1 the repeats of one id sit in slot 0, the only one)"""
+    for mq, mn in ((MQ, MN), (MN, MQ), (4500, 1300)):
+        nbr_q, nbr_n = C.two_lattice_lists(mq, mn, extent, np.random.default_rng(mq + extent), unreferenced)
+        assert nbr_q.shape == (mq, extent) and nbr_n.shape == (mn, extent) and nbr_q.dtype == nbr_n.dtype == np.int32
+        for nbr, into in ((nbr_q, mn), (nbr_n, mq)):
+            p = C.list_properties(nbr, into)
+            assert p["in_range"] and p["all_absent_rows"] >= 1 and p["full_rows"] >= 2 and p["has_largest"] and p["hot"] >= C.HOT_ROWS, p
+            assert p["has_zero"] == (not unreferenced), p
+            assert int(nbr.min()) == -1 and int(nbr[nbr >= 0].min()) == (1 if unreferenced else 0), "the smallest id is named"
+            assert bool(np.all(nbr[-1] == -1)), "the wholly absent row sits in the partial last tile"
+            assert bool(np.all(nbr[0] >= 0)) and bool(np.all(nbr[-2] >= 0)), "rows 0 and rows - 2 are whole"
+            hot = nbr[3:3 + C.HOT_ROWS, min(1, extent - 1)]
+            assert bool(np.all(hot == into - 1)) and 3 < 64 < 3 + C.HOT_ROWS, "the repeats cross a 64-row tile boundary"
+            assert not np.array_equal(nbr[:, extent - 1], np.minimum(np.arange(nbr.shape[0]), into - 1)), "no identity slot"
+
+
+@pytest.mark.parametrize("unreferenced", [False, True])
+def test_permutation_lists_are_injective_with_absent_entries(unreferenced):
+    for mq, mn in ((MQ, MN), (4500, 1300), (1300, 4500)):
+        nbr_q, nbr_n = C.permutation_lists(mq, mn, np.random.default_rng(mq), unreferenced)
+        for nbr, into in ((nbr_q, mn), (nbr_n, mq)):
+            assert nbr.shape[1] == 1 and nbr.dtype == np.int32
+            ids = nbr[nbr >= 0]
+            p = C.list_properties(nbr, into)
+            assert p["in_range"] and p["hot"] == 1 and ids.size == np.unique(ids).size, "every id at most once"
+            assert p["has_largest"] and p["has_zero"] == (not unreferenced) and int(ids.min()) == (1 if unreferenced else 0)
+            assert nbr[-1, 0] == -1 and nbr[0, 0] >= 0 and nbr[-2, 0] >= 0 and int(np.sum(nbr < 0)) >= nbr.shape[0] // 10
+            assert ids.size >= min(nbr.shape[0], into) // 2
+            assert not np.array_equal(nbr[:, 0], np.arange(nbr.shape[0])), "not the identity"
+
+
+def test_the_flip_is_the_identity_at_an_extent_of_one():
+    assert C.flip_slots(1) == [0]
+    assert C.flip_slots(5) == [1, 0, 3, 2, 4] and C.flip_slots(9) == [1, 0, 3, 2, 5, 4, 7, 6, 8]
+    rng = np.random.default_rng(11)
+    for lists in (C.two_lattice_lists, lambda mq, mn, e, r: C.permutation_lists(mq, mn, r)):
+        nbr_q, nbr_n = lists(MQ, MN, 1, rng)
+        vals, W, G = C.operands("random", MQ, MN, 1, V, F, rng)
+        for transposed, x, nbr, bank in ((False, vals, nbr_q, W), (True, G, nbr_n, W)):
+            plain, flipped = C.forward(nbr, x, bank, flip=False, transposed=transposed), C.forward(nbr, x, bank, flip=True, transposed=transposed)
+            assert np.array_equal(plain[0], flipped[0]) and np.array_equal(plain[1], flipped[1])
+    # ... and nowhere else: at E = 5 the flipped forward differs
+    nbr_q, _ = C.two_lattice_lists(MQ, MN, 5, rng)
+    vals, W, _ = C.operands("random", MQ, MN, 5, V, F, rng)
+    assert not np.array_equal(C.forward(nbr_q, vals, W, flip=True)[0], C.forward(nbr_q, vals, W)[0])
+
+
+@pytest.mark.parametrize("extent", [1, 7, 17])
+def test_references_agree_with_autograd_at_other_extents(extent):
+    rng = np.random.default_rng(extent)
+    nbr_q, nbr_n = C.two_lattice_lists(MQ, MN, extent, rng)
+    vals, W, G = C.operands("random", MQ, MN, extent, V, F, rng)
+    refs = (C.forward(nbr_q, vals, W), C.grad_filter(nbr_q, vals, G), C.grad_values(nbr_n, G, W))
+    for name, g, (ref, bound) in zip(("forward", "grad_filter", "grad_values"), _autograd_products(nbr_q, nbr_n, vals, W, G), refs):
+        assert C.within(g, ref, bound, 1e-13, name) <= 1.0

@@ -72,31 +72,32 @@ def _intact(ws, q, what):
     assert bool((ws[q:] == SENTINEL).all()), f"{what}: bytes behind the workspace were written"
 
 
-def _forward(lib, d_nbr, d_vals, d_W, rows, v, f, flags=0):
-    """launches ln_conv_forward_ws inside exactly its queried workspace; (out, check to run after the synchronize)"""
-    q = lib.ln_conv_forward_workspace_bytes(rows, E, v, f)
+def _forward(lib, d_nbr, d_vals, d_W, rows, v, f, flags=0, e=E):
+    """launches ln_conv_forward_ws inside exactly its queried workspace; (out, check to run after the synchronize).  `e`: the filter
+    extent (tests/test_gpu_conv_filter_extents.py shares these helpers)"""
+    q = lib.ln_conv_forward_workspace_bytes(rows, e, v, f)
     ws, out = _workspace(q), _nan(rows, f)
-    rc = lib.ln_conv_forward_ws(_lib.ptr(d_nbr), _lib.ptr(d_vals), _lib.ptr(d_W), rows, E, v, f, flags, _lib.ptr(out), _lib.ptr(ws), q, None, None)
+    rc = lib.ln_conv_forward_ws(_lib.ptr(d_nbr), _lib.ptr(d_vals), _lib.ptr(d_W), rows, e, v, f, flags, _lib.ptr(out), _lib.ptr(ws), q, None, None)
     assert rc == 0, lib.ln_last_error_string()
     return out, lambda: _intact(ws, q, "ln_conv_forward_ws")
 
 
-def _backward(lib, d_q, d_n, d_vals, d_G, d_W, mq, mn, v, f):
-    q = lib.ln_conv_backward_workspace_bytes(mq, mn, E, v, f)
-    ws, gv, gw = _workspace(q), _nan(mn, v), _nan(E * v, f)
-    rc = lib.ln_conv_backward(_lib.ptr(d_q), _lib.ptr(d_n), _lib.ptr(d_vals), _lib.ptr(d_G), _lib.ptr(d_W), mq, mn, E, v, f, _lib.ptr(gv), _lib.ptr(gw),
+def _backward(lib, d_q, d_n, d_vals, d_G, d_W, mq, mn, v, f, e=E):
+    q = lib.ln_conv_backward_workspace_bytes(mq, mn, e, v, f)
+    ws, gv, gw = _workspace(q), _nan(mn, v), _nan(e * v, f)
+    rc = lib.ln_conv_backward(_lib.ptr(d_q), _lib.ptr(d_n), _lib.ptr(d_vals), _lib.ptr(d_G), _lib.ptr(d_W), mq, mn, e, v, f, _lib.ptr(gv), _lib.ptr(gw),
                               _lib.ptr(ws), q, None, None)
     assert rc == 0, lib.ln_last_error_string()
     return gw, gv, lambda: _intact(ws, q, "ln_conv_backward")
 
 
-def _three_products_f32(nbr_q, nbr_n, vals, W, G, shape):
+def _three_products_f32(nbr_q, nbr_n, vals, W, G, shape, e=E):
     """(out, gW, gv) of the library as NumPy arrays"""
     mq, mn, v, f = shape
     lib = _lib.load()
     d_q, d_n, d_vals, d_W, d_G = _dev(nbr_q), _dev(nbr_n), _dev(vals), _dev(W), _dev(G)
-    out, ok_f = _forward(lib, d_q, d_vals, d_W, mq, v, f)
-    gw, gv, ok_b = _backward(lib, d_q, d_n, d_vals, d_G, d_W, mq, mn, v, f)
+    out, ok_f = _forward(lib, d_q, d_vals, d_W, mq, v, f, e=e)
+    gw, gv, ok_b = _backward(lib, d_q, d_n, d_vals, d_G, d_W, mq, mn, v, f, e=e)
     torch.cuda.synchronize()
     ok_f(), ok_b()
     return out.cpu().numpy(), gw.cpu().numpy(), gv.cpu().numpy()
