@@ -528,7 +528,8 @@ int ln_linear_backward(const int* ident, const float* x, const float* grad_y, co
 /* ---- launch diet of the glue around the lattice operators in a training step ----------------------------------------------
  * Weight normalisation of the reference's weight_norm_wrapper with v_dim=None (latticenet_py/lattice/utils.py:72-158; LinearWN,
  * ConvLatticeIm2RowWN, CoarsenLatticeWN, FinefyLatticeWN):  w = v * g / ||v||_F  for v [rows, cols] and one magnitude per row
- * (g_dim 0, g [rows]) or per column (g_dim 1, g [cols]); at most 1024 magnitudes, rows * cols <= 2^24.  One workgroup each way,
+ * (g_dim 0, g [rows]) or per column (g_dim 1, g [cols]); at most 1024 magnitudes, rows * cols <= 2^24 (LN_ERR_UNSUPPORTED);
+ * rows, cols >= 1, g_dim 0 or 1, no null buffer (LN_ERR_ARG); a rejected call launches nothing.  One workgroup each way,
  * sums in a fixed order.  `norm`: one float written by the forward call and read by the backward call.
  *   grad_g[j] = sum_k grad_w[j,k] v[j,k] / n      grad_v = grad_w * g / n - v * (sum_j g[j] sum_k grad_w[j,k] v[j,k]) / n^3 */
 int ln_weight_norm_forward(const float* v, const float* g, int rows, int cols, int g_dim, float* w, float* norm, void* stream);
@@ -579,7 +580,9 @@ int ln_pointnet_reduce_backward(const float* grad_out, int grad_stride, const in
  * float, target [n] int64; ignore_index: a label value that is skipped (pass a value no label takes, e.g. LLONG_MIN, for none).
  * loss_count [2]: {loss = -sum lp[i, y_i] / max(count, 1), max(count, 1)} (count = labels not ignored); labels outside
  * [0, classes) are clamped, as in the gather formulation it replaces.  Backward writes every element of grad_log_probs [n, classes]:
- * -grad_loss / count at (i, y_i) of the labels that count, 0 elsewhere.  Sums in a fixed order (deterministic). */
+ * -grad_loss / count at (i, y_i) of the labels that count, 0 elsewhere.  Sums in a fixed order (deterministic).
+ * n >= 0 (n == 0: loss 0, count 1; the backward writes nothing), classes >= 1, no null buffer, a workspace of at least
+ * ln_nll_workspace_bytes() (all LN_ERR_ARG); a rejected call launches nothing. */
 size_t ln_nll_workspace_bytes(void);
 int ln_nll_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index, void* workspace,
                    size_t workspace_bytes, float* loss_count, void* stream);

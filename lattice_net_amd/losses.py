@@ -96,8 +96,9 @@ def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=
     picked = log_probs.gather(1, target.clamp(0, log_probs.shape[1] - 1).unsqueeze(1)).squeeze(1)
     if ignore_index is None:
         return -picked.mean()
-    keep = (target != ignore_index).to(picked.dtype)
-    return -(picked * keep).sum() / keep.sum().clamp(min=1)
+    keep = target != ignore_index
+    # (selected, not multiplied by a 0 / 1 mask: the kernels never read an ignored row, so a -inf or NaN there must not reach the loss)
+    return -torch.where(keep, picked, torch.zeros_like(picked)).sum() / keep.sum().clamp(min=1).to(picked.dtype)
 
 
 class GeneralizedSoftDiceLoss(torch.nn.Module):
