@@ -358,6 +358,60 @@ __device__ __forceinline__ void ln_reduce_entries(float (&acc)[VEC], int beg, in
     }
 }
 
+// The same batches for the CHAIN instances: source rows of LN_CHAIN_ROW_BYTES (32 floats, or 64 halfs) shared by LN_CHAIN_DIV tokens
+// (the d + 1 = 4 tokens of a point), a lane's chunk = 16 bytes at cbyte = 16 * lane.  Row divisor and row width are constants, and the
+// host has checked (ln_chain_fits) that every id list, weight and source row lies within 4 GB of its base: the three addresses
+// are a uniform base plus an unsigned 32-bit byte offset — (t >> 2) << 7 | cbyte for the row — with no 64-bit multiply or add per token.
+#define LN_CHAIN_DIV 4
+#define LN_CHAIN_ROW_BYTES 128
+template <int VEC, bool HALF, bool SAFE>
+__device__ __forceinline__ void ln_reduce_entries_chain(float (&acc)[VEC], int beg, int end, unsigned cbyte, const int* __restrict__ csr_tok,
+                                                        const float* __restrict__ w, const void* src_v) {
+    static_assert(VEC * (HALF ? 2 : 4) == 16 && LN_CHAIN_DIV == 4 && LN_CHAIN_ROW_BYTES == 128, "16-byte chunks of 128-byte rows");
+    const char* __restrict__ tok_b = reinterpret_cast<const char*>(csr_tok);
+    const char* __restrict__ w_b = reinterpret_cast<const char*>(w);
+    const char* __restrict__ src_b = static_cast<const char*>(src_v);
+    constexpr int U = 4;
+    const unsigned last_b = (unsigned)(end - 1) << 2;
+    for (int e0 = beg; e0 < end; e0 += U) {
+        const unsigned e_b = (unsigned)e0 << 2;
+        int tk[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ok[u] = e_b + 4u * u <= last_b;
+            tk[u] = *reinterpret_cast<const int*>(tok_b + min(e_b + 4u * u, last_b));
+        }
+        float wt[U];
+        float x[U][VEC];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const bool valid = ok[u] && tk[u] >= 0;
+            const unsigned t = (unsigned)max(tk[u], 0);
+            const float wl = *reinterpret_cast<const float*>(w_b + (t << 2));
+            wt[u] = valid ? wl : 0.f;
+            const unsigned off = ((t >> 2) << 7) | cbyte;
+            if constexpr (HALF) {
+                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+                const h8 v8 = *reinterpret_cast<const h8*>(src_b + off);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) x[u][k] = (float)v8[k];
+            } else {
+                const float4 v4 = *reinterpret_cast<const float4*>(src_b + off);
+                x[u][0] = v4.x; x[u][1] = v4.y; x[u][2] = v4.z; x[u][3] = v4.w;
+            }
+            if constexpr (SAFE) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) x[u][k] = valid ? x[u][k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) acc[k] = fmaf(x[u][k], wt[u], acc[k]);
+    }
+}
+
 // one block of segments (256 threads).  Per segment: descriptor -> row -> batches of 4 tokens {4 ids} -> {4 weights, 4 row chunks}.
 // Measured on MI355X (C3, 17.5 us): the kernel is insensitive to the length of this dependency chain — prefetching the next
 // batch's ids with the current gathers (6 trips instead of 10): 18.4 us; all 16 ids + 8 gathers in flight (4 trips, 128
@@ -367,10 +421,15 @@ __device__ __forceinline__ void ln_reduce_entries(float (&acc)[VEC], int beg, in
 // registers, which cost the sparse C3 scan 10 % — hence a variant of its own, chosen by the host)
 // L8 = 8: eight lanes per segment and eight chunks per row as COMPILE-TIME constants (32 fp32 channels on float4 lanes: the headline chain) —
 // the lane / group arithmetic becomes shifts, the chunk loop and the shuffle rounds unroll; 0: both from the arguments.
-template <int VEC, bool HALF, bool WG, int L8 = 0>
-__device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const LnReduceArgs& a) {
+// CHAIN (with L8 = 8): also the token divisor and the row width of the chain as constants and 32-bit offsets from uniform bases
+// (ln_reduce_entries_chain); `so.sid` counts from the region's first descriptor `seg_desc` (below 2^23); deterministic mode is the
+// template flag DET and `direct_rows` (the descriptor names the row) is read once per workgroup; the combine asks one ballot per wave
+// whether any two neighbouring lane groups hold the same row, and skips the rounds no lane needs.
+template <int VEC, bool HALF, bool WG, int L8 = 0, bool CHAIN = false, bool DET = false>
+__device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const LnReduceArgs& a, const int4* __restrict__ seg_desc,
+                                                bool direct_rows) {
+    static_assert(!CHAIN || L8 == 8, "the chain instances are eight lanes x eight chunks");
     const int* __restrict__ csr_tok = a.csr_tok;
-    const int4* __restrict__ seg_desc = a.seg_desc;
     const int* __restrict__ grp_row = a.grp_row;
     const float* __restrict__ w = a.w;
     float* __restrict__ dst = a.dst;
@@ -380,16 +439,17 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
     const int grp_in_wave = lane / lanes_per_seg;
     const int groups_per_wave = 64 / lanes_per_seg;
     const bool active = so.active;
-    const bool rows_in_desc = a.seg_count[LN_XCD_GROUPS + 1] & 1;  // (uniform: a scalar load)
+    const bool deterministic = CHAIN ? DET : a.deterministic != 0;
     int grp = -1, beg = 0, rbeg = 0, rend = 0, cnt = 0, row = -1;
     if (active) {
-        const int4 d = seg_desc[so.sid];  // {group, first entry, entries to the end of the group, offset inside the group}
+        // {group, first entry, entries to the end of the group, offset inside the group}
+        const int4 d = CHAIN ? *reinterpret_cast<const int4*>(reinterpret_cast<const char*>(seg_desc) + ((unsigned)so.sid << 4)) : seg_desc[so.sid];
         grp = d.x;
         beg = d.y;
         cnt = min(LN_SEG, d.z);
         rbeg = beg - d.w;
         rend = beg + d.z;
-        if (a.deterministic) {  // the lane group of a row's FIRST segment walks the whole row, in CSR order; the others stand by
+        if (deterministic) {  // the lane group of a row's FIRST segment walks the whole row, in CSR order; the others stand by
             cnt = d.w == 0 ? d.z : 0;
             if (d.w != 0) grp = -1 - grp;  // (never equal to a neighbour's group: no combining)
         }
@@ -398,7 +458,7 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
     // the descriptor names the row itself (bucketed build), a hash slot (row = entries[slot]) or a row-group (ln_csr_build)
     if (active) {
         const int g0 = grp >= 0 ? grp : -1 - grp;
-        row = (rows_in_desc || !grp_row) ? g0 : grp_row[g0];
+        row = direct_rows ? g0 : grp_row[g0];
     }
     const int V = chunks * VEC;
     const int nchunk_iter = (chunks + lanes_per_seg - 1) / lanes_per_seg;  // wave-uniform trip count (shuffles inside)
@@ -406,38 +466,73 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
     const int shift = __ffs(src_div) - 1;
     for (int it = 0; it < nchunk_iter; ++it) {
         const int c = lc + it * lanes_per_seg;
-        const bool cok = active && row >= 0 && c < chunks && (!a.deterministic || cnt > 0);
+        const bool cok = active && row >= 0 && c < chunks && (!deterministic || cnt > 0);
         float acc[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
         if (cok) {
-            ln_reduce_entries<VEC, HALF, false>(acc, beg, end, c, csr_tok, w, a.src, src_div, src_stride, pow2, shift);
+            if constexpr (CHAIN)
+                ln_reduce_entries_chain<VEC, HALF, false>(acc, beg, end, (unsigned)c << 4, csr_tok, w, a.src);
+            else
+                ln_reduce_entries<VEC, HALF, false>(acc, beg, end, c, csr_tok, w, a.src, src_div, src_stride, pow2, shift);
             bool nan = false;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) nan |= acc[k] != acc[k];
             if (nan) {  // a NaN or an Inf in the segment's rows: again, with the padding and the -1 ids selected out (rare: off the hot path)
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-                ln_reduce_entries<VEC, HALF, true>(acc, beg, end, c, csr_tok, w, a.src, src_div, src_stride, pow2, shift);
+                if constexpr (CHAIN)
+                    ln_reduce_entries_chain<VEC, HALF, true>(acc, beg, end, (unsigned)c << 4, csr_tok, w, a.src);
+                else
+                    ln_reduce_entries<VEC, HALF, true>(acc, beg, end, c, csr_tok, w, a.src, src_div, src_stride, pow2, shift);
             }
         }
         // segmented suffix reduction over the lane groups of this wave (runs of equal group id are contiguous)
         int run_end = end;
-        for (int off = 1; off < groups_per_wave; off <<= 1) {
-            const int delta = off * lanes_per_seg;
-            const int o_grp = __shfl_down(grp, delta, 64);
-            const int o_end = __shfl_down(run_end, delta, 64);
-            float o_acc[VEC];
+        bool head;
+        if constexpr (CHAIN) {
+            // joins[lane]: my group continues in the next lane group.  Runs are contiguous, so "the group 2 (4) lane groups on is mine"
+            // is joins at both hops of half that distance: the conditions of all three rounds, and `head`, are shifts of ONE ballot in
+            // scalar registers.  A round whose mask is empty would add nothing and is skipped — for the whole wave, its six (ten) moves
+            // through the LDS crossbar with it; the rounds that run add the same partial sums in the same order as the loop below.
+            const int next_grp = __builtin_amdgcn_ds_bpermute(((lane + 8) & 63) << 2, grp);
+            const unsigned long long joins1 = __ballot(grp_in_wave + 1 < groups_per_wave && next_grp == grp && grp >= 0);
+            if (joins1 != 0ull) {
+                unsigned long long joins = joins1;
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) o_acc[k] = __shfl_down(acc[k], delta, 64);
-            if (grp_in_wave + off < groups_per_wave && o_grp == grp && grp >= 0) {
+                for (int off = 1; off < groups_per_wave; off <<= 1) {
+                    if (joins == 0ull) break;  // (wave-uniform; no longer run in this wave)
+                    const int from = ((lane + off * 8) & 63) << 2;
+                    const int o_end = __builtin_amdgcn_ds_bpermute(from, run_end);
+                    float o_acc[VEC];
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) acc[k] += o_acc[k];
-                run_end = max(run_end, o_end);
+                    for (int k = 0; k < VEC; ++k) o_acc[k] = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(acc[k])));
+                    if (__builtin_amdgcn_inverse_ballot_w64(joins)) {
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) acc[k] += o_acc[k];
+                        run_end = max(run_end, o_end);
+                    }
+                    joins &= joins >> (off * 8);  // both hops of this distance join: the group 2 * off lane groups on is mine
+                }
             }
+            head = !__builtin_amdgcn_inverse_ballot_w64(joins1 << 8);  // (no lane group before the first; a group < 0 never joins and never writes)
+        } else {
+            for (int off = 1; off < groups_per_wave; off <<= 1) {
+                const int delta = off * lanes_per_seg;
+                const int o_grp = __shfl_down(grp, delta, 64);
+                const int o_end = __shfl_down(run_end, delta, 64);
+                float o_acc[VEC];
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) o_acc[k] = __shfl_down(acc[k], delta, 64);
+                if (grp_in_wave + off < groups_per_wave && o_grp == grp && grp >= 0) {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc[k] += o_acc[k];
+                    run_end = max(run_end, o_end);
+                }
+            }
+            const int prev_grp = __shfl_up(grp, lanes_per_seg, 64);
+            head = (grp_in_wave == 0) || (prev_grp != grp);
         }
-        const int prev_grp = __shfl_up(grp, lanes_per_seg, 64);
-        const bool head = (grp_in_wave == 0) || (prev_grp != grp);
         // ... and across the wave boundaries of the workgroup: a run that reaches the end of its wave takes in the FIRST run of the
         // next wave(s) when it is the same group.  On dense clouds (C5: 27 tokens per vertex) most rows have several segments and a
         // run cut by a wave boundary costs lanes x VEC float atomics per piece: plain stores instead of the atomics took the C5 splat
@@ -473,7 +568,8 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
             }
         }
         if (cok && head && !absorbed) {
-            float* d = dst + (size_t)row * V + c * VEC;
+            // (the one 64-bit address left in the CHAIN instances: a reduce is not told how many rows dst has; row >= 0 here)
+            float* d = dst + (CHAIN ? (size_t)(unsigned)row : (size_t)row) * V + c * VEC;
             if (beg == rbeg && run_end == rend) {  // this run is the whole group: no other writer
                 if constexpr (VEC == 8) {
                     *reinterpret_cast<float4*>(d) = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -492,24 +588,36 @@ __device__ __forceinline__ void ln_reduce_chunk(const LnSegOfThread& so, const L
 }
 
 // body of the segment reduce for workgroup `block_x` of `nblocks`
-template <int VEC, bool HALF, bool WG, int L8 = 0>
+template <int VEC, bool HALF, bool WG, int L8 = 0, bool CHAIN = false, bool DET = false>
 __device__ __forceinline__ void ln_reduce_body(int block_x, int nblocks, const LnReduceArgs& a) {
-    for (LnSegWalk wk(block_x, nblocks, L8 ? L8 : a.lanes_per_seg, a.seg_count, a.seg_region); wk.more(); wk.next())
-        ln_reduce_chunk<VEC, HALF, WG, L8>(wk.here(), a);
+    // the descriptor names the row itself (bucketed build: bit 0 of the format word), or its group is its row (no grp_row)
+    const bool direct_rows = (a.seg_count[LN_XCD_GROUPS + 1] & 1) || !a.grp_row;  // (uniform: a scalar load, once per workgroup)
+    for (LnSegWalk wk(block_x, nblocks, L8 ? L8 : a.lanes_per_seg, a.seg_count, a.seg_region); wk.more(); wk.next()) {
+        if constexpr (CHAIN) {
+            // ln_chain_fits: a region holds fewer than 2^23 segments, so its lane index and its descriptors' byte offsets fit 32 bits
+            const unsigned gt = (unsigned)wk.j * 256u + threadIdx.x;
+            const LnSegOfThread so{(long long)(gt >> 3), int(gt & 7u), (gt >> 3) < (unsigned)wk.cnt};
+            ln_reduce_chunk<VEC, HALF, WG, L8, true, DET>(so, a, a.seg_desc + wk.base, direct_rows);
+        } else {
+            ln_reduce_chunk<VEC, HALF, WG, L8>(wk.here(), a, a.seg_desc, direct_rows);
+        }
+    }
 }
 
-template <int VEC, bool HALF, bool WG, int L8 = 0>
-__global__ void __launch_bounds__(256) k_csr_reduce_segments(LnReduceArgs a) { ln_reduce_body<VEC, HALF, WG, L8>(blockIdx.x, gridDim.x, a); }
+template <int VEC, bool HALF, bool WG, int L8 = 0, bool CHAIN = false, bool DET = false>
+__global__ void __launch_bounds__(256) k_csr_reduce_segments(LnReduceArgs a) {
+    ln_reduce_body<VEC, HALF, WG, L8, CHAIN, DET>(blockIdx.x, gridDim.x, a);
+}
 
 // Horizontal fusion of the two launches that follow a splat build and do not depend on each other: workgroups
 // [0, reduce_blocks) accumulate the point features onto the vertices (segment reduce), the rest run the same-level
 // neighbour traversal.  One launch instead of two, and the traversal's short, latency-bound workgroups fill the CUs
 // the reduce's tail leaves idle.
-template <int VEC, int D, bool HALF, bool WG, int L8 = 0>
+template <int VEC, int D, bool HALF, bool WG, int L8 = 0, bool CHAIN = false, bool DET = false>
 __global__ void __launch_bounds__(256)
     k_reduce_and_neighbours(LnReduceArgs a, int reduce_blocks, LnTable t, int query_rows_upper, int* __restrict__ nbr) {
     if ((int)blockIdx.x < reduce_blocks) {
-        ln_reduce_body<VEC, HALF, WG, L8>(blockIdx.x, reduce_blocks, a);
+        ln_reduce_body<VEC, HALF, WG, L8, CHAIN, DET>(blockIdx.x, reduce_blocks, a);
     } else {
         // whole vertices per workgroup, and over a space-ordered table the vertices of kd region x on XCD x: the 9 lookups of a vertex
         // land in the slot run of its own region, which then sits in ONE L2 instead of in all eight
@@ -521,8 +629,18 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// The CHAIN instances take rows of LN_CHAIN_ROW_BYTES shared by LN_CHAIN_DIV tokens on eight 16-byte lanes, and address the id lists, the
+// weights, the source rows and a region's descriptors with 32-bit byte offsets.  LnCsr.seg_region >= ln_csr_max_segments(tokens, .) >
+// tokens / LN_CSR_SEG bounds the tokens the CSR was built over: at most 2^23 descriptors per region mean fewer than 2^27 tokens, i.e.
+// less than 2^29 bytes of ids or weights, 2^27 bytes of descriptors per region and (2^27 / 4 rows) x 128 = 2^32 bytes of source rows.
+static bool ln_chain_fits(const LnCsr* csr, bool half, int vec, int chunks, int lanes, int src_div, int src_stride) {
+    return vec * (half ? 2 : 4) == 16 && chunks == 8 && lanes == 8 && src_div == LN_CHAIN_DIV &&
+           (long long)src_stride * (half ? 2 : 4) == LN_CHAIN_ROW_BYTES && csr->seg_region >= 1 && csr->seg_region <= (1ll << 23);
+}
+
 static int ln_reduce_args(const char* who, const LnCsr* csr, const int* grp_row, long long max_segments, const void* src, bool half,
-                          const float* w, int val_dim, int src_div, int src_stride, float* dst, LnReduceArgs& a, int& vec, long long& work) {
+                          const float* w, int val_dim, int src_div, int src_stride, float* dst, LnReduceArgs& a, int& vec, long long& work,
+                          bool& chain) {
     LN_REQUIRE(max_segments >= 0 && val_dim >= 1 && src_div >= 1 && src_stride >= val_dim, LN_ERR_ARG, "%s: bad sizes", who);
     LN_REQUIRE(max_segments == 0 || (csr && csr->grp_start && csr->csr_tok && csr->seg_desc && csr->seg_count && src && w && dst),
                LN_ERR_ARG, "%s: null buffer", who);
@@ -535,6 +653,7 @@ static int ln_reduce_args(const char* who, const LnCsr* csr, const int* grp_row,
     int lanes = 1;
     while (lanes < chunks && lanes < 64) lanes <<= 1;
     work = max_segments * lanes;
+    chain = max_segments > 0 && ln_chain_fits(csr, half, vec, chunks, lanes, src_div, src_stride);
     if (max_segments > 0) a = LnReduceArgs{csr->grp_start, csr->csr_tok, reinterpret_cast<const int4*>(csr->seg_desc), csr->seg_count, grp_row, src, w, chunks, lanes,
                                            src_div, src_stride, dst, csr->seg_region, (csr->dense & 2) ? 1 : 0};
     return LN_OK;
@@ -545,7 +664,8 @@ static int ln_csr_reduce_rows_impl(const char* who, const LnCsr* csr, const int*
     LnReduceArgs a;
     int vec;
     long long work;
-    int rc = ln_reduce_args(who, csr, grp_row, max_segments, src, half, w, val_dim, src_div, src_stride, dst, a, vec, work);
+    bool chain;
+    int rc = ln_reduce_args(who, csr, grp_row, max_segments, src, half, w, val_dim, src_div, src_stride, dst, a, vec, work, chain);
     if (rc) return rc;
     if (max_segments == 0) return LN_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -555,10 +675,16 @@ static int ln_csr_reduce_rows_impl(const char* who, const LnCsr* csr, const int*
     const bool wg = ((csr->dense & 1) != 0 || a.lanes_per_seg >= 16) && vec >= 4 && !(csr->dense & 2);
 #define LN_REDUCE_LAUNCH(VV, HH)                                                                                                     \
     {                                                                                                                                \
-        if (wg && VV == 8 && HH && a.lanes_per_seg == 8 && a.chunks == 8)                                                            \
+        if (wg && VV == 8 && HH && chain)                                                                                            \
+            LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<8, true, true, 8, true>), grid, block, 0, st, a);              \
+        else if (wg && VV == 8 && HH && a.lanes_per_seg == 8 && a.chunks == 8)                                                       \
             LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<8, true, true, 8>), grid, block, 0, st, a);                    \
         else if (wg)                                                                                                                 \
             LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<VV, HH, (VV >= 4)>), grid, block, 0, st, a);                   \
+        else if (VV == 4 && !HH && chain && a.deterministic)                                                                         \
+            LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<4, false, false, 8, true, true>), grid, block, 0, st, a);      \
+        else if (VV == 4 && !HH && chain)                                                                                            \
+            LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<4, false, false, 8, true>), grid, block, 0, st, a);            \
         else if (VV == 4 && !HH && a.lanes_per_seg == 8 && a.chunks == 8)                                                            \
             LN_LAUNCH("k_csr_reduce_segments", (k_csr_reduce_segments<4, false, false, 8>), grid, block, 0, st, a);                  \
         else                                                                                                                         \
@@ -594,7 +720,8 @@ static int ln_splat_tail_impl(const char* who, const LnCsr* csr, const int* grp_
     LnReduceArgs a;
     int vec;
     long long work;
-    int rc = ln_reduce_args(who, csr, grp_row, max_segments, src, half, w, val_dim, src_div, src_stride, dst, a, vec, work);
+    bool chain;
+    int rc = ln_reduce_args(who, csr, grp_row, max_segments, src, half, w, val_dim, src_div, src_stride, dst, a, vec, work, chain);
     if (rc) return rc;
     LN_REQUIRE(table && table->slot_keys && table->entries && table->keys && table->nr_filled && table->capacity > 0, LN_ERR_ARG,
                "%s: bad table", who);
@@ -629,6 +756,17 @@ static int ln_splat_tail_impl(const char* who, const LnCsr* csr, const int* grp_
         else LN_FUSED_LAUNCH(1, DD, false)                                                                                           \
         break;
     const bool wg = ((csr->dense & 1) != 0 || a.lanes_per_seg >= 16) && vec >= 4 && !(csr->dense & 2);
+    // the chain's instances (LN_CHAIN_DIV = 3 + 1 tokens per point: instantiated for three position dimensions only)
+    if (chain && d == 3 && half && vec == 8 && wg)
+        LN_LAUNCH("k_reduce_and_neighbours", (k_reduce_and_neighbours<8, 3, true, true, 8, true>), grid, block, 0, st, a, reduce_blocks, *table,
+                  query_rows_upper, nbr);
+    else if (chain && d == 3 && !half && vec == 4 && !wg && a.deterministic)
+        LN_LAUNCH("k_reduce_and_neighbours", (k_reduce_and_neighbours<4, 3, false, false, 8, true, true>), grid, block, 0, st, a, reduce_blocks,
+                  *table, query_rows_upper, nbr);
+    else if (chain && d == 3 && !half && vec == 4 && !wg)
+        LN_LAUNCH("k_reduce_and_neighbours", (k_reduce_and_neighbours<4, 3, false, false, 8, true>), grid, block, 0, st, a, reduce_blocks, *table,
+                  query_rows_upper, nbr);
+    else
     switch (d) { LN_FUSED_CASE(1) LN_FUSED_CASE(2) LN_FUSED_CASE(3) LN_FUSED_CASE(4) LN_FUSED_CASE(5) LN_FUSED_CASE(6) }
 #undef LN_FUSED_LAUNCH
 #undef LN_FUSED_CASE
