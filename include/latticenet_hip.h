@@ -609,6 +609,44 @@ int ln_lovasz_forward(const float* log_probs, const long long* target, long long
                       void* workspace, size_t workspace_bytes, float* loss, float* per_class, float* dloss_dlogp, void* stream);
 int ln_lovasz_backward(const float* dloss_dlogp, const float* grad_loss, long long n, int classes, float* grad_log_probs, void* stream);
 
+/* The same loss PER CLOUD for a batch of clouds in one matrix (Berman's per_image=True): the n rows are cloud-major, cloud b owns rows
+ * [b n0, min((b + 1) n0, n)) with n0 = points_per_cloud, B = ceil(n / n0) clouds, the last one possibly shorter (what
+ * Lattice.set_cloud_batch defines; points_per_cloud >= n is one cloud).  per_cloud [B] (may be NULL) and row b of per_class
+ * [B, classes] (may be NULL) are what ln_lovasz_forward gives on cloud b's rows alone, bit for bit: the same arithmetic, ties by
+ * ascending point index inside the cloud, the cloud's own set of counting classes; a cloud with no counting class has loss 0.
+ * loss[0] = (sum_b per_cloud[b]) / B, the clouds added in a fixed order (strided over 256 threads in series, then the fixed tree of a
+ * workgroup).  dloss_dlogp [n, classes], every element written: the single-cloud coefficient of the point within its cloud, divided
+ * by B (one IEEE division: one more rounding, none when B is a power of two); a class that does not count in cloud b is 0 on that
+ * cloud's rows only.
+ * ln_lovasz_backward is the backward.  The sort works on B x classes segments of at most n0 items: keys, payloads and tile histograms
+ * are per (cloud, class), a tile never spans two clouds, and the sort payload is the point's index INSIDE ITS CLOUD (plus the foreground
+ * bit).  One launch more than ln_lovasz_forward (the mean over the clouds), none per cloud.
+ * Limits (LN_ERR_ARG otherwise, nothing launched or written): points_per_cloud >= 1, n >= 0, 1 <= classes <= 1024, n * classes < 2^31,
+ * B <= 65535 (the cloud is the z coordinate of the tile grids and the y coordinate of the scan grids, the class their y / x coordinate;
+ * no grid has 2^32 work-items in one dimension: B x classes itself is bounded only by B <= 65535 and classes <= 1024), reduction 0 or 1,
+ * a workspace of ln_lovasz_clouds_workspace_bytes (a pure host function, total).  The workspace grows with B x classes, not only with
+ * n x classes: besides 16 bytes per (point, class) it holds 1 KB of digit histogram per (cloud, class, tile of 2048 points of a cloud),
+ * however few points a cloud has — 700 clouds of 3 points at 20 classes take 14 MB, 65 535 clouds at 65 classes 4.4 GB.
+ * n == 0 sets loss to 0 and runs no sort.  No host synchronisation, no allocation, no float atomics: safe inside a stream capture,
+ * bitwise reproducible. */
+size_t ln_lovasz_clouds_workspace_bytes(long long n, long long points_per_cloud, int classes);
+int ln_lovasz_forward_clouds(const float* log_probs, const long long* target, long long n, long long points_per_cloud, int classes,
+                             long long ignore_index, int reduction, void* workspace, size_t workspace_bytes, float* loss, float* per_cloud,
+                             float* per_class, float* dloss_dlogp, void* stream);
+
+/* Intersection / union counts of the validation metric (callbacks/scores.py), per cloud of such a batch, added onto the int64
+ * accumulators intersection [classes] and union_ [classes].  scores [n, classes] float, target [n] int64.  Per cloud: pred_i = the
+ * lowest class index among the maxima of row i (torch.argmax); hit_c = #{pred = target = c} with the UNCLAMPED label (a label outside
+ * [0, classes) never hits); n_gt_c counts labels clamped to [0, classes - 1]; n_pred_c = #{pred = c}; in_gt_c = n_gt_c > 0 and
+ * c != unlabeled_index (any value outside [0, classes) for none).  intersection[c] += sum_b hit in_gt, union_[c] += sum_b (n_gt +
+ * n_pred - hit) in_gt — Scores.accumulate_scores called cloud by cloud.  All integer: exact and independent of any order.  Rows that
+ * hold a NaN are NOT held to torch's rule.  Limits and host behaviour as ln_lovasz_forward_clouds (the cloud is the y coordinate of
+ * the grid: B <= 65535); n == 0 adds nothing. */
+size_t ln_iou_counts_clouds_workspace_bytes(long long n, long long points_per_cloud, int classes);
+int ln_iou_counts_clouds(const float* scores, const long long* target, long long n, long long points_per_cloud, int classes,
+                         long long unlabeled_index, void* workspace, size_t workspace_bytes, long long* intersection, long long* union_,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

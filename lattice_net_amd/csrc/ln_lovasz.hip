@@ -25,6 +25,14 @@
 //                      scale_c s g p scattered to dloss_dlogp[point, c]  (s = -1 foreground, +1 background)
 //   k_lovasz_finish    tile sums -> per-class losses -> loss
 //   k_lovasz_backward  grad_log_probs = grad_loss * dloss_dlogp
+//
+// Batch of clouds (ln_lovasz_forward_clouds): the same kernels over B x C segments.  The points are cloud-major, cloud b owns rows
+// [b n0, min((b + 1) n0, n)): every cloud has n0 points, the last one len_B-1 <= n0.  The cloud is the z coordinate of every grid, the
+// class its y coordinate, a tile of 2048 sorted positions its x coordinate — so a tile never spans two clouds, and the tiles behind a
+// short last cloud find no item.  Segment (b, c) keeps its keys and payloads at  b n0 C + c len_b  (all clouds in front of b are
+// full: the buffers stay n C words), its tile histograms, tile counts and tile sums at  (b C + c) * tiles(n0);  the payload is the
+// point's index INSIDE its cloud.  The single-cloud call is the case n0 = n, B = 1 of the same launches.  k_lovasz_finish runs one
+// workgroup per cloud; k_lovasz_cloud_mean adds the clouds' losses in a fixed order and divides by B.  The gradient coefficient is divided by B.
 #include "ln_common.h"
 
 #define LN_LV_THREADS 256
@@ -34,6 +42,7 @@
 #define LN_LV_SCAN_THREADS 1024
 #define LN_LV_PASSES 4
 #define LN_LV_MAX_CLASSES 1024
+#define LN_LV_MAX_CLOUDS 65535  // grid z
 #define LN_LV_FG 0x80000000u
 
 __device__ __forceinline__ float ln_lv_prob(float lp) {
@@ -48,42 +57,62 @@ __device__ __forceinline__ long long ln_lv_item(int b, int j) {
     return (long long)b * LN_LV_TILE + (threadIdx.x >> 6) * (64 * LN_LV_IPT) + j * 64 + (threadIdx.x & 63);
 }
 
-__global__ void __launch_bounds__(LN_LV_THREADS)
-    k_lovasz_keys(const float* __restrict__ lp, const long long* __restrict__ target, long long n, int C, uint32_t* __restrict__ keys,
-                  uint32_t* __restrict__ pay) {
-    const long long i = (long long)blockIdx.x * LN_LV_THREADS + threadIdx.x;
-    const int c = blockIdx.y;
-    if (i >= n) return;
-    const long long t = target[i];
-    const long long tc = t < 0 ? 0 : (t >= C ? C - 1 : t);
-    const bool fg = tc == c;
-    const float e = ln_lv_error(lp[i * C + c], fg);
-    keys[(long long)c * n + i] = 0x7FFFFFFFu - (__float_as_uint(e) & 0x7FFFFFFFu);
-    pay[(long long)c * n + i] = uint32_t(i) | (fg ? LN_LV_FG : 0u);
+// Segment (cloud blockIdx.z, class blockIdx.y) of a launch: `first` = the cloud's first point row, `len` = its points (n0, less for the
+// last cloud), `base` = the segment's first word in the key / payload buffers, `id` = cloud * C + class.
+struct LnLvSegment {
+    long long first, len, base, id;
+};
+__device__ __forceinline__ LnLvSegment ln_lv_segment(long long n, long long n0, int C) {
+    LnLvSegment s;
+    s.first = (long long)blockIdx.z * n0;
+    s.len = n - s.first < n0 ? n - s.first : n0;
+    s.base = s.first * C + (long long)blockIdx.y * s.len;
+    s.id = (long long)blockIdx.z * C + blockIdx.y;
+    return s;
 }
 
-// digit histogram of every tile: hist[(c * 256 + digit) * nblk + b]
 __global__ void __launch_bounds__(LN_LV_THREADS)
-    k_lovasz_hist(const uint32_t* __restrict__ keys, long long n, int nblk, int shift, uint32_t* __restrict__ hist) {
+    k_lovasz_keys(const float* __restrict__ lp, const long long* __restrict__ target, long long n, long long n0, int C,
+                  uint32_t* __restrict__ keys, uint32_t* __restrict__ pay) {
+    const long long i = (long long)blockIdx.x * LN_LV_THREADS + threadIdx.x;  // inside the cloud
+    const int c = blockIdx.y;
+    const LnLvSegment s = ln_lv_segment(n, n0, C);
+    if (i >= s.len) return;
+    const long long t = target[s.first + i];
+    const long long tc = t < 0 ? 0 : (t >= C ? C - 1 : t);
+    const bool fg = tc == c;
+    const float e = ln_lv_error(lp[(s.first + i) * C + c], fg);
+    keys[s.base + i] = 0x7FFFFFFFu - (__float_as_uint(e) & 0x7FFFFFFFu);
+    pay[s.base + i] = uint32_t(i) | (fg ? LN_LV_FG : 0u);
+}
+
+// digit histogram of every tile: hist[(segment * 256 + digit) * nblk + b]
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_hist(const uint32_t* __restrict__ keys, long long n, long long n0, int C, int nblk, int shift, uint32_t* __restrict__ hist) {
     __shared__ uint32_t s_h[256];
-    const int b = blockIdx.x, c = blockIdx.y;
+    const int b = blockIdx.x;
+    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const long long len = sg.len;
     s_h[threadIdx.x] = 0;
     __syncthreads();
-    const uint32_t* k = keys + (long long)c * n;
+    const uint32_t* k = keys + sg.base;
 #pragma unroll
     for (int j = 0; j < LN_LV_IPT; ++j) {
         const long long pos = ln_lv_item(b, j);
-        if (pos < n) atomicAdd(&s_h[(k[pos] >> shift) & 255u], 1u);  // (integer: the order of the additions is immaterial)
+        if (pos < len) atomicAdd(&s_h[(k[pos] >> shift) & 255u], 1u);  // (integer: the order of the additions is immaterial)
     }
     __syncthreads();
-    hist[((long long)c * 256 + threadIdx.x) * nblk + b] = s_h[threadIdx.x];
+    hist[(sg.id * 256 + threadIdx.x) * nblk + b] = s_h[threadIdx.x];
 }
 
-// exclusive scan in place of `len` ints per class (one workgroup per class, contiguous chunk per thread); totals[c] = the sum
+// exclusive scan in place of `len` ints per segment (one workgroup per segment, contiguous chunk per thread); totals[segment] = the sum.
+// Grid (classes, clouds): with 1024 threads a one-dimensional grid of B C workgroups would pass the 2^32 work-items a launch may
+// have in one dimension at B C = 2^22.
 __global__ void __launch_bounds__(LN_LV_SCAN_THREADS)
     k_lovasz_scan(uint32_t* __restrict__ data, long long len, int* __restrict__ totals) {
     __shared__ int s_tmp[LN_LV_SCAN_THREADS / 64];
-    uint32_t* d = data + (long long)blockIdx.x * len;
+    const long long seg = (long long)blockIdx.y * gridDim.x + blockIdx.x;
+    uint32_t* d = data + seg * len;
     const long long chunk = (len + LN_LV_SCAN_THREADS - 1) / LN_LV_SCAN_THREADS;
     const long long lo = threadIdx.x * chunk;
     const long long hi = lo + chunk < len ? lo + chunk : len;
@@ -96,24 +125,26 @@ __global__ void __launch_bounds__(LN_LV_SCAN_THREADS)
         d[k] = uint32_t(run);
         run += v;
     }
-    if (totals && threadIdx.x == 0) totals[blockIdx.x] = total;
+    if (totals && threadIdx.x == 0) totals[seg] = total;
 }
 
 // one stable pass: an item goes to  (items of smaller digits) + (items of its digit in earlier tiles)  [both: the scanned hist]
 //                                 + (items of its digit earlier in this tile: earlier waves, earlier rounds, lower lanes)
 __global__ void __launch_bounds__(LN_LV_THREADS)
     k_lovasz_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ pay_in, uint32_t* __restrict__ keys_out,
-                     uint32_t* __restrict__ pay_out, const uint32_t* __restrict__ hist, long long n, int nblk, int shift) {
+                     uint32_t* __restrict__ pay_out, const uint32_t* __restrict__ hist, long long n, long long n0, int C, int nblk,
+                     int shift) {
     __shared__ uint32_t s_cnt[LN_LV_WAVES][256];
-    const int b = blockIdx.x, c = blockIdx.y;
+    const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long seg = (long long)c * n;
+    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const long long seg = sg.base, len = sg.len;
     uint32_t key[LN_LV_IPT], pl[LN_LV_IPT], rank[LN_LV_IPT];
 #pragma unroll
     for (int j = 0; j < LN_LV_IPT; ++j) {
         const long long pos = ln_lv_item(b, j);
-        key[j] = pos < n ? keys_in[seg + pos] : 0u;
-        pl[j] = pos < n ? pay_in[seg + pos] : 0u;
+        key[j] = pos < len ? keys_in[seg + pos] : 0u;
+        pl[j] = pos < len ? pay_in[seg + pos] : 0u;
     }
 #pragma unroll
     for (int w = 0; w < LN_LV_WAVES; ++w) s_cnt[w][threadIdx.x] = 0;
@@ -121,7 +152,7 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
     const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
     for (int j = 0; j < LN_LV_IPT; ++j) {
-        const bool valid = ln_lv_item(b, j) < n;
+        const bool valid = ln_lv_item(b, j) < len;
         const uint32_t d = (key[j] >> shift) & 255u;
         unsigned long long peers = __ballot(valid);  // lanes of this round that hold the same digit
 #pragma unroll
@@ -144,7 +175,7 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
     }
     __syncthreads();
     {  // thread = digit: wave counts -> first destination of every wave's items of that digit
-        uint32_t run = hist[((long long)c * 256 + threadIdx.x) * nblk + b];
+        uint32_t run = hist[(sg.id * 256 + threadIdx.x) * nblk + b];
 #pragma unroll
         for (int w = 0; w < LN_LV_WAVES; ++w) {
             const uint32_t v = s_cnt[w][threadIdx.x];
@@ -155,9 +186,9 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < LN_LV_IPT; ++j) {
-        if (ln_lv_item(b, j) >= n) continue;
+        if (ln_lv_item(b, j) >= len) continue;
         const long long dst = (long long)s_cnt[wave][(key[j] >> shift) & 255u] + rank[j];
-        if (dst < n) {  // (always, by construction)
+        if (dst < len) {  // (always, by construction)
             keys_out[seg + dst] = key[j];
             pay_out[seg + dst] = pl[j];
         }
@@ -165,15 +196,17 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
 }
 
 __global__ void __launch_bounds__(LN_LV_THREADS)
-    k_lovasz_fg_count(const uint32_t* __restrict__ pay, long long n, int nblk, uint32_t* __restrict__ fgcnt) {
+    k_lovasz_fg_count(const uint32_t* __restrict__ pay, long long n, long long n0, int C, int nblk, uint32_t* __restrict__ fgcnt) {
     __shared__ int s_w[LN_LV_WAVES];
-    const int b = blockIdx.x, c = blockIdx.y;
-    const uint32_t* p = pay + (long long)c * n;
+    const int b = blockIdx.x;
+    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const long long len = sg.len;
+    const uint32_t* p = pay + sg.base;
     int cnt = 0;
 #pragma unroll
     for (int j = 0; j < LN_LV_IPT; ++j) {
         const long long pos = ln_lv_item(b, j);
-        const bool fg = pos < n && (p[pos] & LN_LV_FG);
+        const bool fg = pos < len && (p[pos] & LN_LV_FG);
         cnt += __popcll(__ballot(fg));  // wave-uniform
     }
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
@@ -182,7 +215,7 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
         int t = 0;
 #pragma unroll
         for (int w = 0; w < LN_LV_WAVES; ++w) t += s_w[w];
-        fgcnt[(long long)c * nblk + b] = uint32_t(t);
+        fgcnt[sg.id * nblk + b] = uint32_t(t);
     }
 }
 
@@ -209,14 +242,16 @@ __device__ __forceinline__ float ln_lv_block_sum(float x, float* s_w) {
 
 __global__ void __launch_bounds__(LN_LV_THREADS)
     k_lovasz_dot(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pay, const uint32_t* __restrict__ fgbase,
-                 const int* __restrict__ G, const float* __restrict__ lp, long long n, int C, int nblk, long long ignore_index,
-                 int reduction, float* __restrict__ partial, float* __restrict__ dl) {
+                 const int* __restrict__ Gall, const float* __restrict__ lp, long long n, long long n0, int C, int nblk,
+                 long long ignore_index, int reduction, float clouds, float* __restrict__ partial, float* __restrict__ dl) {
     __shared__ int s_tmp[8];
     __shared__ int s_fg[LN_LV_WAVES];
     __shared__ float s_w[LN_LV_WAVES];
     const int b = blockIdx.x, c = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long seg = (long long)c * n;
+    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const long long seg = sg.base, len = sg.len;
+    const int* G = Gall + (long long)blockIdx.z * C;  // of this cloud's classes
     const int counting = ln_lv_counting(G, C, ignore_index, s_tmp);
     const int Gc = G[c];
     const bool counts = Gc > 0 && c != ignore_index;
@@ -227,14 +262,14 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
 #pragma unroll
     for (int j = 0; j < LN_LV_IPT; ++j) {
         const long long pos = ln_lv_item(b, j);
-        key[j] = pos < n ? keys[seg + pos] : 0u;
-        pl[j] = pos < n ? pay[seg + pos] : 0u;
+        key[j] = pos < len ? keys[seg + pos] : 0u;
+        pl[j] = pos < len ? pay[seg + pos] : 0u;
         fgmask[j] = __ballot((pl[j] & LN_LV_FG) != 0);
         mine += __popcll(fgmask[j]);
     }
     if (lane == 0) s_fg[wave] = mine;
     __syncthreads();
-    long long F = fgbase[(long long)c * nblk + b];  // foreground elements in front of this wave's first item
+    long long F = fgbase[sg.id * nblk + b];  // foreground elements in front of this wave's first item
 #pragma unroll
     for (int w = 0; w < LN_LV_WAVES; ++w)
         if (w < wave) F += s_fg[w];
@@ -245,28 +280,33 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
         const long long pos = ln_lv_item(b, j);
         const long long Fk = F + __popcll(fgmask[j] & upto);  // inclusive
         F += __popcll(fgmask[j]);
-        if (pos >= n) continue;
+        if (pos >= len) continue;
         const bool fg = (pl[j] & LN_LV_FG) != 0;
         const long long i = pl[j] & ~LN_LV_FG;
-        if (i >= n) continue;  // (never: the payload is a point index)
+        if (i >= len) continue;  // (never: the payload is a point index inside the cloud)
+        const long long at = (sg.first + i) * C + c;
         float coef = 0.f;
         if (counts) {
             const long long U = Gc + (pos + 1 - Fk), I = Gc - Fk;
             const float g = fg ? 1.f / float(U) : float(I) / float((unsigned long long)(U * (U - 1)));
             const float e = __uint_as_float(0x7FFFFFFFu - key[j]);
             acc += e * g;
-            coef = ((fg ? -g : g) * ln_lv_prob(lp[i * C + c])) * scale;
+            coef = (((fg ? -g : g) * ln_lv_prob(lp[at])) * scale) / clouds;  // one rounding (none when `clouds` is a power of two; x / 1 = x)
         }
-        dl[i * C + c] = coef;
+        dl[at] = coef;
     }
     const float t = ln_lv_block_sum(acc, s_w);
-    if (threadIdx.x == 0) partial[(long long)c * nblk + b] = t;
+    if (threadIdx.x == 0) partial[sg.id * nblk + b] = t;
 }
 
+// one workgroup per cloud: loss[cloud], per_class[cloud, :]
 __global__ void __launch_bounds__(LN_LV_THREADS)
-    k_lovasz_finish(const float* __restrict__ partial, const int* __restrict__ G, int nblk, int C, long long ignore_index, int reduction,
-                    float* __restrict__ loss, float* __restrict__ per_class) {
+    k_lovasz_finish(const float* __restrict__ partial_all, const int* __restrict__ Gall, int nblk, int C, long long ignore_index,
+                    int reduction, float* __restrict__ loss, float* __restrict__ per_class_all) {
     __shared__ float s_w[LN_LV_WAVES];
+    const float* partial = partial_all + (long long)blockIdx.x * C * nblk;
+    const int* G = Gall + (long long)blockIdx.x * C;
+    float* per_class = per_class_all ? per_class_all + (long long)blockIdx.x * C : nullptr;
     float total = 0.f;
     int counting = 0;
     for (int c = 0; c < C; ++c) {
@@ -282,7 +322,21 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
             if (per_class) per_class[c] = counts ? pc : 0.f;
         }
     }
-    if (threadIdx.x == 0) loss[0] = reduction == 0 ? total / float(counting < 1 ? 1 : counting) : total;
+    if (threadIdx.x == 0) loss[blockIdx.x] = reduction == 0 ? total / float(counting < 1 ? 1 : counting) : total;
+}
+
+// loss[0] = (cloud[0] + .. + cloud[B - 1]) / B: the clouds strided over the 256 threads in series, then the workgroup's fixed tree
+__global__ void __launch_bounds__(LN_LV_THREADS)
+    k_lovasz_cloud_mean(const float* __restrict__ cloud, long long B, float* __restrict__ loss, float* __restrict__ per_cloud) {
+    __shared__ float s_w[LN_LV_WAVES];
+    float acc = 0.f;
+    for (long long k = threadIdx.x; k < B; k += LN_LV_THREADS) {
+        const float v = cloud[k];
+        acc += v;
+        if (per_cloud) per_cloud[k] = v;
+    }
+    const float t = ln_lv_block_sum(acc, s_w);
+    if (threadIdx.x == 0) loss[0] = t / float(B);
 }
 
 __global__ void __launch_bounds__(256)
@@ -294,14 +348,21 @@ __global__ void __launch_bounds__(256)
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct LnLovaszLayout {
-    int nblk;
-    size_t keys[2], pay[2], hist, fgcnt, G, partial, bytes;
+    long long n0, clouds;  // points of a full cloud (<= n), clouds (>= 1)
+    int nblk;              // tiles of a full cloud
+    size_t keys[2], pay[2], hist, fgcnt, G, partial, cloud, bytes;
 };
 size_t ln_lv_align(size_t x) { return (x + 255) & ~size_t(255); }
-LnLovaszLayout ln_lv_layout(long long n, int classes) {
+// total: any argument gives a layout (negative sizes count as 0, points_per_cloud is brought into [1, max(n, 1)])
+LnLovaszLayout ln_lv_layout(long long n, long long points_per_cloud, int classes, bool per_cloud) {
     LnLovaszLayout L;
-    const size_t N = n > 0 ? size_t(n) : 0, C = classes > 0 ? size_t(classes) : 0;
-    L.nblk = int((N + LN_LV_TILE - 1) / LN_LV_TILE);
+    const size_t N = n > 0 ? size_t(n) : 0;
+    const size_t P = points_per_cloud < 1 || N == 0 ? 1 : (size_t(points_per_cloud) > N ? N : size_t(points_per_cloud));
+    const size_t B = N == 0 ? 1 : (N + P - 1) / P;
+    const size_t C = classes > 0 ? size_t(classes) : 0, S = C * B;  // classes, segments
+    L.n0 = (long long)P;
+    L.clouds = (long long)B;
+    L.nblk = int(((N < P ? N : P) + LN_LV_TILE - 1) / LN_LV_TILE);
     size_t at = 0;
     for (int k = 0; k < 2; ++k) {
         L.keys[k] = at;
@@ -310,37 +371,42 @@ LnLovaszLayout ln_lv_layout(long long n, int classes) {
         at = ln_lv_align(at + C * N * 4);
     }
     L.hist = at;
-    at = ln_lv_align(at + C * 256 * size_t(L.nblk) * 4);
+    at = ln_lv_align(at + S * 256 * size_t(L.nblk) * 4);
     L.fgcnt = at;
-    at = ln_lv_align(at + C * size_t(L.nblk) * 4);
+    at = ln_lv_align(at + S * size_t(L.nblk) * 4);
     L.G = at;
-    at = ln_lv_align(at + C * 4);
+    at = ln_lv_align(at + S * 4);
     L.partial = at;
-    at = ln_lv_align(at + C * size_t(L.nblk) * 4);
+    at = ln_lv_align(at + S * size_t(L.nblk) * 4);
+    L.cloud = at;
+    if (per_cloud) at = ln_lv_align(at + B * 4);
     L.bytes = at + 256;
     return L;
 }
-}  // namespace
 
-extern "C" size_t ln_lovasz_workspace_bytes(long long n, int classes) { return ln_lv_layout(n, classes).bytes; }
-
-extern "C" int ln_lovasz_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index,
-                                 int reduction, void* workspace, size_t workspace_bytes, float* loss, float* per_class,
-                                 float* dloss_dlogp, void* stream) {
-    LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_LV_MAX_CLASSES, LN_ERR_ARG, "ln_lovasz_forward: bad sizes (n >= 0, 1 <= classes <= %d)",
+// Both entry points: `who` names the caller in messages; per_cloud_form: ln_lovasz_forward_clouds (the other passes
+// points_per_cloud = n, one cloud, and k_lovasz_finish writes the loss itself).
+int ln_lv_forward(const char* who, bool per_cloud_form, const float* log_probs, const long long* target, long long n,
+                  long long points_per_cloud, int classes, long long ignore_index, int reduction, void* workspace, size_t workspace_bytes,
+                  float* loss, float* per_cloud, float* per_class, float* dloss_dlogp, hipStream_t st) {
+    LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_LV_MAX_CLASSES, LN_ERR_ARG, "%s: bad sizes (n >= 0, 1 <= classes <= %d)", who,
                LN_LV_MAX_CLASSES);
-    LN_REQUIRE(n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_ARG, "ln_lovasz_forward: n * classes must stay below 2^31");
-    LN_REQUIRE(reduction == 0 || reduction == 1, LN_ERR_ARG, "ln_lovasz_forward: reduction is 0 (mean) or 1 (sum)");
-    LN_REQUIRE(loss, LN_ERR_ARG, "ln_lovasz_forward: null buffer");
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) {  // no class is present: the loss is 0
+    LN_REQUIRE(points_per_cloud >= 1 || !per_cloud_form, LN_ERR_ARG, "%s: bad sizes (points_per_cloud >= 1)", who);
+    LN_REQUIRE(n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_ARG, "%s: n * classes must stay below 2^31", who);
+    LN_REQUIRE(reduction == 0 || reduction == 1, LN_ERR_ARG, "%s: reduction is 0 (mean) or 1 (sum)", who);
+    LN_REQUIRE(loss, LN_ERR_ARG, "%s: null buffer", who);
+    const LnLovaszLayout L = ln_lv_layout(n, points_per_cloud, classes, per_cloud_form);
+    LN_REQUIRE(L.clouds <= LN_LV_MAX_CLOUDS, LN_ERR_ARG, "%s: %lld clouds, at most %d (the cloud is the z coordinate of the grids)", who,
+               L.clouds, LN_LV_MAX_CLOUDS);
+    if (n == 0) {  // no class is present: the loss is 0 (and there is no cloud: per_cloud and the per-cloud per_class have no element)
         int rc = ln_zero_async(loss, sizeof(float), st);
-        if (rc == LN_OK && per_class) rc = ln_zero_async(per_class, size_t(classes) * sizeof(float), st);
+        if (rc == LN_OK && per_class && !per_cloud_form) rc = ln_zero_async(per_class, size_t(classes) * sizeof(float), st);
         return rc;
     }
-    LN_REQUIRE(log_probs && target && dloss_dlogp, LN_ERR_ARG, "ln_lovasz_forward: null buffer");
-    const LnLovaszLayout L = ln_lv_layout(n, classes);
-    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_lovasz_forward: null / small workspace (%zu bytes needed)", L.bytes);
+    LN_REQUIRE(log_probs && target && dloss_dlogp, LN_ERR_ARG, "%s: null buffer", who);
+    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "%s: null / small workspace (%zu bytes needed)", who, L.bytes);
+    const long long n0 = L.n0;
+    const int B = int(L.clouds);
     char* ws = static_cast<char*>(workspace);
     uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(ws + L.keys[0]), reinterpret_cast<uint32_t*>(ws + L.keys[1])};
     uint32_t* pay[2] = {reinterpret_cast<uint32_t*>(ws + L.pay[0]), reinterpret_cast<uint32_t*>(ws + L.pay[1])};
@@ -348,22 +414,47 @@ extern "C" int ln_lovasz_forward(const float* log_probs, const long long* target
     uint32_t* fgcnt = reinterpret_cast<uint32_t*>(ws + L.fgcnt);
     int* G = reinterpret_cast<int*>(ws + L.G);
     float* partial = reinterpret_cast<float*>(ws + L.partial);
-    const dim3 tiles(L.nblk, classes), thr(LN_LV_THREADS);
-    LN_LAUNCH("k_lovasz_keys", k_lovasz_keys, dim3(ln_div_up(n, LN_LV_THREADS), classes), thr, 0, st, log_probs, target, n, classes, keys[0],
-              pay[0]);
+    float* cloud = reinterpret_cast<float*>(ws + L.cloud);
+    const dim3 tiles(L.nblk, classes, B), segments(classes, B), thr(LN_LV_THREADS);
+    LN_LAUNCH("k_lovasz_keys", k_lovasz_keys, dim3(ln_div_up(n0, LN_LV_THREADS), classes, B), thr, 0, st, log_probs, target, n, n0, classes,
+              keys[0], pay[0]);
     for (int pass = 0; pass < LN_LV_PASSES; ++pass) {
         const int in = pass & 1, out = in ^ 1, shift = 8 * pass;
-        LN_LAUNCH("k_lovasz_hist", k_lovasz_hist, tiles, thr, 0, st, keys[in], n, L.nblk, shift, hist);
-        LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, dim3(classes), dim3(LN_LV_SCAN_THREADS), 0, st, hist, 256ll * L.nblk, (int*)nullptr);
-        LN_LAUNCH("k_lovasz_scatter", k_lovasz_scatter, tiles, thr, 0, st, keys[in], pay[in], keys[out], pay[out], hist, n, L.nblk, shift);
+        LN_LAUNCH("k_lovasz_hist", k_lovasz_hist, tiles, thr, 0, st, keys[in], n, n0, classes, L.nblk, shift, hist);
+        LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, segments, dim3(LN_LV_SCAN_THREADS), 0, st, hist, 256ll * L.nblk, (int*)nullptr);
+        LN_LAUNCH("k_lovasz_scatter", k_lovasz_scatter, tiles, thr, 0, st, keys[in], pay[in], keys[out], pay[out], hist, n, n0, classes, L.nblk,
+                  shift);
     }
     static_assert(LN_LV_PASSES % 2 == 0, "the sorted order ends in buffer 0");
-    LN_LAUNCH("k_lovasz_fg_count", k_lovasz_fg_count, tiles, thr, 0, st, pay[0], n, L.nblk, fgcnt);
-    LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, dim3(classes), dim3(LN_LV_SCAN_THREADS), 0, st, fgcnt, (long long)L.nblk, G);
-    LN_LAUNCH("k_lovasz_dot", k_lovasz_dot, tiles, thr, 0, st, keys[0], pay[0], fgcnt, G, log_probs, n, classes, L.nblk, ignore_index, reduction,
-              partial, dloss_dlogp);
-    LN_LAUNCH("k_lovasz_finish", k_lovasz_finish, dim3(1), thr, 0, st, partial, G, L.nblk, classes, ignore_index, reduction, loss, per_class);
-    return ln_check_launch("ln_lovasz_forward");
+    LN_LAUNCH("k_lovasz_fg_count", k_lovasz_fg_count, tiles, thr, 0, st, pay[0], n, n0, classes, L.nblk, fgcnt);
+    LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, segments, dim3(LN_LV_SCAN_THREADS), 0, st, fgcnt, (long long)L.nblk, G);
+    LN_LAUNCH("k_lovasz_dot", k_lovasz_dot, tiles, thr, 0, st, keys[0], pay[0], fgcnt, G, log_probs, n, n0, classes, L.nblk, ignore_index,
+              reduction, float(B), partial, dloss_dlogp);
+    LN_LAUNCH("k_lovasz_finish", k_lovasz_finish, dim3(B), thr, 0, st, partial, G, L.nblk, classes, ignore_index, reduction,
+              per_cloud_form ? cloud : loss, per_class);
+    if (per_cloud_form)
+        LN_LAUNCH("k_lovasz_cloud_mean", k_lovasz_cloud_mean, dim3(1), thr, 0, st, cloud, (long long)B, loss, per_cloud);
+    return ln_check_launch(who);
+}
+}  // namespace
+
+extern "C" size_t ln_lovasz_workspace_bytes(long long n, int classes) { return ln_lv_layout(n, n, classes, false).bytes; }
+extern "C" size_t ln_lovasz_clouds_workspace_bytes(long long n, long long points_per_cloud, int classes) {
+    return ln_lv_layout(n, points_per_cloud, classes, true).bytes;
+}
+
+extern "C" int ln_lovasz_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index,
+                                 int reduction, void* workspace, size_t workspace_bytes, float* loss, float* per_class,
+                                 float* dloss_dlogp, void* stream) {
+    return ln_lv_forward("ln_lovasz_forward", false, log_probs, target, n, n, classes, ignore_index, reduction, workspace, workspace_bytes,
+                         loss, nullptr, per_class, dloss_dlogp, (hipStream_t)stream);
+}
+
+extern "C" int ln_lovasz_forward_clouds(const float* log_probs, const long long* target, long long n, long long points_per_cloud,
+                                        int classes, long long ignore_index, int reduction, void* workspace, size_t workspace_bytes,
+                                        float* loss, float* per_cloud, float* per_class, float* dloss_dlogp, void* stream) {
+    return ln_lv_forward("ln_lovasz_forward_clouds", true, log_probs, target, n, points_per_cloud, classes, ignore_index, reduction, workspace,
+                         workspace_bytes, loss, per_cloud, per_class, dloss_dlogp, (hipStream_t)stream);
 }
 
 extern "C" int ln_lovasz_backward(const float* dloss_dlogp, const float* grad_loss, long long n, int classes, float* grad_log_probs,

@@ -7,6 +7,10 @@ along that order; classes absent from the cloud and the ignore class are skipped
 processed at once with no host synchronisation — the reference loops over classes and reads one scalar per class back to
 the host.  With FUSED_LOVASZ set, float32 CUDA inputs take the HIP kernels of csrc/ln_lovasz.hip; everything else, and everything while
 the flag is off, the torch form ([C, N] sort / cumsum).
+
+A batch of clouds in one lattice (Lattice.set_cloud_batch) hands its log-probabilities over as one cloud-major [N, C] matrix.  The
+reference's step and its validation work on ONE cloud: LovaszSoftmax(points_per_cloud=) and Scores.accumulate_scores(points_per_cloud=)
+take the loss and the counts per cloud (Berman's per_image=True), so that a batched step is the mean of the clouds' reference steps.
 """
 from __future__ import annotations
 
@@ -19,9 +23,18 @@ __all__ = ["GeneralizedSoftDiceLoss", "LovaszSoftmax", "Scores", "nll_loss_gathe
 
 _NO_LABEL = -(1 << 62)  # "no ignore_index": a value no label takes
 FUSED_NLL = True
+FUSED_IOU_COUNTS = True  # Scores.accumulate_scores(points_per_cloud=): integer-exact either way, and the torch form of one cloud synchronises
 FUSED_LOVASZ = False  # off until tools/bench_losses.py has shown the kernels below the torch form on an MI355X
 _LOVASZ_MAX_CLASSES = 1024  # limits of ln_lovasz_forward (include/latticenet_hip.h)
 _LOVASZ_MAX_ELEMENTS = 1 << 31
+_LOVASZ_MAX_CLOUDS = 65535  # of ln_lovasz_forward_clouds and ln_iou_counts_clouds
+
+
+def _lovasz_fused_ok(inputs, targets) -> bool:
+    """The inputs LovaszSoftmax hands to the kernels (reduction "mean" or "sum"), while FUSED_LOVASZ is set."""
+    return FUSED_LOVASZ and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.is_contiguous() and targets.is_cuda and \
+        targets.dtype == torch.int64 and targets.numel() == inputs.shape[0] and inputs.shape[0] >= 1 and \
+        1 <= inputs.shape[1] <= _LOVASZ_MAX_CLASSES and inputs.numel() < _LOVASZ_MAX_ELEMENTS
 
 
 class _NllFunction(torch.autograd.Function):
@@ -85,6 +98,30 @@ class _LovaszFunction(torch.autograd.Function):
         return grad, None, None, None
 
 
+class _LovaszCloudsFunction(torch.autograd.Function):
+    """ln_lovasz_forward_clouds: the same kernels over (cloud, class) segments, the mean over the clouds; d loss / d log_probs carries
+    the 1 / clouds, so the backward is that of _LovaszFunction."""
+
+    @staticmethod
+    def forward(ctx, log_probs, target, ignore_index, reduction, points_per_cloud):
+        from . import _lib
+        lib = _lib.load()
+        n, c = log_probs.shape
+        dev = log_probs.device
+        ws = torch.empty((lib.ln_lovasz_clouds_workspace_bytes(n, points_per_cloud, c),), dtype=torch.uint8, device=dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        dloss = torch.empty((n, c), dtype=torch.float32, device=dev)
+        _lib.check(lib.ln_lovasz_forward_clouds(_lib.ptr(log_probs), _lib.ptr(target), n, points_per_cloud, c, ignore_index, reduction,
+                                                _lib.ptr(ws), ws.numel(), _lib.ptr(loss), None, None, _lib.ptr(dloss), _lib.stream_ptr(dev)),
+                   "ln_lovasz_forward_clouds")
+        ctx.save_for_backward(dloss)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        return _LovaszFunction.backward(ctx, grad_loss) + (None,)
+
+
 def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=None) -> torch.Tensor:
     """Mean negative log-likelihood, as torch.nn.NLLLoss(ignore_index=...) (ln_train.py:130).  float32 CUDA inputs take the fused
     kernels; everything else is written as gather + masked mean (torch's nll_loss kernels reduce a [120 k, C] input in a single
@@ -127,19 +164,84 @@ class GeneralizedSoftDiceLoss(torch.nn.Module):
         return loss_per_class.sum() / nr_classes
 
 
+def _lovasz_per_class(errors_sorted, order, onehot):
+    """Class-major rows along the last axis ([C, N], or [B, C, n0] for a batch of clouds): the Jaccard gradient along each row's sorted
+    order dotted with the sorted errors, and the rows' foreground counts."""
+    fg_sorted = torch.gather(onehot, -1, order)
+    # gradient of the Jaccard loss along the sorted order: J_k = 1 - (G - cumsum fg) / (G + cumsum (1 - fg))
+    gts = fg_sorted.sum(-1, keepdim=True)
+    intersection = gts - fg_sorted.cumsum(-1)
+    union = gts + (1.0 - fg_sorted).cumsum(-1)
+    jaccard = 1.0 - intersection / union
+    grad = torch.cat((jaccard[..., :1], jaccard[..., 1:] - jaccard[..., :-1]), -1)
+    return (errors_sorted * grad).sum(-1), gts.squeeze(-1)
+
+
 class LovaszSoftmax(torch.nn.Module):
-    def __init__(self, ignore_index, reduction: str = "mean"):
+    """points_per_cloud=None: the loss of one cloud, the reference's.  points_per_cloud=n0 (what Lattice.points_per_cloud() returns for
+    a batch set up with set_cloud_batch; reduction "mean" or "sum"): the [N, C] input is a cloud-major batch of ceil(N / n0) clouds of
+    n0 points, the last possibly shorter, and the result is the MEAN OVER THE CLOUDS of each cloud's own loss — its own sort, its own
+    Jaccard index, its own set of present classes.  The kernels (FUSED_LOVASZ) take at most 65 535 clouds, the limit of
+    ln_lovasz_forward_clouds; a batch of more clouds is computed by the torch form, like every other input the kernels do not take."""
+
+    def __init__(self, ignore_index, reduction: str = "mean", points_per_cloud=None):
         super().__init__()
+        if points_per_cloud is not None:
+            if reduction not in ("mean", "sum"):
+                raise ValueError("LovaszSoftmax(points_per_cloud=) needs reduction 'mean' or 'sum': the classes present differ from cloud to cloud")
+            if int(points_per_cloud) < 1:
+                raise ValueError("points_per_cloud >= 1")
+            points_per_cloud = int(points_per_cloud)
         self.ignore_index = ignore_index
         self.reduction = reduction
+        self.points_per_cloud = points_per_cloud
+
+    def _keep(self, c, device):
+        """[C] mask of the classes that may count, or None (no host scalar: safe inside a stream capture)"""
+        if self.ignore_index is not None and 0 <= int(self.ignore_index) < c:
+            return torch.arange(c, device=device) != int(self.ignore_index)
+        return None
+
+    def _forward_clouds_torch(self, inputs, targets):
+        """The [C, N] form batched as [B_full, C, n0] plus a [1, C, rest] term for a shorter last cloud; shapes depend on sizes only."""
+        n, c = inputs.shape
+        n0 = min(self.points_per_cloud, max(n, 1))
+        full, rest = divmod(n, n0)
+        clouds = full + (1 if rest else 0)
+        if clouds == 0:
+            return inputs.sum() * 0.0
+        keep = self._keep(c, inputs.device)
+        total = None
+        for lo, hi, b in ((0, full * n0, full), (full * n0, n, 1 if rest else 0)):
+            if b == 0:
+                continue
+            probs = inputs[lo:hi].exp().reshape(b, (hi - lo) // b, c).transpose(1, 2)  # [b, C, points]
+            onehot = torch.zeros((hi - lo, c), dtype=probs.dtype, device=probs.device).scatter_(1, targets[lo:hi].clamp(0, c - 1).unsqueeze(1), 1.0)
+            onehot = onehot.reshape(b, (hi - lo) // b, c).transpose(1, 2).contiguous()
+            errors_sorted, order = torch.sort((onehot - probs).abs(), dim=2, descending=True)
+            per_class, gts = _lovasz_per_class(errors_sorted, order, onehot)
+            present = gts > 0
+            if keep is not None:
+                present = present & keep
+            per_cloud = (per_class * present).sum(1)
+            if self.reduction == "mean":
+                per_cloud = per_cloud / present.sum(1).clamp(min=1)
+            total = per_cloud.sum() if total is None else total + per_cloud.sum()
+        return total / clouds
 
     def forward(self, inputs, targets):
         """inputs: log-probabilities [N, C] (the model's log-softmax, ln_train.py:156); targets: int64 [N]."""
         if inputs.dim() != 2:
             raise ValueError("LovaszSoftmax expects [N, C] log-probabilities")
-        if FUSED_LOVASZ and self.reduction in ("mean", "sum") and inputs.is_cuda and inputs.dtype == torch.float32 and \
-                inputs.is_contiguous() and targets.is_cuda and targets.dtype == torch.int64 and targets.numel() == inputs.shape[0] and \
-                inputs.shape[0] >= 1 and 1 <= inputs.shape[1] <= _LOVASZ_MAX_CLASSES and inputs.numel() < _LOVASZ_MAX_ELEMENTS:
+        if self.points_per_cloud is not None:
+            if self.reduction not in ("mean", "sum"):  # (also when it was reassigned after construction)
+                raise ValueError("LovaszSoftmax(points_per_cloud=) needs reduction 'mean' or 'sum'")
+            if _lovasz_fused_ok(inputs, targets) and -(-inputs.shape[0] // self.points_per_cloud) <= _LOVASZ_MAX_CLOUDS:
+                return _LovaszCloudsFunction.apply(inputs, targets.reshape(-1).contiguous(),
+                                                   _NO_LABEL if self.ignore_index is None else int(self.ignore_index),
+                                                   0 if self.reduction == "mean" else 1, self.points_per_cloud)
+            return self._forward_clouds_torch(inputs, targets.reshape(-1))
+        if self.reduction in ("mean", "sum") and _lovasz_fused_ok(inputs, targets):
             # equal errors are ordered by point index and the Jaccard gradient is taken in closed form (csrc/ln_lovasz.hip)
             return _LovaszFunction.apply(inputs, targets.reshape(-1).contiguous(), _NO_LABEL if self.ignore_index is None else int(self.ignore_index),
                                          0 if self.reduction == "mean" else 1)
@@ -159,17 +261,10 @@ class LovaszSoftmax(torch.nn.Module):
             order = torch.stack([p[1] for p in parts])
         else:
             errors_sorted, order = torch.sort(errors, dim=1, descending=True)
-        fg_sorted = torch.gather(onehot, 1, order)
-        # gradient of the Jaccard loss along the sorted order: J_k = 1 - (G - cumsum fg) / (G + cumsum (1 - fg))
-        gts = fg_sorted.sum(1, keepdim=True)
-        intersection = gts - fg_sorted.cumsum(1)
-        union = gts + (1.0 - fg_sorted).cumsum(1)
-        jaccard = 1.0 - intersection / union
-        grad = torch.cat((jaccard[:, :1], jaccard[:, 1:] - jaccard[:, :-1]), 1)
-        per_class = (errors_sorted * grad).sum(1)
-        present = gts.squeeze(1) > 0
-        if self.ignore_index is not None and 0 <= int(self.ignore_index) < c:
-            keep = torch.arange(c, device=probs.device) != int(self.ignore_index)  # (no host scalar: safe inside a stream capture)
+        per_class, gts = _lovasz_per_class(errors_sorted, order, onehot)
+        present = gts > 0
+        keep = self._keep(c, probs.device)
+        if keep is not None:
             present = present & keep
         if self.reduction == "none":
             return per_class[present]
@@ -196,14 +291,21 @@ class Scores:
         self.union_per_class = None
         self.nr_classes = None
 
-    def accumulate_scores(self, pred_softmax, gt, unlabeled_idx):
+    def accumulate_scores(self, pred_softmax, gt, unlabeled_idx, points_per_cloud=None):
+        """points_per_cloud=None: one cloud.  points_per_cloud=n0 (Lattice.points_per_cloud() of a batch set up with set_cloud_batch):
+        the rows are a cloud-major batch of ceil(N / n0) clouds and every cloud is scored on its own — only the classes present in
+        THAT cloud's ground truth count there, as when the clouds are handed over one by one.  No host synchronisation on float32
+        CUDA scores (ln_iou_counts_clouds): usable inside a captured step."""
         c = pred_softmax.shape[1]
-        pred = pred_softmax.detach().argmax(1)
         gt = gt.detach().reshape(-1)
         if self.intersection_per_class is None:
             self.nr_classes = c
             self.intersection_per_class = torch.zeros(c, dtype=torch.int64, device=gt.device)
             self.union_per_class = torch.zeros(c, dtype=torch.int64, device=gt.device)
+        if points_per_cloud is not None:
+            self._accumulate_clouds(pred_softmax.detach(), gt, unlabeled_idx, int(points_per_cloud))
+            return
+        pred = pred_softmax.detach().argmax(1)
         hit = torch.bincount(gt[pred == gt], minlength=c)[:c]
         n_gt = torch.bincount(gt.clamp(0, c - 1), minlength=c)[:c]
         n_pred = torch.bincount(pred, minlength=c)[:c]
@@ -212,6 +314,41 @@ class Scores:
             in_gt[int(unlabeled_idx)] = False
         self.intersection_per_class += hit * in_gt
         self.union_per_class += (n_gt + n_pred - hit) * in_gt
+
+    def _accumulate_clouds(self, scores, gt, unlabeled_idx, n0):
+        if n0 < 1:
+            raise ValueError("points_per_cloud >= 1")
+        n, c = scores.shape
+        clouds = -(-n // n0)
+        if FUSED_IOU_COUNTS and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and gt.is_cuda and \
+                gt.dtype == torch.int64 and gt.numel() == n and 1 <= c <= _LOVASZ_MAX_CLASSES and scores.numel() < _LOVASZ_MAX_ELEMENTS and \
+                clouds <= _LOVASZ_MAX_CLOUDS and self.intersection_per_class.is_cuda:
+            from . import _lib
+            lib = _lib.load()
+            scores, gt = scores.contiguous(), gt.contiguous()
+            ws = torch.empty((lib.ln_iou_counts_clouds_workspace_bytes(n, n0, c),), dtype=torch.uint8, device=scores.device)
+            _lib.check(lib.ln_iou_counts_clouds(_lib.ptr(scores), _lib.ptr(gt), n, n0, c, -1 if unlabeled_idx is None else int(unlabeled_idx),
+                                                _lib.ptr(ws), ws.numel(), _lib.ptr(self.intersection_per_class), _lib.ptr(self.union_per_class),
+                                                _lib.stream_ptr(scores.device)), "ln_iou_counts_clouds")
+            return
+        if n == 0:
+            return
+        # per-cloud histograms through the offset label cloud * C + class; a miss goes to a bin of its own (no boolean-mask index)
+        pred = scores.argmax(1)
+        base = (torch.arange(n, device=gt.device) // n0) * c
+        ones = torch.ones(n, dtype=torch.int64, device=gt.device)
+
+        def hist(idx):
+            return torch.zeros(clouds * c + 1, dtype=torch.int64, device=gt.device).scatter_add_(0, idx, ones)[:clouds * c].view(clouds, c)
+
+        hit = hist(torch.where(pred == gt, base + pred, torch.full_like(base, clouds * c)))
+        n_gt = hist(base + gt.clamp(0, c - 1))
+        n_pred = hist(base + pred)
+        in_gt = n_gt > 0
+        if unlabeled_idx is not None and 0 <= int(unlabeled_idx) < c:
+            in_gt = in_gt & (torch.arange(c, device=gt.device) != int(unlabeled_idx))
+        self.intersection_per_class += (hit * in_gt).sum(0)
+        self.union_per_class += ((n_gt + n_pred - hit) * in_gt).sum(0)
 
     def all_reduce(self, dist):
         if dist is not None and self.intersection_per_class is not None:
