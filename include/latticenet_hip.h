@@ -647,6 +647,33 @@ int ln_iou_counts_clouds(const float* scores, const long long* target, long long
                          long long unlabeled_index, void* workspace, size_t workspace_bytes, long long* intersection, long long* union_,
                          void* stream);
 
+/* Generalized soft Dice loss of the training loop (ln_train.py:127, diceloss.py:172-209) over log_probs [n, classes] float and target
+ * [n] int64, one cloud or PER CLOUD of a cloud-major batch (clouds as ln_lovasz_forward_clouds defines them: cloud b owns rows
+ * [b n0, min((b + 1) n0, n)) with n0 = points_per_cloud, B = ceil(n / n0), the last one possibly shorter; points_per_cloud >= n is one
+ * cloud).  Per cloud, with p = exp(log_probs) and w_c = 0 for c == ignore_index (pass a value no class takes, e.g. LLONG_MIN, for none),
+ * else 1:  I_c = sum_i p_ic [y_i = c], S_c = sum_i p_ic, G_c = #{y_i = c}, D_c = S_c + G_c + 1e-6, the cloud's loss =
+ * sum_c w_c (1 - 2 I_c / D_c) / classes.  Points labelled ignore_index still count in S of every class, the division is by all
+ * classes, a class absent from the cloud contributes w_c / classes.  A LABEL OUTSIDE [0, classes) BELONGS TO NO CLASS: its point
+ * counts in S only (the torch form faults on such a label).
+ * loss[0] = the mean over the clouds of each cloud's loss, the clouds added in a fixed order (strided over 256 threads in series, then
+ * the fixed tree of a workgroup).  per_cloud [B] (may be NULL): the clouds' losses.  stats [B, 3, classes] (may be NULL): I, S and G as
+ * float.  coef [B, 2, classes]: a_c = 2 w_c / (classes D_c) / B and b_c = a_c I_c / D_c, what the backward needs.  per_cloud[b] and
+ * stats[b] are what the call gives on cloud b's rows alone, bit for bit: a cloud is cut into tiles by its own length.
+ * ln_dice_backward (one elementwise launch) writes every element of grad_log_probs [n, classes]:
+ * -grad_loss[0] p_ic (a_c [y_i = c] - b_c) with the coefficients of the point's cloud; the caller does not zero the buffer; an entry
+ * with log_probs = -inf gets 0.  Called with the sizes of the forward call.
+ * Limits (LN_ERR_ARG otherwise, nothing launched or written): points_per_cloud >= 1, n >= 0, 1 <= classes <= 1024, n * classes < 2^31,
+ * B <= 65535 (the cloud is the y coordinate of the grid), no null buffer but the optional ones, a workspace of ln_dice_workspace_bytes
+ * (a pure host function, total; at most 24 bytes per (point, class) and 16 per (cloud, class)).  n == 0: ln_dice_forward sets loss to 0,
+ * ln_dice_backward launches nothing.  Two launches forward, one backward; no host synchronisation, no allocation, no float atomics:
+ * safe inside a stream capture, bitwise reproducible.  Rows that hold a NaN are not held to any rule. */
+size_t ln_dice_workspace_bytes(long long n, long long points_per_cloud, int classes);
+int ln_dice_forward(const float* log_probs, const long long* target, long long n, long long points_per_cloud, int classes,
+                    long long ignore_index, void* workspace, size_t workspace_bytes, float* loss, float* per_cloud, float* stats, float* coef,
+                    void* stream);
+int ln_dice_backward(const float* log_probs, const long long* target, const float* coef, const float* grad_loss, long long n,
+                     long long points_per_cloud, int classes, float* grad_log_probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

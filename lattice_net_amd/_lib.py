@@ -157,6 +157,9 @@ SIGNATURES = {
     "ln_lovasz_forward_clouds": (_i, [_vp, _vp, _ll, _ll, _i, _ll, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ln_iou_counts_clouds_workspace_bytes": (_sz, [_ll, _ll, _i]),
     "ln_iou_counts_clouds": (_i, [_vp, _vp, _ll, _ll, _i, _ll, _vp, _sz, _vp, _vp, _vp]),
+    "ln_dice_workspace_bytes": (_sz, [_ll, _ll, _i]),
+    "ln_dice_forward": (_i, [_vp, _vp, _ll, _ll, _i, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ln_dice_backward": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _i, _vp, _vp]),
     "ln_max_centre_forward": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp]),
     "ln_max_centre_backward_workspace_bytes": (_sz, [_ll, _i, _i]),
     "ln_max_centre_backward": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _sz, _vp]),

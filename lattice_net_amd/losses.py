@@ -25,6 +25,7 @@ _NO_LABEL = -(1 << 62)  # "no ignore_index": a value no label takes
 FUSED_NLL = True
 FUSED_IOU_COUNTS = True  # Scores.accumulate_scores(points_per_cloud=): integer-exact either way, and the torch form of one cloud synchronises
 FUSED_LOVASZ = False  # off until tools/bench_losses.py has shown the kernels below the torch form on an MI355X
+FUSED_DICE = True  # by the rule FUSED_LOVASZ states: tools/bench_losses.py on an MI355X has csrc/ln_dice.hip below the torch form, one cloud and per cloud
 _LOVASZ_MAX_CLASSES = 1024  # limits of ln_lovasz_forward (include/latticenet_hip.h)
 _LOVASZ_MAX_ELEMENTS = 1 << 31
 _LOVASZ_MAX_CLOUDS = 65535  # of ln_lovasz_forward_clouds and ln_iou_counts_clouds
@@ -32,9 +33,18 @@ _LOVASZ_MAX_CLOUDS = 65535  # of ln_lovasz_forward_clouds and ln_iou_counts_clou
 
 def _lovasz_fused_ok(inputs, targets) -> bool:
     """The inputs LovaszSoftmax hands to the kernels (reduction "mean" or "sum"), while FUSED_LOVASZ is set."""
-    return FUSED_LOVASZ and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.is_contiguous() and targets.is_cuda and \
+    return FUSED_LOVASZ and _kernel_inputs(inputs, targets)
+
+
+def _kernel_inputs(inputs, targets) -> bool:
+    return inputs.is_cuda and inputs.dtype == torch.float32 and inputs.is_contiguous() and targets.is_cuda and \
         targets.dtype == torch.int64 and targets.numel() == inputs.shape[0] and inputs.shape[0] >= 1 and \
         1 <= inputs.shape[1] <= _LOVASZ_MAX_CLASSES and inputs.numel() < _LOVASZ_MAX_ELEMENTS
+
+
+def _dice_fused_ok(inputs, targets) -> bool:
+    """The inputs GeneralizedSoftDiceLoss hands to the kernels (the limits of ln_dice_forward are the Lovasz ones), while FUSED_DICE is set."""
+    return FUSED_DICE and inputs.dim() == 2 and _kernel_inputs(inputs, targets)
 
 
 class _NllFunction(torch.autograd.Function):
@@ -122,6 +132,38 @@ class _LovaszCloudsFunction(torch.autograd.Function):
         return _LovaszFunction.backward(ctx, grad_loss) + (None,)
 
 
+class _DiceFunction(torch.autograd.Function):
+    """csrc/ln_dice.hip: two launches forward (per-tile partial sums of I, S, G in a fixed order, one finishing workgroup that leaves
+    the coefficients a, b per (cloud, class)), one backward that writes the whole [n, C] gradient.  points_per_cloud >= n: one cloud."""
+
+    @staticmethod
+    def forward(ctx, log_probs, target, ignore_index, points_per_cloud):
+        from . import _lib
+        lib = _lib.load()
+        n, c = log_probs.shape
+        dev = log_probs.device
+        clouds = -(-n // points_per_cloud)
+        ws = torch.empty((lib.ln_dice_workspace_bytes(n, points_per_cloud, c),), dtype=torch.uint8, device=dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        coef = torch.empty((clouds, 2, c), dtype=torch.float32, device=dev)
+        _lib.check(lib.ln_dice_forward(_lib.ptr(log_probs), _lib.ptr(target), n, points_per_cloud, c, ignore_index, _lib.ptr(ws), ws.numel(),
+                                       _lib.ptr(loss), None, None, _lib.ptr(coef), _lib.stream_ptr(dev)), "ln_dice_forward")
+        ctx.save_for_backward(log_probs, target, coef)
+        ctx.points_per_cloud = points_per_cloud
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        from . import _lib
+        log_probs, target, coef = ctx.saved_tensors
+        n, c = log_probs.shape
+        g = grad_loss.contiguous().float()
+        grad = torch.empty_like(log_probs)
+        _lib.check(_lib.load().ln_dice_backward(_lib.ptr(log_probs), _lib.ptr(target), _lib.ptr(coef), _lib.ptr(g), n, ctx.points_per_cloud, c,
+                                                _lib.ptr(grad), _lib.stream_ptr(g.device)), "ln_dice_backward")
+        return grad, None, None, None
+
+
 def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=None) -> torch.Tensor:
     """Mean negative log-likelihood, as torch.nn.NLLLoss(ignore_index=...) (ln_train.py:130).  float32 CUDA inputs take the fused
     kernels; everything else is written as gather + masked mean (torch's nll_loss kernels reduce a [120 k, C] input in a single
@@ -142,17 +184,62 @@ class GeneralizedSoftDiceLoss(torch.nn.Module):
     """The alternative to Lovasz-Softmax that ln_train.py:127 keeps at hand (reference latticenet_py/lattice/diceloss.py:172-209):
     with p = exp(log_probs) [N, C] and labels [N], per class  dice_c = 2 sum_i p_ic [y_i = c] / (sum_i p_ic + #{y_i = c} + 1e-6);
     loss = sum_c w_c (1 - dice_c) / C with w = 1 except w[ignore_index] = 0 (the division keeps all C classes, as there).
-    No one-hot matrix is built: the intersection is a gather + index_add over the labels."""
+    No one-hot matrix is built: the intersection is a gather + index_add over the labels.
 
-    def __init__(self, p=1, smooth=1, reduction="mean", weight=1, ignore_index=None):
+    points_per_cloud=None: the loss of one cloud, the reference's.  points_per_cloud=n0 (what Lattice.points_per_cloud() returns for a
+    batch set up with set_cloud_batch): the [N, C] input is a cloud-major batch of ceil(N / n0) clouds of n0 points, the last possibly
+    shorter, and the result is the MEAN OVER THE CLOUDS of each cloud's own loss (a ratio of sums: not the loss of the whole batch).
+    With FUSED_DICE set, float32 CUDA inputs within the limits of ln_dice_forward take the kernels of csrc/ln_dice.hip (bitwise
+    reproducible; a label outside [0, C) belongs to no class there); everything else, and everything while the flag is off, the torch
+    form, which faults on such a label as the reference does."""
+
+    def __init__(self, p=1, smooth=1, reduction="mean", weight=1, ignore_index=None, points_per_cloud=None):
         super().__init__()
         self.p, self.smooth, self.reduction = p, smooth, reduction  # accepted and unused, as in the reference
         self.ignore_index = ignore_index
+        if points_per_cloud is not None:
+            if int(points_per_cloud) < 1:
+                raise ValueError("points_per_cloud >= 1")
+            points_per_cloud = int(points_per_cloud)
+        self.points_per_cloud = points_per_cloud
+
+    def _forward_clouds_torch(self, output, target):
+        """The single-cloud form batched as [B_full, C, n0] plus a [1, C, rest] term for a shorter last cloud; shapes depend on sizes
+        only and nothing is read back: runs on the CPU and inside a stream capture."""
+        n, c = output.shape
+        n0 = min(self.points_per_cloud, max(n, 1))
+        full, rest = divmod(n, n0)
+        clouds = full + (1 if rest else 0)
+        if clouds == 0:
+            return output.sum() * 0.0
+        total = None
+        for lo, hi, b in ((0, full * n0, full), (full * n0, n, 1 if rest else 0)):
+            if b == 0:
+                continue
+            probs = output[lo:hi].exp().reshape(b, (hi - lo) // b, c).transpose(1, 2)  # [b, C, points]
+            labels = target[lo:hi].reshape(b, 1, (hi - lo) // b)
+            picked = probs.gather(1, labels).squeeze(1)  # [b, points]
+            intersection = torch.zeros((b, c), dtype=probs.dtype, device=probs.device).scatter_add_(1, labels.squeeze(1), picked)
+            counts = torch.zeros((b, c), dtype=probs.dtype, device=probs.device).scatter_add_(1, labels.squeeze(1), torch.ones_like(picked))
+            loss_per_class = 1.0 - 2.0 * intersection / (probs.sum(2) + counts + 1e-6)
+            if self.ignore_index is not None:
+                loss_per_class = loss_per_class * (torch.arange(c, device=probs.device) != int(self.ignore_index)).to(probs.dtype)
+            per_cloud = loss_per_class.sum(1) / c
+            total = per_cloud.sum() if total is None else total + per_cloud.sum()
+        return total / clouds
 
     def forward(self, output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        target = target.reshape(-1)
+        if _dice_fused_ok(output, target) and (self.points_per_cloud is None or
+                                               -(-output.shape[0] // self.points_per_cloud) <= _LOVASZ_MAX_CLOUDS):
+            return _DiceFunction.apply(output, target.contiguous(), _NO_LABEL if self.ignore_index is None else int(self.ignore_index),
+                                       output.shape[0] if self.points_per_cloud is None else self.points_per_cloud)
+        if self.points_per_cloud is not None:
+            if output.dim() != 2:
+                raise ValueError("GeneralizedSoftDiceLoss(points_per_cloud=) expects [N, C] log-probabilities")
+            return self._forward_clouds_torch(output, target)
         nr_classes = output.shape[1]
         probs = output.exp()
-        target = target.reshape(-1)
         picked = probs.gather(1, target.unsqueeze(1)).squeeze(1)
         intersection = torch.zeros(nr_classes, dtype=probs.dtype, device=probs.device).index_add_(0, target, picked)
         counts = torch.zeros(nr_classes, dtype=probs.dtype, device=probs.device).index_add_(0, target, torch.ones_like(picked))

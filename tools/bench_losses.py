@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time of the training losses on a [120k, 20] prediction: NLL, Lovasz-Softmax (HIP kernels, and the torch form with
-losses.FUSED_LOVASZ off), soft Dice; forward + backward.  Then the same matrix as a batch of 16 clouds x 7 500 points: the per-cloud
+losses.FUSED_LOVASZ off), soft Dice (HIP kernels, and the torch form with losses.FUSED_DICE off; then per cloud); forward + backward.  Then the same matrix as a batch of 16 clouds x 7 500 points: the per-cloud
 loss (ln_lovasz_forward_clouds against 16 calls of ln_lovasz_forward and against the batched torch form) and the per-cloud IoU
 counts (ln_iou_counts_clouds against Scores.accumulate_scores cloud by cloud)."""
 import os, sys, time
@@ -37,7 +37,18 @@ def five(fn):
 print(f"log_softmax + lovasz (HIP kernels) {five(lambda: run_lovasz(True))}")
 print(f"log_softmax + lovasz (torch form)  {five(lambda: run_lovasz(False))}")
 losses.FUSED_LOVASZ = default
-print(f"log_softmax + dice  {run(lambda lp: dice(lp, target)):6.3f} ms")
+# soft Dice, one cloud and 16 clouds x 7 500 points: FUSED_DICE goes on only when the kernels' median is below the torch form's fastest
+# run in BOTH pairs
+def run_dice(fused, loss):
+    losses.FUSED_DICE = fused
+    return run(lambda lp: loss(lp, target))
+default_dice = losses.FUSED_DICE
+dice_clouds = GeneralizedSoftDiceLoss(ignore_index=0, points_per_cloud=7500)
+print(f"log_softmax + dice (torch form)                          {five(lambda: run_dice(False, dice))}")
+print(f"log_softmax + dice (HIP kernels)                         {five(lambda: run_dice(True, dice))}")
+print(f"16 x 7500: log_softmax + dice per cloud (torch form)     {five(lambda: run_dice(False, dice_clouds))}")
+print(f"16 x 7500: log_softmax + dice per cloud (HIP kernels)    {five(lambda: run_dice(True, dice_clouds))}")
+losses.FUSED_DICE = default_dice
 
 # ---- a batch of clouds: 16 clouds x 7 500 points, the per-cloud loss and the per-cloud IoU counts -----------------------------------
 # (each line: five(), as above)
