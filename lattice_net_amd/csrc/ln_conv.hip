@@ -24,7 +24,7 @@
 #include "ln_common.h"
 #include <stdlib.h>
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
+#include "ln_bf16x3.h"
 
 #include "ln_conv_plan.h"
 #include <type_traits>
@@ -185,33 +185,8 @@ __global__ void __launch_bounds__(256) LN_CONV_WAVES_ATTR
 }
 
 // ------------------------------------------------------------------------------------------
-// The per-slot gather-GEMM on the bf16 matrix cores with exactly-split operands ("bf16x3"), for lattices of >= LN_CONV_B3_MIN_ROWS vertices.
-// fp32-input MFMA runs at the fp32 VECTOR rate on gfx950 (32 cycles per 16x16x4): at ScanNet / SemanticKITTI shapes the kernel
-// above sits at 50-80 % of that peak.  Here a = a1 + a2 + a3 EXACTLY, each part the top 16 bits of what is left (bf16 has fp32's
-// exponent range, so no scaling; 3 x 8 significant bits = fp32's 24), the same for the filter, and a*b is accumulated in fp32 as
-// the six products of total order <= 4: a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1 (what is dropped is < 2^-23 |ab|).  One
-// v_mfma_f32_16x16x32_bf16 contracts 32 channels in ~17 cycles, so a slot costs 6 V/32 NT of those instead of V/4 NT of 32
-// cycles: 2.5x less matrix time, for ~8 bit operations per gathered value.  The filter bank is split once per call
-// (k_conv_split_bank) into fragment order, so staging a slot is a straight 16-byte copy.
-// Lane (i, q) holds its quarter of the gathered row, V/4 contiguous channels: MFMA step s takes channels [8s, 8s + 8) of the
-// quarter as the A fragment of k-group q, i.e. the contraction order inside a slot is permuted; the bank uses the same order.
+// The bf16x3 kernels.  Their arithmetic (exact three-way split, two parts per dword, six products in a pinned order) is ln_bf16x3.h's.
 // ------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// x = hi + mid + lo exactly, each the top 16 bits of the remainder; returned as raw bf16 bit patterns in the HIGH half-words
-// (`lo` comes back UNMASKED — its low half-word is whatever is left below the third part: every user takes the high half-word only, by a
-// 16-bit shift or through ln_pack_hi)
-__device__ __forceinline__ void ln_split3_bits(float x, unsigned int& hi, unsigned int& mid, unsigned int& lo) {
-    hi = __float_as_uint(x) & 0xFFFF0000u;
-    const float r1 = x - __uint_as_float(hi);
-    mid = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(mid);
-    lo = __float_as_uint(r2);
-}
-// two bf16 per dword: the HIGH half-word of `a` in the low half, the high half-word of `b` in the high half — one v_perm_b32 (round 6;
-// before: shift + or on masked words, 3 more vector-ALU instructions per pair of split values)
-__device__ __forceinline__ unsigned int ln_pack_hi(unsigned int a, unsigned int b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-
 // One block of the slab sum (k_reduce_slabs4 below): 64 outputs as 16 float4 columns x 16 slab groups (every thread has its
 // <= ceil(nslabs / 16) float4 loads in flight at once), combined through LDS in a fixed order.  total % 64 == 0.
 __device__ __forceinline__ void ln_reduce_slabs4_block(int vb, const float* __restrict__ partial, int nslabs, int total, float* __restrict__ out) {
@@ -291,7 +266,10 @@ __global__ void __launch_bounds__(256)
     dst[base + 2 * 64 * 8] = (unsigned short)(l >> 16);
 }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// FLIP reads slot e^1 of an un-flipped neighbour list (the centre slot E - 1 stays).
+template <bool FLIP>
+__device__ __forceinline__ int ln_slot_of(int e, int E) { return (FLIP && e < E - 1) ? (e ^ 1) : e; }
+
 #ifndef LN_CONV_B3_PIPE
 #define LN_CONV_B3_PIPE(V) ((V) <= 128)  // fragments read one chain ahead: +12 registers (the register estimate at the use decides: at 128 channels only with T = 3)
 #endif
@@ -537,7 +515,6 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(LN
 // Workgroup = 4 waves x 32 rows; 64 KB of LDS at 128 columns -> two workgroups per CU, whose barriers overlap.
 // Absent neighbours and rows past m read a zero row, so the DMA needs no predication.
 // ------------------------------------------------------------------------------------------
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 // One LDS-DMA wave-instruction (64 lanes x 16 bytes -> LDS bytes [lds_dst, lds_dst + 1024)), issued from inline asm so that hipcc
 // does not know an LDS write is pending: with the builtin it puts `s_waitcnt vmcnt(0)` in front of the next ds_read of ANY LDS
 // object, i.e. waits for the chunk just requested.  The kernel orders the data itself (counted vmcnt + barrier).  hipcc's own vmcnt
@@ -637,7 +614,7 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
         const size_t g0 = (size_t)blockIdx.x * R * E, g_end = (size_t)m * E;
         for (int x = tid; x < R * E; x += 64 * W) s_nbr[x] = (g0 + x < g_end) ? nbr[g0 + x] : -1;
     }
-    auto slot_of = [&](int e) -> int { return (FLIP && e < E - 1) ? (e ^ 1) : e; };
+    auto slot_of = [&](int e) -> int { return ln_slot_of<FLIP>(e, E); };
     // A piece j of a row tile covers its rows 8j .. 8j+7: lane -> (row 8j + (lane >> 3), position lane & 7); this wave requests
     // pieces ch * APW .. ch * APW + APW - 1
     const int a_row = lane >> 3;
@@ -691,22 +668,6 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
             for (int j2 = 0; j2 < 2; ++j2) araw[s][j2] = my_a[(s * 4 + h * 2 + j2) ^ a_sw];
     };
     bf16x8 ap[2][3];
-    auto split_step = [&](int s, bf16x8 (&dst)[2][3]) {
-        u32x4 p1, p2, p3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // x = hi + mid + lo with each part the top 16 bits of the remainder (ln_split3_bits), written out so that only the two
-            // masks the subtractions need are computed: the byte permutes below take the top half-words of x, r1 and r2 directly.
-            // Two bf16 per dword, the lower channel in the low half-word.
-            const float x0 = __uint_as_float(araw[s][j >> 1][(2 * j) & 3]), x1 = __uint_as_float(araw[s][j >> 1][(2 * j + 1) & 3]);
-            const float r10 = x0 - __uint_as_float(__float_as_uint(x0) & 0xFFFF0000u), r11 = x1 - __uint_as_float(__float_as_uint(x1) & 0xFFFF0000u);
-            const float r20 = r10 - __uint_as_float(__float_as_uint(r10) & 0xFFFF0000u), r21 = r11 - __uint_as_float(__float_as_uint(r11) & 0xFFFF0000u);
-            p1[j] = __builtin_amdgcn_perm(__float_as_uint(x1), __float_as_uint(x0), 0x07060302u);
-            p2[j] = __builtin_amdgcn_perm(__float_as_uint(r11), __float_as_uint(r10), 0x07060302u);
-            p3[j] = __builtin_amdgcn_perm(__float_as_uint(r21), __float_as_uint(r20), 0x07060302u);
-        }
-        dst[s][0] = __builtin_bit_cast(bf16x8, p1), dst[s][1] = __builtin_bit_cast(bf16x8, p2), dst[s][2] = __builtin_bit_cast(bf16x8, p3);
-    };
 
     // Software pipeline, per wave.  While the products of chunk t issue, the rows of chunk t + 1 (landed before the barrier of
     // iteration t) are read from LDS and split; and the products of a chunk's SECOND K-step are held back until the barrier of the
@@ -748,23 +709,14 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
         load_ids(2);
     }
     bf16x8 ap_b[2][3];
-    split_step(0, ap);
-    split_step(1, ap);
+    ln_split3_pack8_raw(araw[0], ap[0]);
+    ln_split3_pack8_raw(araw[1], ap[1]);
 #ifdef LN_STAMPS
     unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long wall0 = wall_clock64();
     unsigned t_prev = LN_R32_CYC();
 #endif
     u32x4 fb0[NTW][3], fb1[NTW][3];  // fragments of the first / second K-step
-    // products of K-step s of one chunk: the NTW accumulation chains advance together (product p of every column tile, then
-    // product p + 1); small terms first, the dominant product last
-    auto products = [&](bf16x8 (&a)[3], u32x4 (&f)[NTW][3]) {
-#define LN_R32_PRODUCT(PA, PB)                                                                                                        \
-    _Pragma("unroll") for (int nt = 0; nt < NTW; ++nt)                                                                                \
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], __builtin_bit_cast(bf16x8, f[nt][PB]), acc[nt], 0, 0, 0);
-        LN_R32_PRODUCT(2, 0) LN_R32_PRODUCT(0, 2) LN_R32_PRODUCT(1, 1) LN_R32_PRODUCT(1, 0) LN_R32_PRODUCT(0, 1) LN_R32_PRODUCT(0, 0)
-#undef LN_R32_PRODUCT
-    };
     // the walk's next three chunks, advanced once per iteration (no division in the loop); past the end they stay on the last chunk
     int w_e[3], w_kc[3];
 #pragma unroll
@@ -812,15 +764,15 @@ __global__ void __launch_bounds__(64 * RT * CH) __attribute__((amdgpu_waves_per_
         for (int nt = 0; nt < NTW; ++nt)
 #pragma unroll
             for (int x = 0; x < 3; ++x) fb1[nt][x] = sb[((NT + nt) * 3 + x) * 64];
-        products(cur[0], fb0);
+        ln_b3_mfma32(cur[0], fb0, acc);
         LN_R32_PHASE(4);  // first K-step's products issued
         requests(it, 0, NPIECES);
         load_ids_of_slot(w_e[2]);
         LN_R32_PHASE(5);  // requests issued
-        split_step(0, nxt);
-        products(cur[1], fb1);
+        ln_split3_pack8_raw(araw[0], nxt[0]);
+        ln_b3_mfma32(cur[1], fb1, acc);
         LN_R32_PHASE(6);  // second K-step's products issued
-        split_step(1, nxt);
+        ln_split3_pack8_raw(araw[1], nxt[1]);
         LN_R32_PHASE(7);  // next rows split
         advance(it);
     };
@@ -891,7 +843,7 @@ __global__ void __launch_bounds__(128 * RT) __attribute__((amdgpu_waves_per_eu((
         const size_t g0 = (size_t)blockIdx.x * R * E, g_end = (size_t)m * E;
         for (int x = tid; x < R * E; x += 64 * W) s_nbr[x] = (g0 + x < g_end) ? nbr[g0 + x] : -1;
     }
-    auto slot_of = [&](int e) -> int { return (FLIP && e < E - 1) ? (e ^ 1) : e; };
+    auto slot_of = [&](int e) -> int { return ln_slot_of<FLIP>(e, E); };
     const int a_row = lane >> 3;  // A piece j of a row tile = rows 8j .. 8j+7; this wave requests pieces 2 kh and 2 kh + 1
     const int* my_ids = s_nbr + (rt * 32 + kh * 16 + a_row) * E;
     const unsigned int lds_b = __builtin_amdgcn_readfirstlane(ln_lds_addr(s_b));
@@ -934,19 +886,6 @@ __global__ void __launch_bounds__(128 * RT) __attribute__((amdgpu_waves_per_eu((
 #pragma unroll
         for (int j2 = 0; j2 < 2; ++j2) araw[j2] = my_a[(kh * 4 + h * 2 + j2) ^ a_sw];
     };
-    auto split = [&](bf16x8 (&dst)[3]) {
-        u32x4 p1, p2, p3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float x0 = __uint_as_float(araw[j >> 1][(2 * j) & 3]), x1 = __uint_as_float(araw[j >> 1][(2 * j + 1) & 3]);
-            const float r10 = x0 - __uint_as_float(__float_as_uint(x0) & 0xFFFF0000u), r11 = x1 - __uint_as_float(__float_as_uint(x1) & 0xFFFF0000u);
-            const float r20 = r10 - __uint_as_float(__float_as_uint(r10) & 0xFFFF0000u), r21 = r11 - __uint_as_float(__float_as_uint(r11) & 0xFFFF0000u);
-            p1[j] = __builtin_amdgcn_perm(__float_as_uint(x1), __float_as_uint(x0), 0x07060302u);
-            p2[j] = __builtin_amdgcn_perm(__float_as_uint(r11), __float_as_uint(r10), 0x07060302u);
-            p3[j] = __builtin_amdgcn_perm(__float_as_uint(r21), __float_as_uint(r20), 0x07060302u);
-        }
-        dst[0] = __builtin_bit_cast(bf16x8, p1), dst[1] = __builtin_bit_cast(bf16x8, p2), dst[2] = __builtin_bit_cast(bf16x8, p3);
-    };
     // the walk's next three chunks (as in k_conv_rows32_b3)
     int w_e[3], w_kc[3];
 #pragma unroll
@@ -961,7 +900,7 @@ __global__ void __launch_bounds__(128 * RT) __attribute__((amdgpu_waves_per_eu((
             }
         }
     };
-    {   // a tile without any neighbour (past the real rows of a static-rows launch) writes zeros and leaves (see k_conv_rows32_b3)
+    {
         bool any = false;
         for (int x = tid; x < R * E; x += 64 * W) any |= s_nbr[x] >= 0;
         if (!__syncthreads_or(any)) {
@@ -984,7 +923,7 @@ __global__ void __launch_bounds__(128 * RT) __attribute__((amdgpu_waves_per_eu((
     read_a(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     bf16x8 ap[3], ap_b[3];
-    split(ap);
+    ln_split3_pack8_raw(araw, ap);
     auto iteration = [&](int it, bf16x8 (&cur)[3], bf16x8 (&nxt)[3]) {
         LN_R32_PHASE(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // bank chunk `it` and the rows of chunk it + 1 have landed ...
@@ -998,12 +937,7 @@ __global__ void __launch_bounds__(128 * RT) __attribute__((amdgpu_waves_per_eu((
             for (int x = 0; x < 3; ++x) fb[nt][x] = sb[(nt * 3 + x) * 64];
         read_a((it + 1) & 1);
         LN_R32_PHASE(3);
-        // the NT accumulation chains advance together; small terms first, the dominant product last
-#define LN_R32SK_PRODUCT(PA, PB)                                                                                                       \
-    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                                                  \
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur[PA], __builtin_bit_cast(bf16x8, fb[nt][PB]), acc[nt], 0, 0, 0);
-        LN_R32SK_PRODUCT(2, 0) LN_R32SK_PRODUCT(0, 2) LN_R32SK_PRODUCT(1, 1) LN_R32SK_PRODUCT(1, 0) LN_R32SK_PRODUCT(0, 1) LN_R32SK_PRODUCT(0, 0)
-#undef LN_R32SK_PRODUCT
+        ln_b3_mfma32(cur, fb, acc);
         LN_R32_PHASE(4);
         // requests: bank chunk it + 1, rows of chunk it + 2
 #pragma unroll
@@ -1012,7 +946,7 @@ __global__ void __launch_bounds__(128 * RT) __attribute__((amdgpu_waves_per_eu((
         for (int k = BPW; k < NPIECES; ++k) dma_piece(k, w_e[1], w_kc[1], it & 1);
         load_ids_of_slot(w_e[2]);
         LN_R32_PHASE(5);
-        split(nxt);
+        ln_split3_pack8_raw(araw, nxt);
         LN_R32_PHASE(7);
         advance(it);
     };
@@ -1269,7 +1203,7 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         const size_t g0 = (size_t)bx * (64 * T) * E, g_end = (size_t)m * E;
         for (int x = tid; x < 64 * T * E; x += THREADS) s_nbr[x] = (g0 + x < g_end) ? nbr[g0 + x] : -1;
     }
-    {   // a tile without any neighbour (past the real rows of a static-rows launch: 257 tiles of 192 rows for 256 CUs) writes zeros and leaves
+    {
         bool any = false;
         for (int x = tid; x < 64 * T * E; x += THREADS) any |= s_nbr[x] >= 0;
         if (!__syncthreads_or(any)) {
@@ -1342,27 +1276,14 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const float ae[KQ] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-        u32x4 p1, p2, p3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            unsigned int h0, m0_, l0, h1, m1_, l1;
-            ln_split3_bits(ae[2 * j], h0, m0_, l0);
-            ln_split3_bits(ae[2 * j + 1], h1, m1_, l1);
-            p1[j] = ln_pack_hi(h0, h1);
-            p2[j] = ln_pack_hi(m0_, m1_);
-            p3[j] = ln_pack_hi(l0, l1);
-        }
-        const bf16x8 a1 = __builtin_bit_cast(bf16x8, p1), a2 = __builtin_bit_cast(bf16x8, p2), a3 = __builtin_bit_cast(bf16x8, p3);
+        u32x4 p[3];
+        ln_split3_pack8(ae, 0, p);
+        const bf16x8 ap[3] = {__builtin_bit_cast(bf16x8, p[0]), __builtin_bit_cast(bf16x8, p[1]), __builtin_bit_cast(bf16x8, p[2])};
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const u32x4* pb = s_frag + ((e * NT + nt) * 3) * 64 + lane;
-            const bf16x8 b1 = __builtin_bit_cast(bf16x8, pb[0]), b2 = __builtin_bit_cast(bf16x8, pb[64]), b3 = __builtin_bit_cast(bf16x8, pb[128]);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, b1, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b3, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b1, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b2, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[nt], 0, 0, 0);
+            const bf16x8 bp[3] = {__builtin_bit_cast(bf16x8, pb[0]), __builtin_bit_cast(bf16x8, pb[64]), __builtin_bit_cast(bf16x8, pb[128])};
+            ln_b3_mfma16(ap, bp, acc[nt]);
         }
     }
     // C/D layout: col = lane & 15, row = (lane >> 4) * 4 + reg
@@ -1737,37 +1658,19 @@ __global__ void __launch_bounds__(256)
     grad_filter[g] = acc;
 }
 
-// 16 outputs per workgroup; the slabs are split over 16 thread rows and combined through LDS
-__global__ void __launch_bounds__(256) k_reduce_slabs(const float* __restrict__ partial, int nslabs, int total, float* __restrict__ out) {
-    __shared__ float s_part[16][17];
-    const int o = threadIdx.x & 15;
-    const int part = threadIdx.x >> 4;
-    const int g = blockIdx.x * 16 + o;
-    float acc = 0.0f;
-    if (g < total)
-        for (int s = part; s < nslabs; s += 16) acc += partial[(size_t)s * total + g];
-    s_part[part][o] = acc;
-    __syncthreads();
-    if (part == 0 && g < total) {
-        float r = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) r += s_part[k][o];
-        out[g] = r;
-    }
-}
-
 // total % 64 == 0: 64 outputs per workgroup as 16 float4 columns x 16 slab groups (every thread has its <= ceil(nslabs / 16)
 // float4 loads in flight at once), combined through LDS in a fixed order
 __global__ void __launch_bounds__(256) k_reduce_slabs4(const float* __restrict__ partial, int nslabs, int total, float* __restrict__ out) {
     ln_reduce_slabs4_block(blockIdx.x, partial, nslabs, total, out);
 }
 
-// out[i] = sum over s of partial[s * total + i], in slab order (deterministic); shared with the fp16 filter gradient
+// out[i] = sum over s of partial[s * total + i], in slab order (deterministic); shared with the fp16 filter gradient.  Unaligned or
+// total % 64 != 0: the 16-outputs-per-workgroup sum of ln_common.h
 int ln_reduce_slabs_async(const float* partial, int nslabs, int total, float* out, hipStream_t st) {
     if (total % 64 == 0 && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(partial)) & 15) == 0)
         LN_LAUNCH("k_reduce_slabs", k_reduce_slabs4, dim3(total / 64), dim3(256), 0, st, partial, nslabs, total, out);
     else
-        LN_LAUNCH("k_reduce_slabs", k_reduce_slabs, dim3(ln_div_up(total, 16)), dim3(256), 0, st, partial, nslabs, total, out);
+        LN_LAUNCH("k_reduce_slabs", ln_k_sum_slabs<false>, dim3(ln_div_up(total, 16)), dim3(256), 0, st, partial, nslabs, (long long)total, total, out);
     return LN_OK;
 }
 
@@ -1935,16 +1838,7 @@ __global__ void __launch_bounds__(64 * WV * WF, (WV * WF) > 8 ? 1 : LN_GFB_WAVES
 #pragma unroll
                 for (int a = 0; a < TPV; ++a)
 #pragma unroll
-                    for (int b = 0; b < TPF; ++b) {
-                        floatx4 c = acc[e][a][b];
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][2], fb[b][0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][0], fb[b][2], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][1], fb[b][1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][1], fb[b][0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][0], fb[b][1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][0], fb[b][0], c, 0, 0, 0);
-                        acc[e][a][b] = c;
-                    }
+                    for (int b = 0; b < TPF; ++b) ln_b3_mfma16(fa[a], fb[b], acc[e][a][b]);
             }
         }
     }

@@ -364,7 +364,7 @@ extern "C" int ln_conv_forward_f16(const int* nbr, const void* values_neigh, con
 // "down the rows": a sub-tile of 64 rows is staged row-major in LDS and read with the transposing LDS load of gfx950
 // (ds_read_b64_tr_b16: lane (i, q) receives 4 consecutive rows of column i; two of them = the 8 rows 8q..8q+7 of a 32-row step of
 // v_mfma_f32_16x16x32_f16).  Each wave owns whole 16x16 output
-// tiles D[v, f]; partial [V, F] blocks per row chunk go to slabs, summed by k_reduce_slabs4 / k_reduce_slabs (ln_conv.hip, deterministic).
+// tiles D[v, f]; partial [V, F] blocks per row chunk go to slabs, summed by ln_reduce_slabs_async (ln_conv.hip, deterministic).
 // ------------------------------------------------------------------------------------------
 #define LN_GF16_ROWS 512
 #define LN_GF16_SUB 64
