@@ -674,6 +674,37 @@ int ln_dice_forward(const float* log_probs, const long long* target, long long n
 int ln_dice_backward(const float* log_probs, const long long* target, const float* coef, const float* grad_loss, long long n,
                      long long points_per_cloud, int classes, float* grad_log_probs, void* stream);
 
+/* Class-weighted mean negative log-likelihood PER CLOUD of a cloud-major batch: torch.nn.NLLLoss(weight=, ignore_index=) on every cloud
+ * and the mean over the clouds (ln_train.py:130 on each cloud of a batch; weights as models.py compute_class_weights makes them).
+ * log_probs [n, classes] float, target [n] int64; clouds as ln_dice_forward defines them: cloud b owns rows [b n0, min((b + 1) n0, n))
+ * with n0 = points_per_cloud, B = ceil(n / n0), the last one possibly shorter; points_per_cloud >= n is one cloud.  A label counts when
+ * it differs from ignore_index (pass a value no label takes, e.g. LLONG_MIN, for none); labels outside [0, classes) are clamped, as in
+ * ln_nll_forward, and take the weight of the class they clamp to.  class_weight [classes] float or NULL (every weight 1).  Per cloud:
+ * N_b = sum w[y_i] log_probs[i, y_i] and W_b = sum w[y_i] over the labels that count; weight_sum[b] = W_b, or 1 when W_b == 0 (no label
+ * counts, or every counted weight is zero) — what the backward divides by —; per_cloud[b] = -N_b / weight_sum[b] (0 for such a cloud);
+ * loss[0] = (sum_b per_cloud[b]) / B, the convention of ln_lovasz_forward_clouds and ln_dice_forward.  log_probs is read at the clamped
+ * label of the rows that count and nowhere else, class_weight at the classes of such labels only: a -inf or NaN anywhere else reaches
+ * no output.
+ * Every sum in a fixed order, no float atomics.  Cloud b is summed as ln_nll_forward sums a call of the cloud's length (the same
+ * workgroups, strides, shuffle trees and finishing order), so per_cloud[b] and weight_sum[b] are what this call gives on cloud b's rows
+ * alone, bit for bit, and with class_weight == NULL they are the loss_count of ln_nll_forward on those rows.  The clouds are added
+ * strided over 1024 threads in series, then by the fixed tree of that workgroup.
+ * ln_nll_backward_clouds (one elementwise launch) writes every element of grad_log_probs [n, classes]:
+ * -grad_loss[0] w[y_i] / (B weight_sum[b]) at (i, clamped y_i) of the labels that count, 0 elsewhere; the caller does not zero the
+ * buffer.  Called with the sizes, ignore_index and class_weight of the forward call.
+ * Refused, nothing launched or written: n < 0, classes < 1, points_per_cloud < 1, a null buffer (but class_weight), a workspace below
+ * ln_nll_clouds_workspace_bytes (a pure host function, total) — LN_ERR_ARG; n * classes >= 2^31, B > 65535 (the cloud is the y
+ * coordinate of the grid) — LN_ERR_UNSUPPORTED.  n == 0: the forward sets loss to 0, the backward launches nothing.  Two launches
+ * forward (three for more than 64 clouds of more than 1024 rows each), one backward; no host synchronisation, no allocation: safe
+ * inside a stream capture, bitwise reproducible.  Not held: more than 2^24 counted labels in one cloud without weights (the fp32 count
+ * stops being exact). */
+size_t ln_nll_clouds_workspace_bytes(long long n, long long points_per_cloud);
+int ln_nll_forward_clouds(const float* log_probs, const long long* target, long long n, long long points_per_cloud, int classes,
+                          long long ignore_index, const float* class_weight, void* workspace, size_t workspace_bytes, float* loss,
+                          float* per_cloud, float* weight_sum, void* stream);
+int ln_nll_backward_clouds(const long long* target, const float* grad_loss, const float* weight_sum, long long n, long long points_per_cloud,
+                           int classes, long long ignore_index, const float* class_weight, float* grad_log_probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

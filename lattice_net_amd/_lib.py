@@ -150,6 +150,9 @@ SIGNATURES = {
     "ln_nll_workspace_bytes": (_sz, []),
     "ln_nll_forward": (_i, [_vp, _vp, _ll, _i, _ll, _vp, _sz, _vp, _vp]),
     "ln_nll_backward": (_i, [_vp, _vp, _vp, _ll, _i, _ll, _vp, _vp]),
+    "ln_nll_clouds_workspace_bytes": (_sz, [_ll, _ll]),
+    "ln_nll_forward_clouds": (_i, [_vp, _vp, _ll, _ll, _i, _ll, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ln_nll_backward_clouds": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _ll, _vp, _vp, _vp]),
     "ln_lovasz_workspace_bytes": (_sz, [_ll, _i]),
     "ln_lovasz_forward": (_i, [_vp, _vp, _ll, _i, _ll, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "ln_lovasz_backward": (_i, [_vp, _vp, _ll, _i, _vp, _vp]),

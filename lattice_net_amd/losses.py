@@ -18,7 +18,7 @@ import os
 
 import torch
 
-__all__ = ["GeneralizedSoftDiceLoss", "LovaszSoftmax", "Scores", "nll_loss_gather"]
+__all__ = ["GeneralizedSoftDiceLoss", "LovaszSoftmax", "NLLLoss", "Scores", "nll_loss_gather"]
 
 
 _NO_LABEL = -(1 << 62)  # "no ignore_index": a value no label takes
@@ -26,7 +26,8 @@ FUSED_NLL = True
 FUSED_IOU_COUNTS = True  # Scores.accumulate_scores(points_per_cloud=): integer-exact either way, and the torch form of one cloud synchronises
 FUSED_LOVASZ = False  # off until tools/bench_losses.py has shown the kernels below the torch form on an MI355X
 FUSED_DICE = True  # by the rule FUSED_LOVASZ states: tools/bench_losses.py on an MI355X has csrc/ln_dice.hip below the torch form, one cloud and per cloud
-_LOVASZ_MAX_CLASSES = 1024  # limits of ln_lovasz_forward (include/latticenet_hip.h)
+FUSED_NLL_CLOUDS = True  # nll_loss_gather(weight=, points_per_cloud=) / NLLLoss: by the rule FUSED_LOVASZ states, tools/bench_losses.py on an MI355X has csrc/ln_nll.hip below the torch forms, one cloud and per cloud
+_LOVASZ_MAX_CLASSES = 1024 # limits of ln_lovasz_forward (include/latticenet_hip.h)
 _LOVASZ_MAX_ELEMENTS = 1 << 31
 _LOVASZ_MAX_CLOUDS = 65535  # of ln_lovasz_forward_clouds and ln_iou_counts_clouds
 
@@ -164,11 +165,98 @@ class _DiceFunction(torch.autograd.Function):
         return grad, None, None, None
 
 
-def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=None) -> torch.Tensor:
+class _NllCloudsFunction(torch.autograd.Function):
+    """csrc/ln_nll.hip: the class-weighted NLL of every cloud of a cloud-major batch and the mean over the clouds — two launches forward
+    (the clouds' sums cut and added as ln_nll_forward does a call of a cloud's length, then the mean in a fixed order), one backward
+    that writes the whole [n, C] gradient.  weight None: every class 1.  points_per_cloud >= n: one cloud."""
+
+    @staticmethod
+    def forward(ctx, log_probs, target, ignore_index, weight, points_per_cloud):
+        from . import _lib
+        lib = _lib.load()
+        lp = log_probs.contiguous()
+        n, c = lp.shape
+        dev = lp.device
+        clouds = -(-n // points_per_cloud)
+        ws = torch.empty((lib.ln_nll_clouds_workspace_bytes(n, points_per_cloud),), dtype=torch.uint8, device=dev)
+        out = torch.empty((1 + 2 * clouds,), dtype=torch.float32, device=dev)  # loss, per_cloud [B], weight_sum [B]: one allocation, addressed
+        p = out.data_ptr()
+        _lib.check(lib.ln_nll_forward_clouds(_lib.ptr(lp), _lib.ptr(target), n, points_per_cloud, c, ignore_index,
+                                             None if weight is None else _lib.ptr(weight), _lib.ptr(ws), ws.numel(), p, p + 4, p + 4 + 4 * clouds,
+                                             _lib.stream_ptr(dev)), "ln_nll_forward_clouds")
+        ctx.save_for_backward(target, out, weight)
+        ctx.shape, ctx.ignore_index, ctx.points_per_cloud = (n, c), ignore_index, points_per_cloud
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        from . import _lib
+        target, out, weight = ctx.saved_tensors
+        n, c = ctx.shape
+        g = grad_loss.contiguous().float()
+        grad = torch.empty((n, c), dtype=torch.float32, device=g.device)
+        _lib.check(_lib.load().ln_nll_backward_clouds(_lib.ptr(target), _lib.ptr(g), out.data_ptr() + 2 * (out.numel() + 1), n, ctx.points_per_cloud, c,
+                                                      ctx.ignore_index, None if weight is None else _lib.ptr(weight), _lib.ptr(grad),
+                                                      _lib.stream_ptr(g.device)), "ln_nll_backward_clouds")
+        return grad, None, None, None, None
+
+
+def _nll_clouds_torch(log_probs, target, ignore_index, weight, points_per_cloud):
+    """The formula of ln_nll_forward_clouds in torch operators: gather, `where`, sums over a [B, n0] view padded behind a shorter last
+    cloud.  Shapes depend on sizes only and nothing is read back: any device, any float dtype, inside a stream capture."""
+    n, c = log_probs.shape
+    if n == 0:
+        return log_probs.sum() * 0.0
+    n0 = min(points_per_cloud, n)
+    clouds = -(-n // n0)
+    clamped = target.clamp(0, c - 1)
+    picked = log_probs.gather(1, clamped.unsqueeze(1)).squeeze(1)
+    zero = torch.zeros_like(picked)
+    w = torch.ones_like(picked) if weight is None else weight.to(device=picked.device, dtype=picked.dtype)[clamped]
+    if ignore_index is not None:
+        keep = target != int(ignore_index)
+        # (selected, not multiplied by a 0 / 1 mask: a -inf or NaN in an ignored row, or in the weight of a class that only ignored labels
+        # carry, must reach neither the loss nor the gradient — w is selected first, so that the product's gradient is 0 * 0 there)
+        w = torch.where(keep, w, zero)
+        terms = torch.where(keep, w * picked, zero)
+    else:
+        terms = w * picked
+    pad = clouds * n0 - n
+    if pad:
+        terms, w = torch.nn.functional.pad(terms, (0, pad)), torch.nn.functional.pad(w, (0, pad))
+    weight_sum = w.reshape(clouds, n0).sum(1)
+    per_cloud = -terms.reshape(clouds, n0).sum(1) / torch.where(weight_sum != 0, weight_sum, torch.ones_like(weight_sum))
+    return per_cloud.sum() / clouds
+
+
+def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=None, *, weight=None, points_per_cloud=None) -> torch.Tensor:
     """Mean negative log-likelihood, as torch.nn.NLLLoss(ignore_index=...) (ln_train.py:130).  float32 CUDA inputs take the fused
     kernels; everything else is written as gather + masked mean (torch's nll_loss kernels reduce a [120 k, C] input in a single
-    workgroup: 0.14 ms forward, 0.09 ms backward on MI355X)."""
+    workgroup: 0.14 ms forward, 0.09 ms backward on MI355X).
+
+    weight ([C] class weights, torch.nn.NLLLoss(weight=): the loss is sum w[y_i] lp[i, y_i] / sum w[y_i]) and points_per_cloud (the
+    [N, C] input is a cloud-major batch of ceil(N / n0) clouds, the last possibly shorter; the result is the MEAN OVER THE CLOUDS of
+    each cloud's own loss, a cloud without a counted label contributing 0, as LovaszSoftmax(points_per_cloud=)) go through
+    ln_nll_forward_clouds on float32 CUDA inputs while FUSED_NLL_CLOUDS is set, and through the torch form otherwise.  With both left at
+    None nothing changes: the same Function, the same kernels, the same bits."""
     target = target.reshape(-1)
+    if weight is not None or points_per_cloud is not None:
+        if log_probs.dim() != 2 or target.shape[0] != log_probs.shape[0]:
+            raise ValueError("nll_loss_gather(weight=, points_per_cloud=) expects [N, C] log-probabilities and N labels")
+        n, c = log_probs.shape
+        if weight is not None and weight.numel() != c:
+            raise ValueError("weight: one value per class")
+        n0 = max(n, 1) if points_per_cloud is None else int(points_per_cloud)
+        if n0 < 1:
+            raise ValueError("points_per_cloud >= 1")
+        if FUSED_NLL_CLOUDS and log_probs.is_cuda and log_probs.dtype == torch.float32 and target.is_cuda and target.dtype == torch.int64 and \
+                n > 0 and log_probs.numel() < _LOVASZ_MAX_ELEMENTS and -(-n // n0) <= _LOVASZ_MAX_CLOUDS:
+            w = weight
+            if w is not None and not (w.device == log_probs.device and w.dtype == torch.float32 and w.dim() == 1 and w.is_contiguous() and
+                                      not w.requires_grad):  # (the buffer of NLLLoss on the model's device passes as it is)
+                w = w.detach().to(device=log_probs.device, dtype=torch.float32).reshape(-1).contiguous()
+            return _NllCloudsFunction.apply(log_probs, target.contiguous(), _NO_LABEL if ignore_index is None else int(ignore_index), w, n0)
+        return _nll_clouds_torch(log_probs, target, ignore_index, None if weight is None else weight.detach().reshape(-1), n0)
     if FUSED_NLL and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 2 and target.is_cuda and \
             target.dtype == torch.int64 and target.shape[0] == log_probs.shape[0] and log_probs.shape[0] > 0:
         return _NllFunction.apply(log_probs, target.contiguous(), _NO_LABEL if ignore_index is None else int(ignore_index))
@@ -178,6 +266,34 @@ def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=
     keep = target != ignore_index
     # (selected, not multiplied by a 0 / 1 mask: the kernels never read an ignored row, so a -inf or NaN there must not reach the loss)
     return -torch.where(keep, picked, torch.zeros_like(picked)).sum() / keep.sum().clamp(min=1).to(picked.dtype)
+
+
+class NLLLoss(torch.nn.Module):
+    """torch.nn.NLLLoss(weight=, ignore_index=, reduction="mean") of the training step (ln_train.py:130) over log-probabilities [N, C],
+    with the class weights of LNN.compute_class_weights and, for a batch of clouds in one lattice, per cloud.
+
+    points_per_cloud=None: the loss of one cloud.  points_per_cloud=n0 (what Lattice.points_per_cloud() returns for a batch set up with
+    set_cloud_batch): the rows are a cloud-major batch of ceil(N / n0) clouds of n0 points, the last possibly shorter, and the result
+    is the MEAN OVER THE CLOUDS of each cloud's own loss  -sum w[y_i] lp[i, y_i] / sum w[y_i]  over the cloud's labels that differ from
+    ignore_index — not the loss of the whole batch, in which a cloud with fewer ignored labels weighs more.  A cloud without a counted
+    label contributes 0 and still counts in the mean, as in LovaszSoftmax(points_per_cloud=).  ignore_index=None ignores no label
+    (torch's default is -100).  Labels outside [0, C) are clamped, as in nll_loss_gather.  With neither weight nor points_per_cloud this
+    is nll_loss_gather(log_probs, target, ignore_index)."""
+
+    def __init__(self, weight=None, ignore_index=None, points_per_cloud=None):
+        super().__init__()
+        if points_per_cloud is not None:
+            if int(points_per_cloud) < 1:
+                raise ValueError("points_per_cloud >= 1")
+            points_per_cloud = int(points_per_cloud)
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight).detach().clone().reshape(-1))
+        self.ignore_index = ignore_index
+        self.points_per_cloud = points_per_cloud
+
+    def forward(self, log_probs: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if log_probs.dim() != 2:
+            raise ValueError("NLLLoss expects [N, C] log-probabilities")
+        return nll_loss_gather(log_probs, target, self.ignore_index, weight=self.weight, points_per_cloud=self.points_per_cloud)
 
 
 class GeneralizedSoftDiceLoss(torch.nn.Module):

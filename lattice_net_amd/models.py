@@ -122,6 +122,17 @@ class LNN(torch.nn.Module):
                                                           dropout_prob=model_params.dropout_last_layer(), experiment=experiment,
                                                           device=device)
         self.logsoftmax = torch.nn.LogSoftmax(dim=1)
+        self._device = torch.device(device)
+
+    def compute_class_weights(self, class_frequencies, background_idx):
+        """Class weights for losses.NLLLoss(weight=) on imbalanced label sets (reference models.py:273-294): 1 / log(1.05 + f) of the
+        classes' frequencies f (an array-like or a tensor, [classes]) — 20.5 for a class that never occurs, 1.39 for one that is every
+        label — with the background class at 1e-8.  float32, on the model's device."""
+        f = torch.as_tensor(np.asarray(class_frequencies.detach().cpu() if torch.is_tensor(class_frequencies) else class_frequencies))
+        param = next(self.parameters(), None)
+        weights = 1.0 / torch.log(1.05 + f.float().to(self._device if param is None else param.device))
+        weights[background_idx] = 1e-8
+        return weights
 
     def forward(self, ls, positions, values):
         with torch.no_grad():

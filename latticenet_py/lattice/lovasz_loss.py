@@ -1,2 +1,2 @@
-"""Alias: LovaszSoftmax of lattice_net_amd.losses."""
-from lattice_net_amd.losses import LovaszSoftmax  # noqa: F401
+"""Alias: LovaszSoftmax of lattice_net_amd.losses, and the NLLLoss that stands next to it in a training step."""
+from lattice_net_amd.losses import LovaszSoftmax, NLLLoss  # noqa: F401

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Time of the training losses on a [120k, 20] prediction: NLL, Lovasz-Softmax (HIP kernels, and the torch form with
+"""Time of the training losses on a [120k, 20] prediction: NLL (then with class weights and per cloud: ln_nll_forward_clouds against
+ln_nll_forward, torch's nll_loss(weight=) and the torch gather form; `--nll` stops after these lines), Lovasz-Softmax (HIP kernels, and the torch form with
 losses.FUSED_LOVASZ off), soft Dice (HIP kernels, and the torch form with losses.FUSED_DICE off; then per cloud); forward + backward.  Then the same matrix as a batch of 16 clouds x 7 500 points: the per-cloud
 loss (ln_lovasz_forward_clouds against 16 calls of ln_lovasz_forward and against the batched torch form) and the per-cloud IoU
 counts (ln_iou_counts_clouds against Scores.accumulate_scores cloud by cloud)."""
@@ -25,6 +26,58 @@ def run(fn):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / 20 * 1e3
 print(f"log_softmax + nll   {run(lambda lp: nll_loss_gather(lp, target, 0)):6.3f} ms")
+
+# ---- NLL with class weights and per cloud (ln_nll_forward_clouds) against the torch forms, one cloud and 16 clouds x 7 500 points ---------
+# Every line: windows of 200 steps (log_softmax + loss forward + backward), 21 windows per variant taken in turn, variant after
+# variant, so that a drift of the clock hits all of them alike (a round before them is dropped); median, fastest and slowest window.  FUSED_NLL_CLOUDS goes on only when
+# the kernels' median is below the torch form's by more than the spread (slowest - fastest window) of either, at BOTH shapes.
+def nll_section():
+    weight = (1.0 / torch.log(1.05 + torch.bincount(target, minlength=c).float() / n)).to(dev)
+    weight[0] = 1e-8
+    def window(fn, steps=200):
+        for _ in range(3):
+            logits.grad = None
+            fn(torch.log_softmax(logits, 1)).backward()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            logits.grad = None
+            fn(torch.log_softmax(logits, 1)).backward()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+    def with_switch(fused, weight, n0):  # (the function form on every line: no Module.__call__ on one side only)
+        def fn(lp):
+            losses.FUSED_NLL_CLOUDS = fused
+            return nll_loss_gather(lp, target, 0, weight=weight, points_per_cloud=n0)
+        return fn
+    one, one_w, per, per_w = (None, n), (weight, n), (None, 7500), (weight, 7500)
+    variants = [
+        ("120000 x 20, one cloud: ln_nll_forward / _backward (no weights)           ", lambda lp: nll_loss_gather(lp, target, 0)),
+        ("120000 x 20, one cloud: ln_nll_forward_clouds / _backward_clouds, no weights", with_switch(True, *one)),
+        ("120000 x 20, one cloud: ln_nll_forward_clouds / _backward_clouds, weights   ", with_switch(True, *one_w)),
+        ("120000 x 20, one cloud: torch.nn.functional.nll_loss(weight=)               ",
+         lambda lp: torch.nn.functional.nll_loss(lp, target, weight=weight, ignore_index=0)),
+        ("120000 x 20, one cloud: torch gather form, weights                          ", with_switch(False, *one_w)),
+        ("16 x 7500 x 20: ln_nll_forward_clouds / _backward_clouds, no weights        ", with_switch(True, *per)),
+        ("16 x 7500 x 20: ln_nll_forward_clouds / _backward_clouds, weights           ", with_switch(True, *per_w)),
+        ("16 x 7500 x 20: batched torch gather form per cloud, no weights             ", with_switch(False, *per)),
+        ("16 x 7500 x 20: batched torch gather form per cloud, weights                ", with_switch(False, *per_w)),
+    ]
+    default = losses.FUSED_NLL_CLOUDS
+    times = [[] for _ in variants]
+    for r in range(22):  # (the first round warms the clocks and is dropped)
+        for k, (_, fn) in enumerate(variants):
+            t = window(fn)
+            if r:
+                times[k].append(t)
+    losses.FUSED_NLL_CLOUDS = default
+    for (name, _), t in zip(variants, times):
+        t.sort()
+        print(f"{name} median {t[len(t) // 2]:6.4f} ms, fastest {t[0]:6.4f} ms, slowest {t[-1]:6.4f} ms")
+nll_section()
+if "--nll" in sys.argv:  # (only the lines above)
+    sys.exit(0)
+
 def run_lovasz(fused):
     losses.FUSED_LOVASZ = fused
     return run(lambda lp: lov(lp, target))
