@@ -41,6 +41,7 @@ extern "C" {
 #define LN_STATUS_KEY_RANGE 2       /* a lattice key did not fit the packed 64-bit slot format */
 #define LN_STATUS_BUCKET_OVERFLOW 4 /* bucketed build: one LDS-staged bucket filled up; nothing of this build is valid,
                                        re-run it with LN_BUILD_ATOMIC_PATH (whose inserts spill past a full bucket) */
+#define LN_STATUS_CLOUD_BAND 8      /* a cloud of a batch leaves its key band (set by ln_cloud_key_extents, never by a build) */
 
 #define LN_MAX_POS_DIM 6
 #define LN_SLOT_MAP_INTS 32 /* ints behind LnTable.slot_map */
@@ -704,6 +705,35 @@ int ln_nll_forward_clouds(const float* log_probs, const long long* target, long 
                           float* per_cloud, float* weight_sum, void* stream);
 int ln_nll_backward_clouds(const long long* target, const float* grad_loss, const float* weight_sum, long long n, long long points_per_cloud,
                            int classes, long long ignore_index, const float* class_weight, float* grad_log_probs, void* stream);
+
+/* Band check of a batch of clouds in one table (LnTable.batch_points / batch_key_step): a launch sequence of its own, queued on `stream`
+ * behind the build of `t` from the same positions and sigmas; the build kernels are not involved.  B = ceil(n / batch_points) clouds.
+ * extents [B, 2] int32 receives, per cloud, the smallest and the largest FIRST key coordinate over the d + 1 simplex vertices of every
+ * point of the cloud, before the cloud's shift (an empty cloud keeps (INT_MAX, INT_MIN)); integer atomics only: order-independent and
+ * bitwise reproducible.  With half = batch_key_step >> 1, cloud c is inside its band when -half + guard <= lo_c and hi_c < half - guard;
+ * an empty cloud is inside.  *first_bad receives the smallest offending cloud, INT_MAX when there is none.  On a violation
+ * LN_STATUS_CLOUD_BAND is ORed into *t->status and, when t->host_counters is set, the report word of the build is stored again with the
+ * bit in it (*t->nr_filled | *t->status << 32 | host_seq << 40: pass the LnTable the build was given).  Three launches, no host
+ * synchronisation, no allocation: safe inside a stream capture.
+ * Refused, nothing launched or written: a null table, buffer or sigmas, a table without a batch (batch_points <= 0), n < 0, guard < 0,
+ * guard >= half — LN_ERR_ARG; pos_dim outside 1..LN_MAX_POS_DIM, B > 65535 (the cloud is the y coordinate of the grid) —
+ * LN_ERR_UNSUPPORTED.  n == 0 launches and writes nothing.
+ *
+ * guard, in key units of the level that is checked (the finest).  Write e for the elevated first coordinate of a point.
+ *  - The d + 1 vertices of the simplex that holds the point differ by at most d in every coordinate and the point is a convex combination
+ *    of them; with one unit for the fp32 rounding of e, every vertex key k of the point has |k - e| <= d + 1.
+ *  - A 1-hop neighbour at dilation 1 (csrc/ln_neighbours.h) is key + 1 in every coordinate but one, key - d in that one (or the mirror
+ *    image): its first coordinate is at most d away, dilation x d at a larger dilation.
+ *  - Level L (sigmas x 2^L, built from the same positions) has e / 2^L, exactly, as its elevated coordinate, and key step and band are
+ *    halved L times (batch_key_step is a multiple of 16 (d + 1): exact for L <= 3).  A level-L key unit is 2^L units of the finest
+ *    level, so in those units a level-L vertex of the point lies within 2^L (d + 1) of e, i.e. within (1 + 2^L)(d + 1) of a finest-level
+ *    vertex of the point, and its 1-hop neighbours within (1 + 2^L)(d + 1) + 2^L d.
+ *  So guard >= (1 + 2^L)(d + 1) + 2^L d keeps the vertices of level L and their 1-hop neighbours inside the band, and the row decode of
+ *  ln_cloud_row_starts right, whenever the finest level passes.  L = 3: 9 (d + 1) + 8 d = 17 d + 9 <= 16 (d + 1) for d <= 7.  The
+ *  default of the Python layer, 16 (d + 1), therefore covers four lattice levels (L = 0..3) at dilation 1 for every supported pos_dim;
+ *  larger dilations or more levels need (1 + 2^L)(d + 1) + dilation 2^L d. */
+int ln_cloud_key_extents(const LnTable* t, const float* positions_raw, const float* sigmas_host, int n, int guard, int* extents,
+                         int* first_bad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("LATTICE_NET_LIB") or os.path.join(_PKG, "liblatticene
 LN_STATUS_TABLE_FULL = 1
 LN_STATUS_KEY_RANGE = 2
 LN_STATUS_BUCKET_OVERFLOW = 4
+LN_STATUS_CLOUD_BAND = 8
 LN_BUILD_WRITE_IDX = 1
 LN_BUILD_CLEAR_FIRST = 2
 LN_BUILD_ATOMIC_PATH = 4
@@ -178,6 +179,7 @@ SIGNATURES = {
     "ln_batch_norm_workspace_bytes": (_sz, [_i]),
     "ln_batch_norm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "ln_cloud_key_extents": (_i, [_T, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ln_slice_classify_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ln_slice_classify_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }

@@ -304,6 +304,8 @@ class CapturedNetworkStep:
             nr, status = Lattice.decode_report(word[0])
             if status & (_lib.LN_STATUS_BUCKET_OVERFLOW | _lib.LN_STATUS_TABLE_FULL | _lib.LN_STATUS_KEY_RANGE):
                 raise _lib.LatticeNetHipError(f"replayed build of lattice level {level} failed (status bits {status}): redo this cloud eagerly")
+            if status & _lib.LN_STATUS_CLOUD_BAND:
+                raise _lib.LatticeNetHipError(f"replayed build of lattice level {level}: " + Lattice.band_violation_message(word))
             if nr > bound:
                 raise _lib.LatticeNetHipError(f"lattice level {level} of this cloud has {nr} vertices, its static row bound is {bound}: "
                                               "rows beyond the bound were dropped; redo this cloud eagerly or re-capture with larger bounds")

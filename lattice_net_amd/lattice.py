@@ -336,6 +336,66 @@ class _TableStorage:
         self.csr_cache.clear()
 
 
+def max_clouds_in_key_range(pos_dim: int, quotient_step: int) -> int:
+    """Largest batch of clouds `quotient_step` cells apart whose bands fit the packable key range of `pos_dim` (README 'Key range':
+    min(32, 60 // d) bits per quotient, and (d + 1) x quotient + remainder in an int32 key).  Cloud c owns the quotients
+    [c q - q / 2, c q + q / 2): B clouds need (B - 1) q + q / 2 <= Q, Q the largest quotient magnitude.  Pure arithmetic."""
+    d, q = int(pos_dim), int(quotient_step)
+    reach = min(2 ** (min(32, 60 // d) - 1), 2 ** 31 // (d + 1))
+    return 0 if reach < q // 2 else (reach - q // 2) // q + 1
+
+
+class _BandCheck:
+    """What set_cloud_batch(check_band=True) hands to clones and coarser levels: the guard and the output buffers of
+    ln_cloud_key_extents, one int32 [2 B + 1] (extents, then the first offending cloud) per (stream, B) — launches on one stream are
+    ordered, so builds on it can share a buffer, and builds on different streams never do."""
+
+    def __init__(self, guard: int):
+        self.guard = int(guard)
+        self.bufs = {}
+
+    @staticmethod
+    def check_key_range(pos_dim: int, quotient_step: int, clouds: int):
+        fits = max_clouds_in_key_range(pos_dim, quotient_step)
+        if clouds > fits:
+            raise ValueError(f"{clouds} clouds x quotient_step {quotient_step} do not fit the packable key range of pos_dim {pos_dim} "
+                             f"({min(32, 60 // pos_dim)} bits per quotient, README 'Key range'): the largest batch that fits is {fits} clouds")
+
+
+# pinned report word (address) -> (buffer, clouds, guard, key step, pos_dim) of the band check last queued behind a build reporting there
+_BAND_REPORTS = {}
+
+
+def suggest_quotient_step(positions: torch.Tensor, sigmas, points_per_cloud: int, guard: Optional[int] = None) -> int:
+    """Set-up-time helper (synchronises): the smallest quotient_step, a multiple of 16 cells, whose band holds every cloud of
+    `positions` ([n, d] float32 on the device, cloud-major, `points_per_cloud` points each) with `guard` (default 16 (d + 1)) under
+    `sigmas`.  Runs the extents kernel of the band check."""
+    if positions.dtype != torch.float32 or positions.dim() != 2 or not positions.is_contiguous():
+        raise ValueError("positions should be a contiguous [n, d] float32 tensor")
+    _require_cuda(positions, "positions")
+    n, d = positions.shape
+    sigmas = [float(s) for s in sigmas]
+    if len(sigmas) != d or d > _lib.LN_MAX_POS_DIM or int(points_per_cloud) < 1:
+        raise ValueError("one sigma per position dimension (at most 6) and points_per_cloud >= 1")
+    guard = 16 * (d + 1) if guard is None else int(guard)
+    if guard < 0:
+        raise ValueError("guard >= 0")
+    if n == 0:
+        return 16
+    clouds = -(-n // int(points_per_cloud))
+    step = ((1 << 30) // (16 * (d + 1))) * 16 * (d + 1)  # a band no packable cloud leaves: only the extents are wanted
+    words = torch.zeros((2 * clouds + 3,), dtype=torch.int32, device=positions.device)  # extents | first_bad | nr_filled | status
+    base = words.data_ptr()
+    t = _lib.LnTable(1, d, None, None, None, None, None, base + 4 * (2 * clouds + 1), base + 4 * (2 * clouds + 2), None, 0, _lib.LN_KEYS_LATTICE, 0,
+                     None, 0, int(points_per_cloud), step, None)
+    _lib.check(_lib.load().ln_cloud_key_extents(C.byref(t), _lib.ptr(positions), _lib.host_floats(sigmas), n, min(guard, (step >> 1) - 1), base,
+                                                base + 8 * clouds, _lib.stream_ptr(positions.device)), "ln_cloud_key_extents")
+    ext = words[: 2 * clouds].view(clouds, 2).tolist()
+    need = max([1] + [max(guard - lo, hi + guard + 1) for lo, hi in ext if lo <= hi])  # half a key step must reach this far
+    cells = -(-need // (8 * (d + 1)))  # half = quotient_step (d + 1) / 2 = 8 (d + 1) per 16 cells
+    return 16 * max(cells, 1)
+
+
 class HashTable:
     """Host owner of the table tensors (src/HashTable.cu:11-115)."""
 
@@ -352,6 +412,9 @@ class HashTable:
         self._batch = (0, 0)  # (points per cloud, key step) of a batch of independent clouds in this table (Lattice.set_cloud_batch)
         self._per_cloud_norm = False  # GroupNorm blocks take their statistics per cloud of the batch (set_cloud_batch(per_cloud_norm=True))
         self._per_cloud_invalid_vertex = False  # Distribute / PointNet drop the first vertex of every cloud (set_cloud_batch(per_cloud_invalid_vertex=True))
+        self._band = None  # band check of the batch (set_cloud_batch(check_band=True)): a _BandCheck shared with clones and coarser levels
+        self._band_launch = False  # this table's builds queue the check (the finest level: its verdict with the guard covers the coarser ones)
+        self._band_last = None  # (int32 [2 B + 1] device buffer, B) of the last checked build of this table
 
     def flush(self):
         """Issues a deferred begin_splat clear, if any (every reader of table state goes through this)."""
@@ -460,6 +523,12 @@ class HashTable:
         if getattr(self, "_readback_pending", False):
             self._readback_pending = False
             arr = self._pinned_np  # int64 view: nr_filled | status << 32 | seq << 40, ONE device store per build
+            if getattr(self, "_band_pending", False):
+                # a band check is queued behind the build: its verdict stores the word again, so wait for the end of the whole sequence
+                self._band_pending = False
+                self._readback_event.synchronize()
+                word = int(arr[0])
+                return [word & 0xFFFFFFFF, (word >> 32) & 0xFF]
             spins = 0
             seq = self._host_seq
             word = int(arr[0])
@@ -602,6 +671,7 @@ class Lattice:
         ht._batch = oh._batch
         ht._per_cloud_norm = oh._per_cloud_norm
         ht._per_cloud_invalid_vertex = oh._per_cloud_invalid_vertex
+        ht._band, ht._band_launch = oh._band, oh._band_launch
         ht._static_levels = getattr(oh, "_static_levels", None)
         ht.m_nr_filled_is_dirty = oh.m_nr_filled_is_dirty
         ht.m_nr_filled = oh.m_nr_filled
@@ -689,6 +759,9 @@ class Lattice:
             w = torch.empty((n * (d + 1),), dtype=torch.float32, device=dev)
         tokens = n * (d + 1)
         st = ht._storage
+        check_band = bool(ht._band_launch and ht._band is not None and ht._batch[0] and n > 0)
+        if check_band:  # (host arithmetic, before anything is queued)
+            ht._band.check_key_range(d, ht._batch[1] // (d + 1), -(-n // ht._batch[0]))
         clear_vals, do_clear = ht.take_pending_clear()  # begin_splat's clear rides in the same C call
         self._choose_hash_capacity(tokens, fresh=do_clear)
         if do_clear:
@@ -737,6 +810,9 @@ class Lattice:
                                        _lib.ptr(idx), _lib.ptr(w), _lib.ptr(distributed), flags, C.byref(csr), _lib.ptr(ws), ws.numel(),
                                        cv, cn, self._stream())
                 _lib.check(rc, "ln_distribute")
+            ht._band_pending = False
+            if check_band:
+                self._queue_band_check(t, positions_raw, n)
             st.touch()
             st.batch_clouds = -(-n // ht._batch[0]) if ht._batch[0] else 0
             st.rows_first_occurrence = bool(flags & _lib.LN_BUILD_CANONICAL_ROWS)
@@ -797,6 +873,50 @@ class Lattice:
         st = self.m_hash_table._storage
         if getattr(st, "replay", None) is not None:
             st.replay.append(fn)
+
+    def _queue_band_check(self, t, positions_raw, n: int):
+        """ln_cloud_key_extents behind the build that was just issued with the struct `t`, on the same stream.  No synchronisation; the
+        output buffer is kept per (stream, clouds) by the _BandCheck all clones of the lattice share, so only the first call allocates."""
+        ht = self.m_hash_table
+        band = ht._band
+        bp, step = ht._batch
+        d = positions_raw.shape[1]
+        clouds = -(-n // bp)
+        stream = self._stream()
+        buf = band.bufs.get((stream, clouds))
+        if buf is None:
+            buf = band.bufs[(stream, clouds)] = torch.empty((2 * clouds + 1,), dtype=torch.int32, device=self._dev())
+        _lib.check(_lib.load().ln_cloud_key_extents(C.byref(t), _lib.ptr(positions_raw), self._sigmas_host(), n, band.guard, buf.data_ptr(),
+                                                    buf.data_ptr() + 8 * clouds, stream), "ln_cloud_key_extents")
+        ht._band_last = (buf, clouds)
+        ht._band_pending = True
+        _BAND_REPORTS[ht._pinned.data_ptr()] = (buf, clouds, band.guard, step, d)
+
+    def cloud_key_extents(self) -> torch.Tensor:
+        """Device int32 [B, 2] of the last checked build of this lattice (set_cloud_batch(check_band=True)): per cloud the smallest and
+        the largest first key coordinate over the simplex vertices of its points, before the cloud's shift; (INT_MAX, INT_MIN) for a cloud
+        without a point.  The buffer is reused by the next checked build of the same batch size on the same stream."""
+        last = self.m_hash_table._band_last
+        if last is None:
+            raise _lib.LatticeNetHipError("cloud_key_extents: no checked build has happened on this lattice (set_cloud_batch(check_band=True))")
+        buf, clouds = last
+        return buf[: 2 * clouds].view(clouds, 2)
+
+    @staticmethod
+    def band_violation_message(report) -> str:
+        """Text for LN_STATUS_CLOUD_BAND in the report word `report` (the pinned int64 view a build logs): reads the extents back."""
+        info = _BAND_REPORTS.get(int(report.ctypes.data)) if report is not None else None
+        if info is None:
+            return "a cloud of the batch leaves its key band (Lattice.set_cloud_batch)"
+        buf, clouds, guard, step, d = info
+        vals = buf.tolist()
+        half, bad = step >> 1, vals[2 * clouds]
+        where = (f"cloud {bad} has first key coordinates [{vals[2 * bad]}, {vals[2 * bad + 1]}]" if 0 <= bad < clouds
+                 else "no cloud of the LAST checked build on this stream offends (the extents buffer was reused since)")
+        return (f"a cloud of the batch leaves its key band: {where}, the band is [{-half + guard}, {half - guard}) "
+                f"(half a key step of {step} = quotient_step {step // (d + 1)} x {d + 1}, less a guard of {guard}); its vertices merge with "
+                "the next cloud's and per-cloud results are wrong.  Raise quotient_step (lattice_net_amd.suggest_quotient_step), use larger "
+                "sigmas or centre the clouds")
 
     def canonicalize_rows(self, idx: torch.Tensor):
         """Relabels the rows of the table the last (bucketed, slot-order) build produced, `idx` and the build's cached CSR into the
@@ -1268,6 +1388,7 @@ class Lattice:
         ht._batch = (bp, (step // (2 * (d + 1))) * (d + 1)) if bp else (0, 0)
         ht._per_cloud_norm = self.m_hash_table._per_cloud_norm
         ht._per_cloud_invalid_vertex = self.m_hash_table._per_cloud_invalid_vertex
+        ht._band = self.m_hash_table._band  # (inherited, but no launch: the finest level's verdict with the guard covers this level)
         ht._storage = _TableStorage(capacity, d, dev, spare_row_width=self.val_dim())
         # [1, val_dim] zeros: a placeholder until the coarse values exist
         ht.m_values_tensor = ht._storage.fresh_row if ht._storage.fresh_row is not None else torch.zeros((1, self.val_dim()), dtype=torch.float32, device=dev)
@@ -1582,16 +1703,27 @@ class Lattice:
         ht._static_levels = None if coarse_bounds is None else {self.m_lvl + 1 + k: int(b) for k, b in enumerate(coarse_bounds)}
 
     def set_cloud_batch(self, points_per_cloud: Optional[int], quotient_step: int = 1 << 13, per_cloud_norm: bool = False,
-                        per_cloud_invalid_vertex: bool = False):
+                        per_cloud_invalid_vertex: bool = False, check_band: bool = False, guard: Optional[int] = None):
         """The multi-cloud launch form for small clouds.  From now on the positions handed to this lattice are a BATCH of independent
         clouds of `points_per_cloud` points each (cloud c = rows c * points_per_cloud ... of the positions tensor; None / 0 switches it
         off).  The lattice of cloud c is translated by c * quotient_step lattice cells along the first coordinate (a translation of the
         permutohedral lattice onto itself: same simplices, ranks and barycentric weights as a build of the cloud alone), so the clouds
         share ONE table without sharing a vertex and every operator of the path — build, neighbour lists, convolutions forward and
         backward, slice, gather, the scatters — runs over the whole batch in one launch with per-cloud results; filter gradients are the
-        sum over the clouds.  The clouds must stay within quotient_step / 2 lattice cells of the origin on the first axis (a cell is
-        ~0.8 (d + 1) sigma wide... see README 'Key range'; 8192 cells and 64 clouds fit the 2^20 cells of d <= 3).  Coarser levels
-        created from this lattice inherit the batch with the step halved per level.
+        sum over the clouds.  The clouds stay within quotient_step / 2 lattice cells of the origin on the first axis (a cell is
+        ~0.8 (d + 1) sigma wide... see README 'Key range'; 8192 cells and 64 clouds fit the 2^20 cells of d <= 3): checked with
+        check_band=True.  Coarser levels created from this lattice inherit the batch with the step halved per level.
+
+        `check_band=True`: every build from positions into this lattice (splat, distribute, just_create_verts; eager, under
+        set_static_rows and inside a stream capture) queues ln_cloud_key_extents behind itself: three small launches, no
+        synchronisation, no allocation after the first call.  A cloud whose simplex vertices leave [-half + guard, half - guard) on the
+        first key coordinate (half = quotient_step (d + 1) / 2 key units) raises LN_STATUS_CLOUD_BAND in the build's status word: the
+        first nr_lattice_vertices() after the build raises LatticeNetHipError naming the cloud, as do static_build_report() and
+        CapturedStep.check() / CapturedNetworkStep.check() after a replay.  `guard` (key units of this level, default 16 (d + 1)) keeps
+        1-hop neighbours at dilation 1 and three coarser levels inside the band as well (include/latticenet_hip.h derives it); coarser
+        levels inherit the switch and launch nothing.  The switch also verifies, on the host, that the batch fits the packable key
+        range (ValueError naming the largest batch that does).  The first vertex-count read then waits for the end of the check instead
+        of the end of the build's scan.  cloud_key_extents() returns the measured extents.
 
         GroupNorm statistics over all rows of the value matrix would mix the clouds.  `per_cloud_norm=True` (needs
         set_row_order("canonical"); coarser levels inherit it) makes the GroupNorm of the `Gn*` blocks and of GroupNormLatticeModule
@@ -1613,12 +1745,21 @@ class Lattice:
         orders, more than 64 clouds; BatchNorm blocks (statistics over the batch by definition) are unchanged.  With the defaults
         False nothing changes."""
         d = self.pos_dim() if self.m_hash_table.is_initialized() else len(self.m_sigmas)
+        band = None
         if not points_per_cloud:
             self.m_hash_table._batch = (0, 0)
         else:
             if int(points_per_cloud) < 1 or int(quotient_step) < 2 or int(quotient_step) % (1 << 4):
                 raise ValueError("points_per_cloud >= 1 and a quotient_step that is a multiple of 16 (halved per coarser level)")
+            if check_band:
+                band = _BandCheck(16 * (d + 1) if guard is None else int(guard))
+                half = int(quotient_step) * (d + 1) // 2
+                if band.guard < 0 or band.guard >= half:
+                    raise ValueError(f"guard {band.guard} must be in [0, {half}): half a key step of quotient_step {int(quotient_step)} x (d + 1)")
+                band.check_key_range(d, int(quotient_step), 1)
             self.m_hash_table._batch = (int(points_per_cloud), int(quotient_step) * (d + 1))
+        self.m_hash_table._band = band
+        self.m_hash_table._band_launch = band is not None
         self.m_hash_table._per_cloud_norm = bool(per_cloud_norm) and bool(points_per_cloud)
         self.m_hash_table._per_cloud_invalid_vertex = bool(per_cloud_invalid_vertex) and bool(points_per_cloud)
         if self.m_hash_table.is_initialized():
@@ -1780,6 +1921,8 @@ class Lattice:
             raise _lib.LatticeNetHipError(f"hash table overflow: capacity {ht.capacity()} is too small for this cloud")
         if status & _lib.LN_STATUS_KEY_RANGE:
             raise _lib.LatticeNetHipError("a lattice key does not fit the packed 64-bit slot format (README: 'Key range')")
+        if status & _lib.LN_STATUS_CLOUD_BAND:
+            raise _lib.LatticeNetHipError(Lattice.band_violation_message(arr))
         if bound is not None and nr > bound:
             raise _lib.LatticeNetHipError(f"this cloud has {nr} lattice vertices but the static row bound is {bound}: rows beyond the "
                                           "bound were dropped from the convolution; raise the bound and re-capture")
@@ -1820,6 +1963,8 @@ class Lattice:
                     f"a lattice key does not fit the packed 64-bit slot format: pos_dim {d} leaves {bits} bits per coordinate, i.e. "
                     f"lattice coordinates within +-{reach} (about +-{reach / (d + 1) / 0.8165:.0f} sigmas from the "
                     "origin per axis); centre the positions or use larger sigmas (README: 'Key range')")
+            if status & _lib.LN_STATUS_CLOUD_BAND:
+                raise _lib.LatticeNetHipError(Lattice.band_violation_message(getattr(ht, "_pinned_np", None)))
             ht.m_nr_filled = nr
             ht.m_nr_filled_is_dirty = False
             if ht._storage is not None:
