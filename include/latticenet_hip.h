@@ -582,8 +582,12 @@ int ln_pointnet_reduce_backward(const float* grad_out, int grad_stride, const in
  * loss_count [2]: {loss = -sum lp[i, y_i] / max(count, 1), max(count, 1)} (count = labels not ignored); labels outside
  * [0, classes) are clamped, as in the gather formulation it replaces.  Backward writes every element of grad_log_probs [n, classes]:
  * -grad_loss / count at (i, y_i) of the labels that count, 0 elsewhere.  Sums in a fixed order (deterministic).
+ * This is the case of ONE cloud without class weights of ln_nll_forward_clouds / ln_nll_backward_clouds below, run by the same kernels
+ * (csrc/ln_nll.hip): loss_count[0] is that call's per_cloud[0], loss_count[1] its weight_sum[0], and no mean over the clouds is taken
+ * (one launch forward up to 1024 rows, two above; one backward).
  * n >= 0 (n == 0: loss 0, count 1; the backward writes nothing), classes >= 1, no null buffer, a workspace of at least
- * ln_nll_workspace_bytes() (all LN_ERR_ARG); a rejected call launches nothing. */
+ * ln_nll_workspace_bytes() (all LN_ERR_ARG); n >= 2^31 or n * classes >= 2^31 (LN_ERR_UNSUPPORTED: the kernels index with 32 bits,
+ * as every other loss entry point does); a rejected call launches nothing. */
 size_t ln_nll_workspace_bytes(void);
 int ln_nll_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index, void* workspace,
                    size_t workspace_bytes, float* loss_count, void* stream);
@@ -686,10 +690,10 @@ int ln_dice_backward(const float* log_probs, const long long* target, const floa
  * loss[0] = (sum_b per_cloud[b]) / B, the convention of ln_lovasz_forward_clouds and ln_dice_forward.  log_probs is read at the clamped
  * label of the rows that count and nowhere else, class_weight at the classes of such labels only: a -inf or NaN anywhere else reaches
  * no output.
- * Every sum in a fixed order, no float atomics.  Cloud b is summed as ln_nll_forward sums a call of the cloud's length (the same
- * workgroups, strides, shuffle trees and finishing order), so per_cloud[b] and weight_sum[b] are what this call gives on cloud b's rows
- * alone, bit for bit, and with class_weight == NULL they are the loss_count of ln_nll_forward on those rows.  The clouds are added
- * strided over 1024 threads in series, then by the fixed tree of that workgroup.
+ * Every sum in a fixed order, no float atomics.  The workgroups, strides, shuffle trees and finishing order of a cloud's sum depend on
+ * the cloud's rows alone, so per_cloud[b] and weight_sum[b] are what this call gives on cloud b's rows alone, bit for bit; with
+ * class_weight == NULL they are the loss_count of ln_nll_forward on those rows by construction: that entry point runs these kernels on
+ * one cloud.  The clouds are added strided over 1024 threads in series, then by the fixed tree of that workgroup.
  * ln_nll_backward_clouds (one elementwise launch) writes every element of grad_log_probs [n, classes]:
  * -grad_loss[0] w[y_i] / (B weight_sum[b]) at (i, clamped y_i) of the labels that count, 0 elsewhere; the caller does not zero the
  * buffer.  Called with the sizes, ignore_index and class_weight of the forward call.

@@ -24,7 +24,7 @@
 //                     stats [B, 3, C].  Per cloud: the class terms in class order, / C.  Then the clouds strided over the 256 threads in
 //                     series and the workgroup's fixed tree, / B.
 //   k_dice_backward   elementwise: grad[i, c] = -grad_loss p (y_i == c ? a - b : -b), every element written.
-#include "ln_common.h"
+#include "ln_loss_common.h"
 
 #define LN_DICE_THREADS 256
 #define LN_DICE_WAVES (LN_DICE_THREADS / 64)
@@ -62,8 +62,8 @@ template <bool WIDE>  // WIDE: C > 256
 __global__ void __launch_bounds__(LN_DICE_THREADS)
     k_dice_partials(const float* __restrict__ lp, const long long* __restrict__ target, long long n, long long n0, int C,
                     uint32_t* __restrict__ partial) {
-    const long long first = (long long)blockIdx.y * n0;
-    const long long len = n - first < n0 ? n - first : n0;
+    const LnCloudRange cloud = ln_cloud_range(n, n0, blockIdx.y);
+    const long long first = cloud.first, len = cloud.len;
     const LnDiceTiling T = ln_dice_tiling(len, C);
     if ((int)blockIdx.x >= T.tiles) return;  // (the whole workgroup)
     const long long row0 = (long long)blockIdx.x * T.tile_rows;
@@ -141,18 +141,6 @@ __global__ void __launch_bounds__(LN_DICE_THREADS)
     }
 }
 
-// fixed tree over a 256-thread workgroup: shuffle tree inside every wave, the four wave sums in order (valid in thread 0)
-__device__ __forceinline__ float ln_dice_block_sum(float x, float* s_w) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    float t = s_w[0];
-#pragma unroll
-    for (int w = 1; w < LN_DICE_WAVES; ++w) t += s_w[w];
-    return t;
-}
-
 // `terms` [B, C]: the class terms, written and read back by this workgroup alone (a barrier in between)
 __global__ void __launch_bounds__(LN_DICE_THREADS)
     k_dice_finish(const uint32_t* __restrict__ partial, long long n, long long n0, int C, int B, int grid_tiles, long long ignore_index,
@@ -162,8 +150,7 @@ __global__ void __launch_bounds__(LN_DICE_THREADS)
     const float Cf = float(C), Bf = float(B);
     for (long long item = threadIdx.x; item < (long long)B * C; item += LN_DICE_THREADS) {
         const int b = int(item / C), c = int(item - (long long)b * C);
-        const long long first = (long long)b * n0;
-        const int tiles = ln_dice_tiling(n - first < n0 ? n - first : n0, C).tiles;
+        const int tiles = ln_dice_tiling(ln_cloud_range(n, n0, b).len, C).tiles;
         const uint32_t* p = partial + (long long)b * grid_tiles * 3 * C + c;
         float I = 0.f, S = 0.f;
         uint32_t G = 0u;
@@ -209,7 +196,7 @@ __global__ void __launch_bounds__(LN_DICE_THREADS)
         if (per_cloud) per_cloud[b] = v;
         acc += v;
     }
-    const float total = ln_dice_block_sum(acc, s_w);
+    const float total = ln_block_sum_256(acc, s_w);
     if (threadIdx.x == 0) loss[0] = total / Bf;
 }
 
@@ -234,15 +221,14 @@ struct LnDiceLayout {
     int grid_tiles;
     size_t partial, terms, bytes;
 };
-// total: any argument gives a layout (negative sizes count as 0, points_per_cloud is brought into [1, max(n, 1)])
+// total: any argument gives a layout (ln_cloud_split)
 LnDiceLayout ln_dice_layout(long long n, long long points_per_cloud, int classes) {
     LnDiceLayout L;
-    const size_t N = n > 0 ? (n < (1ll << 31) ? size_t(n) : size_t(1) << 31) : 0;  // (2^31 rows and more are refused: any size will do)
-    const size_t P = points_per_cloud < 1 || N == 0 ? 1 : (size_t(points_per_cloud) > N ? N : size_t(points_per_cloud));
-    const size_t B = N == 0 ? 1 : (N + P - 1) / P;
+    const LnCloudSplit S = ln_cloud_split(n < (1ll << 31) ? n : 1ll << 31, points_per_cloud);  // (2^31 rows and more are refused: any size will do)
+    const size_t B = size_t(S.clouds);
     const int Cc = classes < 1 ? 1 : (classes > LN_DICE_MAX_CLASSES ? LN_DICE_MAX_CLASSES : classes);
-    L.n0 = (long long)P;
-    L.clouds = (long long)B;
+    L.n0 = S.n0;
+    L.clouds = S.clouds;
     L.grid_tiles = ln_dice_grid_tiles(L.n0, Cc);
     L.partial = 0;
     L.terms = (B * size_t(L.grid_tiles) * 3 * size_t(Cc) * 4 + 255) & ~size_t(255);

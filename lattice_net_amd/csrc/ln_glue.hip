@@ -197,102 +197,3 @@ extern "C" int ln_distribute_centre_clouds(const float* distributed, const int* 
                   splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_cloud, row_starts, clouds, out);
     return ln_check_launch("ln_distribute_centre_clouds");
 }
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Mean negative log-likelihood of the training loop (ln_train.py:130 torch.nn.NLLLoss(ignore_index=...)) over log-probabilities
-// [n, C] and labels [n]:  loss = -sum_i [y_i != ignore] lp[i, y_i] / max(#{y_i != ignore}, 1).
-// torch's own nll_loss reduces in one workgroup (0.14 ms at n = 120 k); written with gather / mean / their autograd it is ten
-// launches.  Here: per-workgroup partial sums in a fixed order + one finishing workgroup forward, one fully written [n, C]
-// gradient pass backward (no zero fill, no scatter).
-#define LN_NLL_BLOCKS 512
-
-__global__ void __launch_bounds__(256)
-    k_nll_partials(const float* __restrict__ lp, const long long* __restrict__ target, long long n, int C, long long ignore_index,
-                   float* __restrict__ partial) {
-    __shared__ float s_sum[4], s_cnt[4];
-    float acc = 0.f, cnt = 0.f;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const long long t = target[i];
-        if (t != ignore_index) {
-            const long long tc = t < 0 ? 0 : (t >= C ? C - 1 : t);  // (the torch formulation clamps out-of-range labels)
-            acc += lp[i * C + tc];
-            cnt += 1.f;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_down(acc, off, 64);
-        cnt += __shfl_down(cnt, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_sum[threadIdx.x >> 6] = acc;
-        s_cnt[threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        partial[2 * blockIdx.x + 1] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-    }
-}
-
-__global__ void __launch_bounds__(LN_NLL_BLOCKS)
-    k_nll_finish(const float* __restrict__ partial, int blocks, float* __restrict__ loss_count) {
-    __shared__ float s_sum[LN_NLL_BLOCKS / 64], s_cnt[LN_NLL_BLOCKS / 64];
-    float acc = threadIdx.x < blocks ? partial[2 * threadIdx.x] : 0.f;
-    float cnt = threadIdx.x < blocks ? partial[2 * threadIdx.x + 1] : 0.f;
-    for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_down(acc, off, 64);
-        cnt += __shfl_down(cnt, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_sum[threadIdx.x >> 6] = acc;
-        s_cnt[threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a = 0.f, c = 0.f;
-        for (int w = 0; w < LN_NLL_BLOCKS / 64; ++w) {
-            a += s_sum[w];
-            c += s_cnt[w];
-        }
-        loss_count[0] = -a / fmaxf(c, 1.f);
-        loss_count[1] = fmaxf(c, 1.f);
-    }
-}
-
-__global__ void __launch_bounds__(256)
-    k_nll_backward(const long long* __restrict__ target, const float* __restrict__ grad_loss, const float* __restrict__ loss_count, long long n,
-                   int C, long long ignore_index, float* __restrict__ grad_lp) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= n * C) return;
-    const long long i = g / C;
-    const int c = int(g - i * C);
-    const long long t = target[i];
-    const long long tc = t < 0 ? 0 : (t >= C ? C - 1 : t);
-    grad_lp[g] = (t != ignore_index && c == tc) ? -grad_loss[0] / loss_count[1] : 0.f;
-}
-
-extern "C" size_t ln_nll_workspace_bytes(void) { return (size_t)LN_NLL_BLOCKS * 2 * sizeof(float); }
-
-extern "C" int ln_nll_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index,
-                              void* workspace, size_t workspace_bytes, float* loss_count, void* stream) {
-    LN_REQUIRE(n >= 0 && classes >= 1, LN_ERR_ARG, "ln_nll_forward: bad sizes");
-    LN_REQUIRE(loss_count && workspace && workspace_bytes >= ln_nll_workspace_bytes(), LN_ERR_ARG, "ln_nll_forward: null buffer / small workspace");
-    LN_REQUIRE(n == 0 || (log_probs && target), LN_ERR_ARG, "ln_nll_forward: null buffer");
-    hipStream_t st = (hipStream_t)stream;
-    int blocks = ln_div_up(n, 256 * 4);
-    blocks = blocks < 1 ? 1 : (blocks > LN_NLL_BLOCKS ? LN_NLL_BLOCKS : blocks);
-    float* partial = static_cast<float*>(workspace);
-    LN_LAUNCH("k_nll_partials", k_nll_partials, dim3(blocks), dim3(256), 0, st, log_probs, target, n, classes, ignore_index, partial);
-    LN_LAUNCH("k_nll_finish", k_nll_finish, dim3(1), dim3(LN_NLL_BLOCKS), 0, st, partial, blocks, loss_count);
-    return ln_check_launch("ln_nll_forward");
-}
-
-extern "C" int ln_nll_backward(const long long* target, const float* grad_loss, const float* loss_count, long long n, int classes,
-                               long long ignore_index, float* grad_log_probs, void* stream) {
-    LN_REQUIRE(n >= 0 && classes >= 1, LN_ERR_ARG, "ln_nll_backward: bad sizes");
-    if (n == 0) return LN_OK;
-    LN_REQUIRE(target && grad_loss && loss_count && grad_log_probs, LN_ERR_ARG, "ln_nll_backward: null buffer");
-    LN_LAUNCH("k_nll_backward", k_nll_backward, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, target, grad_loss, loss_count,
-              n, classes, ignore_index, grad_log_probs);
-    return ln_check_launch("ln_nll_backward");
-}

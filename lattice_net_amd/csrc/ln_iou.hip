@@ -11,7 +11,7 @@
 //                         in the workspace with integer atomics.
 //   k_iou_finish_clouds   one thread per class walks the clouds and adds onto the two int64 accumulators (one writer per class).
 // Rows that hold a NaN are not held to torch's rule (torch.argmax returns the NaN's index; here a NaN never wins a comparison).
-#include "ln_common.h"
+#include "ln_loss_common.h"
 
 #define LN_IOU_THREADS 256
 #define LN_IOU_ROWS 256  // rows of a workgroup
@@ -32,8 +32,8 @@ __global__ void __launch_bounds__(LN_IOU_THREADS)
     k_iou_counts_clouds(const float* __restrict__ scores, const long long* __restrict__ target, long long n, long long n0, int C,
                         uint32_t* __restrict__ counts) {
     __shared__ uint32_t s_hit[LN_IOU_MAX_CLASSES], s_gt[LN_IOU_MAX_CLASSES], s_pred[LN_IOU_MAX_CLASSES];
-    const long long first = (long long)blockIdx.y * n0;
-    const long long len = n - first < n0 ? n - first : n0;
+    const LnCloudRange cloud = ln_cloud_range(n, n0, blockIdx.y);
+    const long long first = cloud.first, len = cloud.len;
     for (int k = threadIdx.x; k < C; k += LN_IOU_THREADS) s_hit[k] = s_gt[k] = s_pred[k] = 0u;
     __syncthreads();
     if (!WAVE_ROW) {
@@ -105,11 +105,8 @@ __global__ void __launch_bounds__(LN_IOU_THREADS)
 }
 
 namespace {
-// total: any argument gives a size (negative sizes count as 0, points_per_cloud below 1 as 1)
-size_t ln_iou_clouds(long long n, long long points_per_cloud) {
-    const size_t N = n > 0 ? size_t(n) : 0, P = points_per_cloud < 1 ? 1 : size_t(points_per_cloud);
-    return (N + P - 1) / P;
-}
+// total: any argument gives a size (ln_cloud_split); no rows, no cloud
+size_t ln_iou_clouds(long long n, long long points_per_cloud) { return n > 0 ? size_t(ln_cloud_split(n, points_per_cloud).clouds) : 0; }
 size_t ln_iou_counts_bytes(long long n, long long points_per_cloud, int classes) {
     return ln_iou_clouds(n, points_per_cloud) * 3 * (classes > 0 ? size_t(classes) : 0) * sizeof(uint32_t);
 }
@@ -125,7 +122,7 @@ extern "C" int ln_iou_counts_clouds(const float* scores, const long long* target
     LN_REQUIRE(n >= 0 && points_per_cloud >= 1 && classes >= 1 && classes <= LN_IOU_MAX_CLASSES, LN_ERR_ARG,
                "ln_iou_counts_clouds: bad sizes (n >= 0, points_per_cloud >= 1, 1 <= classes <= %d)", LN_IOU_MAX_CLASSES);
     LN_REQUIRE(n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_ARG, "ln_iou_counts_clouds: n * classes must stay below 2^31");
-    const long long n0 = points_per_cloud < n ? points_per_cloud : (n > 0 ? n : 1);
+    const long long n0 = ln_cloud_split(n, points_per_cloud).n0;
     const size_t clouds = ln_iou_clouds(n, n0);
     LN_REQUIRE(clouds <= LN_IOU_MAX_CLOUDS, LN_ERR_ARG, "ln_iou_counts_clouds: %zu clouds, at most %d (the cloud is the y coordinate of the grid)",
                clouds, LN_IOU_MAX_CLOUDS);

@@ -33,7 +33,7 @@
 // full: the buffers stay n C words), its tile histograms, tile counts and tile sums at  (b C + c) * tiles(n0);  the payload is the
 // point's index INSIDE its cloud.  The single-cloud call is the case n0 = n, B = 1 of the same launches.  k_lovasz_finish runs one
 // workgroup per cloud; k_lovasz_cloud_mean adds the clouds' losses in a fixed order and divides by B.  The gradient coefficient is divided by B.
-#include "ln_common.h"
+#include "ln_loss_common.h"
 
 #define LN_LV_THREADS 256
 #define LN_LV_WAVES (LN_LV_THREADS / 64)
@@ -64,8 +64,9 @@ struct LnLvSegment {
 };
 __device__ __forceinline__ LnLvSegment ln_lv_segment(long long n, long long n0, int C) {
     LnLvSegment s;
-    s.first = (long long)blockIdx.z * n0;
-    s.len = n - s.first < n0 ? n - s.first : n0;
+    const LnCloudRange cloud = ln_cloud_range(n, n0, blockIdx.z);
+    s.first = cloud.first;
+    s.len = cloud.len;
     s.base = s.first * C + (long long)blockIdx.y * s.len;
     s.id = (long long)blockIdx.z * C + blockIdx.y;
     return s;
@@ -228,18 +229,6 @@ __device__ __forceinline__ int ln_lv_counting(const int* __restrict__ G, int C, 
     return total;
 }
 
-// fixed tree over a 256-thread workgroup: shuffle tree inside every wave, the four wave sums in order (valid in thread 0)
-__device__ __forceinline__ float ln_lv_block_sum(float x, float* s_w) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    float t = s_w[0];
-#pragma unroll
-    for (int w = 1; w < LN_LV_WAVES; ++w) t += s_w[w];
-    return t;
-}
-
 __global__ void __launch_bounds__(LN_LV_THREADS)
     k_lovasz_dot(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pay, const uint32_t* __restrict__ fgbase,
                  const int* __restrict__ Gall, const float* __restrict__ lp, long long n, long long n0, int C, int nblk,
@@ -295,7 +284,7 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
         }
         dl[at] = coef;
     }
-    const float t = ln_lv_block_sum(acc, s_w);
+    const float t = ln_block_sum_256(acc, s_w);
     if (threadIdx.x == 0) partial[sg.id * nblk + b] = t;
 }
 
@@ -312,7 +301,7 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
     for (int c = 0; c < C; ++c) {
         float acc = 0.f;
         for (int k = threadIdx.x; k < nblk; k += LN_LV_THREADS) acc += partial[(long long)c * nblk + k];
-        const float pc = ln_lv_block_sum(acc, s_w);
+        const float pc = ln_block_sum_256(acc, s_w);
         if (threadIdx.x == 0) {
             const bool counts = G[c] > 0 && c != ignore_index;
             if (counts) {
@@ -335,7 +324,7 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
         acc += v;
         if (per_cloud) per_cloud[k] = v;
     }
-    const float t = ln_lv_block_sum(acc, s_w);
+    const float t = ln_block_sum_256(acc, s_w);
     if (threadIdx.x == 0) loss[0] = t / float(B);
 }
 
@@ -353,12 +342,11 @@ struct LnLovaszLayout {
     size_t keys[2], pay[2], hist, fgcnt, G, partial, cloud, bytes;
 };
 size_t ln_lv_align(size_t x) { return (x + 255) & ~size_t(255); }
-// total: any argument gives a layout (negative sizes count as 0, points_per_cloud is brought into [1, max(n, 1)])
+// total: any argument gives a layout (ln_cloud_split)
 LnLovaszLayout ln_lv_layout(long long n, long long points_per_cloud, int classes, bool per_cloud) {
     LnLovaszLayout L;
-    const size_t N = n > 0 ? size_t(n) : 0;
-    const size_t P = points_per_cloud < 1 || N == 0 ? 1 : (size_t(points_per_cloud) > N ? N : size_t(points_per_cloud));
-    const size_t B = N == 0 ? 1 : (N + P - 1) / P;
+    const LnCloudSplit split = ln_cloud_split(n, points_per_cloud);
+    const size_t N = n > 0 ? size_t(n) : 0, P = size_t(split.n0), B = size_t(split.clouds);
     const size_t C = classes > 0 ? size_t(classes) : 0, S = C * B;  // classes, segments
     L.n0 = (long long)P;
     L.clouds = (long long)B;

@@ -1,7 +1,9 @@
-// Class-weighted mean negative log-likelihood PER CLOUD of a cloud-major batch (torch.nn.NLLLoss(weight=, ignore_index=) on every cloud,
-// the mean over the clouds), forward value and the gradient wrt the log-probabilities.  The single-cloud, unweighted loss of the
-// training loop stays where it is (ln_nll_forward / ln_nll_backward, ln_glue.hip); this file repeats its partition and its trees, so a
-// cloud is summed exactly as ln_nll_forward sums a call of that cloud's length.
+// Mean negative log-likelihood of a cloud-major batch, forward value and the gradient wrt the log-probabilities: every NLL kernel of the
+// library.  Two forward entry points into one host function (ln_nllc_forward), two backward ones into another:
+//   ln_nll_forward_clouds / ln_nll_backward_clouds   class weights, per cloud (torch.nn.NLLLoss(weight=, ignore_index=) on every cloud, the
+//                                                    mean over the clouds);
+//   ln_nll_forward / ln_nll_backward                 the loss of the training loop: one cloud of all n rows, no weights, no mean over the
+//                                                    clouds — per_cloud and weight_sum are the two words of loss_count.
 //
 // Cloud b owns rows [b n0, min((b + 1) n0, n)), B = ceil(n / n0).  A label counts when it differs from ignore_index; labels outside
 // [0, C) are clamped and take the weight of the class they clamp to; w = 1 without class weights.  Per cloud
@@ -10,27 +12,30 @@
 //     d loss / d lp[i, y_i] = -grad_loss w[y_i] / (B D_b)  on the counted rows, 0 everywhere else.
 // log_probs is read at (counted row, clamped label) only and class_weight at the clamped label of a counted row only.
 //
-// Arithmetic, pinned so that tests/nll_clouds_reference.py can count its roundings and repeat its order: every sum in a fixed order, no
-// float atomics, IEEE division, no contraction (-ffp-contract=off).  A cloud of len rows is cut as ln_nll_forward cuts n = len rows:
+// Arithmetic, pinned so that tests/glue_reference.py (nll_emulate_cloud) can count its roundings and repeat its order: every sum in a
+// fixed order, no float atomics, IEEE division, no contraction (-ffp-contract=off).  A cloud of len rows is cut into
 // blocks = clamp(ceil(len / 1024), 1, 512) workgroups of 256 threads, grid-stride by blocks * 256, the shuffle tree of a wave,
-// (s0 + s1) + (s2 + s3) over the four waves, then the finish of k_nll_finish: partial t in lane t of a 512-lane layout, the shuffle
-// tree of each of its 8 waves, the 8 wave totals added in order from 0.
+// (s0 + s1) + (s2 + s3) over the four waves, then the finish: partial t in lane t of a 512-lane layout, the shuffle tree of each of its
+// 8 waves, the 8 wave totals added in order from 0.  The sum depends on the cloud's rows alone: a cloud of a batch and a one-cloud call of
+// the same rows run the same code and give the same bits.
 //
 //   k_nll_clouds_wave      n0 <= 64: a wave per cloud, four clouds per workgroup, no LDS and no barrier.  One row per lane; the other three
 //                          waves of the 256-thread layout and the 511 other lanes of the finish would add +0, which changes no bit (an
-//                          accumulator that starts at +0 is never -0).  Writes per_cloud / weight_sum itself.
+//                          accumulator that starts at +0 is never -0).  Writes per_cloud / weight_sum itself.  A cloud of no rows (the
+//                          one-cloud entry at n = 0) reads nothing and publishes -0 / 1.
 //   k_nll_clouds_partials  grid (blocks of the longest cloud, clouds): a workgroup takes part of ONE cloud; workgroups behind a cloud's
 //                          last block leave.  n0 <= 1024 (one block per cloud): writes per_cloud / weight_sum itself, by the same
 //                          argument; otherwise one (N, W) partial per workgroup.
-//   k_nll_clouds_finish    16 waves.  Phase 1 (n0 > 1024): a wave per cloud, the finish of k_nll_finish by 8 loads per lane and 8 shuffle
-//                          trees, no LDS.  Phase 2: the clouds strided over the 1024 threads in series, the shuffle tree of every wave, the
-//                          16 wave totals in order, / B.  Up to LN_NLLC_FUSED_CLOUDS clouds one workgroup runs both phases (two launches
-//                          forward, as ln_nll_forward); more clouds of more than 1024 rows take phase 1 on a grid and phase 2 in a
-//                          launch of its own.
+//   k_nll_clouds_finish    16 waves.  Phase 1 (n0 > 1024): a wave per cloud, the finish above by 8 loads per lane and 8 shuffle trees, no
+//                          LDS.  Phase 2: the clouds strided over the 1024 threads in series, the shuffle tree of every wave, the 16 wave
+//                          totals in order, / B.  Up to LN_NLLC_FUSED_CLOUDS clouds one workgroup runs both phases (two launches
+//                          forward); more clouds of more than 1024 rows take phase 1 on a grid and phase 2 in a launch of its own.  The
+//                          one-cloud entry never runs phase 2: its sum starts from +0 and would turn the -0 of a call without a counted
+//                          label into +0.
 //   k_nll_clouds_backward  elementwise, every element of [n, C] written.
-#include "ln_common.h"
+#include "ln_loss_common.h"
 
-#define LN_NLLC_BLOCKS 512        // LN_NLL_BLOCKS of ln_glue.hip
+#define LN_NLLC_BLOCKS 512        // workgroups of a cloud at the most; ln_nll_workspace_bytes holds their partials
 #define LN_NLLC_THREADS 256
 #define LN_NLLC_ROWS_PER_BLOCK 1024
 #define LN_NLLC_WAVE_ROWS 64      // clouds up to this many rows: a wave per cloud
@@ -39,7 +44,7 @@
 #define LN_NLLC_FUSED_CLOUDS 64   // clouds whose phase 1 the single finishing workgroup takes (4 per wave)
 #define LN_NLLC_MAX_CLOUDS 65535  // grid y
 
-// blocks of a cloud of len rows: those of ln_nll_forward for n = len
+// blocks of a cloud of len rows
 LN_HD int ln_nllc_blocks(long long len) {
     const long long b = (len + LN_NLLC_ROWS_PER_BLOCK - 1) / LN_NLLC_ROWS_PER_BLOCK;
     return b < 1 ? 1 : (b > LN_NLLC_BLOCKS ? LN_NLLC_BLOCKS : int(b));
@@ -64,7 +69,7 @@ __device__ __forceinline__ void ln_nllc_row(const float* __restrict__ lp, const 
 }
 
 __device__ __forceinline__ void ln_nllc_publish(float a, float w, float* __restrict__ per_cloud, float* __restrict__ weight_sum, int b) {
-    const float d = w != 0.f ? w : 1.f;  // (without weights: max(count, 1), as k_nll_finish)
+    const float d = w != 0.f ? w : 1.f;  // (without weights: max(count, 1))
     per_cloud[b] = -a / d;
     weight_sum[b] = d;
 }
@@ -76,10 +81,9 @@ __global__ void __launch_bounds__(LN_NLLC_THREADS)
     const int b = blockIdx.x * (LN_NLLC_THREADS / 64) + (threadIdx.x >> 6);
     if (b >= B) return;  // (the whole wave; the kernel has no barrier)
     const int lane = threadIdx.x & 63;
-    const long long first = (long long)b * n0;
-    const long long len = n - first < n0 ? n - first : n0;
+    const LnCloudRange cloud = ln_cloud_range(n, n0, b);
     float acc = 0.f, wsum = 0.f;
-    if (lane < len) ln_nllc_row<WEIGHTED>(lp, target, first + lane, C, ignore_index, cw, acc, wsum);
+    if (lane < cloud.len) ln_nllc_row<WEIGHTED>(lp, target, cloud.first + lane, C, ignore_index, cw, acc, wsum);
     for (int off = 32; off > 0; off >>= 1) {
         acc += __shfl_down(acc, off, 64);
         wsum += __shfl_down(wsum, off, 64);
@@ -94,13 +98,12 @@ __global__ void __launch_bounds__(LN_NLLC_THREADS)
                           float* __restrict__ weight_sum) {
     constexpr bool WEIGHTED = (MODE & 1) != 0, DIRECT = (MODE & 2) != 0;
     __shared__ float s_sum[4], s_cnt[4];
-    const long long first = (long long)blockIdx.y * n0;
-    const long long len = n - first < n0 ? n - first : n0;
-    const int blocks = ln_nllc_blocks(len);
+    const LnCloudRange cloud = ln_cloud_range(n, n0, blockIdx.y);
+    const int blocks = ln_nllc_blocks(cloud.len);
     if ((int)blockIdx.x >= blocks) return;  // (the whole workgroup)
     float acc = 0.f, wsum = 0.f;
-    for (long long i = (long long)blockIdx.x * LN_NLLC_THREADS + threadIdx.x; i < len; i += (long long)blocks * LN_NLLC_THREADS)
-        ln_nllc_row<WEIGHTED>(lp, target, first + i, C, ignore_index, cw, acc, wsum);
+    for (long long i = (long long)blockIdx.x * LN_NLLC_THREADS + threadIdx.x; i < cloud.len; i += (long long)blocks * LN_NLLC_THREADS)
+        ln_nllc_row<WEIGHTED>(lp, target, cloud.first + i, C, ignore_index, cw, acc, wsum);
     for (int off = 32; off > 0; off >>= 1) {
         acc += __shfl_down(acc, off, 64);
         wsum += __shfl_down(wsum, off, 64);
@@ -130,8 +133,7 @@ __global__ void __launch_bounds__(LN_NLLC_FINISH_THREADS)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (MODE & 1) {
         for (int b = blockIdx.x * LN_NLLC_FINISH_WAVES + wave; b < B; b += gridDim.x * LN_NLLC_FINISH_WAVES) {
-            const long long first = (long long)b * n0;
-            const int blocks = ln_nllc_blocks(n - first < n0 ? n - first : n0);
+            const int blocks = ln_nllc_blocks(ln_cloud_range(n, n0, b).len);
             const float* p = partial + (long long)b * grid_blocks * 2;
             float x[LN_NLLC_BLOCKS / 64], y[LN_NLLC_BLOCKS / 64];
 #pragma unroll
@@ -174,8 +176,8 @@ __global__ void __launch_bounds__(LN_NLLC_FINISH_THREADS)
 
 // x / d for 0 <= x < 2^31 and 1 <= d < 2^31 as a multiplication and a shift (Granlund & Montgomery 1994, N = 31): with l = ceil(log2 d)
 // and m = ceil(2^(31 + l) / d) < 2^32,  2^(31 + l) <= m d < 2^(31 + l) + 2^l,  so  floor(x m / 2^(31 + l)) = floor(x / d).  The backward
-// divides every element index twice (row, cloud); with two runtime divisions it took 7.1 us at 120 000 x 20 on an MI355X (k_nll_backward,
-// one division: 5.7 us), like this 5.4 us.
+// divides every element index twice (row, cloud); with two runtime divisions it took 7.1 us at 120 000 x 20 on an MI355X (a one-cloud
+// kernel with one runtime division: 5.7 us), like this 5.4 us.
 struct LnDivU31 {
     unsigned m;
     int shift;
@@ -205,6 +207,7 @@ __global__ void __launch_bounds__(256)
     grad_lp[g] = v;
 }
 
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct LnNllcLayout {
@@ -212,12 +215,12 @@ struct LnNllcLayout {
     int grid_blocks;       // blocks of the longest cloud
     size_t bytes;
 };
-// total: any argument gives a layout (negative sizes count as 0, points_per_cloud is brought into [1, max(n, 1)])
+// total: any argument gives a layout (ln_cloud_split)
 LnNllcLayout ln_nllc_layout(long long n, long long points_per_cloud) {
     LnNllcLayout L;
-    const long long N = n > 0 ? (n < (1ll << 31) ? n : (1ll << 31)) : 0;  // (2^31 rows and more are refused: any size will do)
-    L.n0 = points_per_cloud < 1 || N == 0 ? 1 : (points_per_cloud > N ? N : points_per_cloud);
-    L.clouds = N == 0 ? 1 : (N + L.n0 - 1) / L.n0;
+    const LnCloudSplit S = ln_cloud_split(n < (1ll << 31) ? n : 1ll << 31, points_per_cloud);  // (2^31 rows and more are refused: any size will do)
+    L.n0 = S.n0;
+    L.clouds = S.clouds;
     L.grid_blocks = ln_nllc_blocks(L.n0);
     // clouds of one block publish their sums themselves: no partials
     L.bytes = 256 + (L.grid_blocks > 1 ? ((size_t(L.clouds) * size_t(L.grid_blocks) * 2 * sizeof(float) + 255) & ~size_t(255)) : 0);
@@ -232,24 +235,13 @@ int ln_nllc_sizes(const char* who, long long n, long long points_per_cloud, int 
                who, L.clouds, LN_NLLC_MAX_CLOUDS);
     return LN_OK;
 }
-}  // namespace
 
-extern "C" size_t ln_nll_clouds_workspace_bytes(long long n, long long points_per_cloud) { return ln_nllc_layout(n, points_per_cloud).bytes; }
-
-extern "C" int ln_nll_forward_clouds(const float* log_probs, const long long* target, long long n, long long points_per_cloud, int classes,
-                                     long long ignore_index, const float* class_weight, void* workspace, size_t workspace_bytes, float* loss,
-                                     float* per_cloud, float* weight_sum, void* stream) {
-    LnNllcLayout L;
-    const int rc = ln_nllc_sizes("ln_nll_forward_clouds", n, points_per_cloud, classes, L);
-    if (rc != LN_OK) return rc;
-    LN_REQUIRE(loss, LN_ERR_ARG, "ln_nll_forward_clouds: null buffer");
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) return ln_zero_async(loss, sizeof(float), st);  // no cloud: the loss is 0; per_cloud and weight_sum have no element
-    LN_REQUIRE(log_probs && target && per_cloud && weight_sum, LN_ERR_ARG, "ln_nll_forward_clouds: null buffer");
-    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_nll_forward_clouds: null / small workspace (%zu bytes needed)", L.bytes);
-    float* partial = static_cast<float*>(workspace);
+// Both forward entry points, their arguments checked.  loss == nullptr: the one-cloud entry, which takes no mean over the clouds (phase 2).
+int ln_nllc_forward(const char* who, const float* log_probs, const long long* target, long long n, const LnNllcLayout& L, int classes,
+                    long long ignore_index, const float* class_weight, float* partial, float* loss, float* per_cloud, float* weight_sum,
+                    hipStream_t st) {
     const int B = int(L.clouds);
-    const bool direct = L.grid_blocks == 1;
+    const bool direct = L.grid_blocks == 1, mean = loss != nullptr;
     if (L.n0 <= LN_NLLC_WAVE_ROWS) {
         const dim3 grid(ln_div_up(B, LN_NLLC_THREADS / 64)), thr(LN_NLLC_THREADS);
         if (class_weight)
@@ -276,15 +268,49 @@ extern "C" int ln_nll_forward_clouds(const float* log_probs, const long long* ta
 #define LN_NLLC_FINISH(MODE, GRID) \
     LN_LAUNCH("k_nll_clouds_finish", k_nll_clouds_finish<MODE>, dim3(GRID), fthr, 0, st, partial, n, L.n0, B, L.grid_blocks, per_cloud, weight_sum, loss)
     if (direct) {
-        LN_NLLC_FINISH(2, 1);
+        if (mean) LN_NLLC_FINISH(2, 1);
     } else if (B <= LN_NLLC_FUSED_CLOUDS) {
-        LN_NLLC_FINISH(3, 1);
+        if (mean) LN_NLLC_FINISH(3, 1);
+        else LN_NLLC_FINISH(1, 1);
     } else {
         LN_NLLC_FINISH(1, ln_div_up(B, LN_NLLC_FINISH_WAVES));
-        LN_NLLC_FINISH(2, 1);
+        if (mean) LN_NLLC_FINISH(2, 1);
     }
 #undef LN_NLLC_FINISH
-    return ln_check_launch("ln_nll_forward_clouds");
+    return ln_check_launch(who);
+}
+
+// Both backward entry points, their arguments checked and n > 0.
+int ln_nllc_backward(const char* who, const long long* target, const float* grad_loss, const float* weight_sum, long long n,
+                     const LnNllcLayout& L, int classes, long long ignore_index, const float* class_weight, float* grad_log_probs,
+                     hipStream_t st) {
+    const dim3 grid(ln_div_up(n * classes, 256)), thr(256);
+    const LnDivU31 by_n0 = ln_div_u31(L.n0), by_C = ln_div_u31(classes);  // (1 <= n0 <= n < 2^31, 1 <= classes <= n * classes < 2^31)
+    if (class_weight)
+        LN_LAUNCH("k_nll_clouds_backward", k_nll_clouds_backward<true>, grid, thr, 0, st, target, grad_loss, weight_sum, int(n * classes), by_n0,
+                  by_C, classes, int(L.clouds), ignore_index, class_weight, grad_log_probs);
+    else
+        LN_LAUNCH("k_nll_clouds_backward", k_nll_clouds_backward<false>, grid, thr, 0, st, target, grad_loss, weight_sum, int(n * classes), by_n0,
+                  by_C, classes, int(L.clouds), ignore_index, class_weight, grad_log_probs);
+    return ln_check_launch(who);
+}
+}  // namespace
+
+extern "C" size_t ln_nll_clouds_workspace_bytes(long long n, long long points_per_cloud) { return ln_nllc_layout(n, points_per_cloud).bytes; }
+
+extern "C" int ln_nll_forward_clouds(const float* log_probs, const long long* target, long long n, long long points_per_cloud, int classes,
+                                     long long ignore_index, const float* class_weight, void* workspace, size_t workspace_bytes, float* loss,
+                                     float* per_cloud, float* weight_sum, void* stream) {
+    LnNllcLayout L;
+    const int rc = ln_nllc_sizes("ln_nll_forward_clouds", n, points_per_cloud, classes, L);
+    if (rc != LN_OK) return rc;
+    LN_REQUIRE(loss, LN_ERR_ARG, "ln_nll_forward_clouds: null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) return ln_zero_async(loss, sizeof(float), st);  // no cloud: the loss is 0; per_cloud and weight_sum have no element
+    LN_REQUIRE(log_probs && target && per_cloud && weight_sum, LN_ERR_ARG, "ln_nll_forward_clouds: null buffer");
+    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_nll_forward_clouds: null / small workspace (%zu bytes needed)", L.bytes);
+    return ln_nllc_forward("ln_nll_forward_clouds", log_probs, target, n, L, classes, ignore_index, class_weight, static_cast<float*>(workspace),
+                           loss, per_cloud, weight_sum, st);
 }
 
 extern "C" int ln_nll_backward_clouds(const long long* target, const float* grad_loss, const float* weight_sum, long long n,
@@ -295,13 +321,32 @@ extern "C" int ln_nll_backward_clouds(const long long* target, const float* grad
     if (rc != LN_OK) return rc;
     if (n == 0) return LN_OK;
     LN_REQUIRE(target && grad_loss && weight_sum && grad_log_probs, LN_ERR_ARG, "ln_nll_backward_clouds: null buffer");
-    const dim3 grid(ln_div_up(n * classes, 256)), thr(256);
-    const LnDivU31 by_n0 = ln_div_u31(L.n0), by_C = ln_div_u31(classes);  // (1 <= n0 <= n < 2^31, 1 <= classes <= n * classes < 2^31)
-    if (class_weight)
-        LN_LAUNCH("k_nll_clouds_backward", k_nll_clouds_backward<true>, grid, thr, 0, (hipStream_t)stream, target, grad_loss, weight_sum,
-                  int(n * classes), by_n0, by_C, classes, int(L.clouds), ignore_index, class_weight, grad_log_probs);
-    else
-        LN_LAUNCH("k_nll_clouds_backward", k_nll_clouds_backward<false>, grid, thr, 0, (hipStream_t)stream, target, grad_loss, weight_sum,
-                  int(n * classes), by_n0, by_C, classes, int(L.clouds), ignore_index, class_weight, grad_log_probs);
-    return ln_check_launch("ln_nll_backward_clouds");
+    return ln_nllc_backward("ln_nll_backward_clouds", target, grad_loss, weight_sum, n, L, classes, ignore_index, class_weight, grad_log_probs,
+                            (hipStream_t)stream);
+}
+
+// The one-cloud, unweighted entry: points_per_cloud = n.  One size serves every n: the partials of one cloud.
+extern "C" size_t ln_nll_workspace_bytes(void) { return (size_t)LN_NLLC_BLOCKS * 2 * sizeof(float); }
+
+extern "C" int ln_nll_forward(const float* log_probs, const long long* target, long long n, int classes, long long ignore_index,
+                              void* workspace, size_t workspace_bytes, float* loss_count, void* stream) {
+    LnNllcLayout L;
+    const int rc = ln_nllc_sizes("ln_nll_forward", n, n > 0 ? n : 1, classes, L);
+    if (rc != LN_OK) return rc;
+    LN_REQUIRE(loss_count && workspace && workspace_bytes >= ln_nll_workspace_bytes(), LN_ERR_ARG, "ln_nll_forward: null buffer / small workspace");
+    LN_REQUIRE(n == 0 || (log_probs && target), LN_ERR_ARG, "ln_nll_forward: null buffer");
+    // (n = 0: a wave over a cloud of no rows writes -0 and 1)
+    return ln_nllc_forward("ln_nll_forward", log_probs, target, n, L, classes, ignore_index, nullptr, static_cast<float*>(workspace), nullptr,
+                           loss_count, loss_count + 1, (hipStream_t)stream);
+}
+
+extern "C" int ln_nll_backward(const long long* target, const float* grad_loss, const float* loss_count, long long n, int classes,
+                               long long ignore_index, float* grad_log_probs, void* stream) {
+    LnNllcLayout L;
+    const int rc = ln_nllc_sizes("ln_nll_backward", n, n > 0 ? n : 1, classes, L);
+    if (rc != LN_OK) return rc;
+    if (n == 0) return LN_OK;
+    LN_REQUIRE(target && grad_loss && loss_count && grad_log_probs, LN_ERR_ARG, "ln_nll_backward: null buffer");
+    return ln_nllc_backward("ln_nll_backward", target, grad_loss, loss_count + 1, n, L, classes, ignore_index, nullptr, grad_log_probs,
+                            (hipStream_t)stream);
 }

@@ -32,6 +32,25 @@ _LOVASZ_MAX_ELEMENTS = 1 << 31
 _LOVASZ_MAX_CLOUDS = 65535  # of ln_lovasz_forward_clouds and ln_iou_counts_clouds
 
 
+def _label_or_none(ignore_index) -> int:
+    """ignore_index as the kernels take it."""
+    return _NO_LABEL if ignore_index is None else int(ignore_index)
+
+
+def _checked_points_per_cloud(points_per_cloud):
+    """The points_per_cloud argument of a loss's constructor: None or an int >= 1."""
+    if points_per_cloud is None:
+        return None
+    if int(points_per_cloud) < 1:
+        raise ValueError("points_per_cloud >= 1")
+    return int(points_per_cloud)
+
+
+def _clouds_ok(n, points_per_cloud) -> bool:
+    """The batch has no more clouds than the kernels take (None: one cloud)."""
+    return points_per_cloud is None or -(-n // points_per_cloud) <= _LOVASZ_MAX_CLOUDS
+
+
 def _lovasz_fused_ok(inputs, targets) -> bool:
     """The inputs LovaszSoftmax hands to the kernels (reduction "mean" or "sum"), while FUSED_LOVASZ is set."""
     return FUSED_LOVASZ and _kernel_inputs(inputs, targets)
@@ -49,8 +68,9 @@ def _dice_fused_ok(inputs, targets) -> bool:
 
 
 class _NllFunction(torch.autograd.Function):
-    """csrc/ln_glue.hip: two launches forward (partial sums in a fixed order, one finishing workgroup), one backward that writes the
-    whole [n, C] gradient — instead of gather / mean and the zero fill + scatter of their autograd."""
+    """csrc/ln_nll.hip, its one-cloud entry without class weights: at most two launches forward (partial sums in a fixed order, one
+    finishing workgroup), one backward that writes the whole [n, C] gradient — instead of gather / mean and the zero fill + scatter of
+    their autograd."""
 
     @staticmethod
     def forward(ctx, log_probs, target, ignore_index):
@@ -167,7 +187,7 @@ class _DiceFunction(torch.autograd.Function):
 
 class _NllCloudsFunction(torch.autograd.Function):
     """csrc/ln_nll.hip: the class-weighted NLL of every cloud of a cloud-major batch and the mean over the clouds — two launches forward
-    (the clouds' sums cut and added as ln_nll_forward does a call of a cloud's length, then the mean in a fixed order), one backward
+    (the clouds' sums, each cut and added by the kernels that serve ln_nll_forward on a cloud's rows, then the mean in a fixed order), one backward
     that writes the whole [n, C] gradient.  weight None: every class 1.  points_per_cloud >= n: one cloud."""
 
     @staticmethod
@@ -250,16 +270,17 @@ def nll_loss_gather(log_probs: torch.Tensor, target: torch.Tensor, ignore_index=
         if n0 < 1:
             raise ValueError("points_per_cloud >= 1")
         if FUSED_NLL_CLOUDS and log_probs.is_cuda and log_probs.dtype == torch.float32 and target.is_cuda and target.dtype == torch.int64 and \
-                n > 0 and log_probs.numel() < _LOVASZ_MAX_ELEMENTS and -(-n // n0) <= _LOVASZ_MAX_CLOUDS:
+                n > 0 and log_probs.numel() < _LOVASZ_MAX_ELEMENTS and _clouds_ok(n, n0):
             w = weight
             if w is not None and not (w.device == log_probs.device and w.dtype == torch.float32 and w.dim() == 1 and w.is_contiguous() and
                                       not w.requires_grad):  # (the buffer of NLLLoss on the model's device passes as it is)
                 w = w.detach().to(device=log_probs.device, dtype=torch.float32).reshape(-1).contiguous()
-            return _NllCloudsFunction.apply(log_probs, target.contiguous(), _NO_LABEL if ignore_index is None else int(ignore_index), w, n0)
+            return _NllCloudsFunction.apply(log_probs, target.contiguous(), _label_or_none(ignore_index), w, n0)
         return _nll_clouds_torch(log_probs, target, ignore_index, None if weight is None else weight.detach().reshape(-1), n0)
     if FUSED_NLL and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 2 and target.is_cuda and \
-            target.dtype == torch.int64 and target.shape[0] == log_probs.shape[0] and log_probs.shape[0] > 0:
-        return _NllFunction.apply(log_probs, target.contiguous(), _NO_LABEL if ignore_index is None else int(ignore_index))
+            target.dtype == torch.int64 and target.shape[0] == log_probs.shape[0] and log_probs.shape[0] > 0 and \
+            log_probs.numel() < _LOVASZ_MAX_ELEMENTS:  # (the limit of ln_nll_forward; beyond it the torch form)
+        return _NllFunction.apply(log_probs, target.contiguous(), _label_or_none(ignore_index))
     picked = log_probs.gather(1, target.clamp(0, log_probs.shape[1] - 1).unsqueeze(1)).squeeze(1)
     if ignore_index is None:
         return -picked.mean()
@@ -282,13 +303,9 @@ class NLLLoss(torch.nn.Module):
 
     def __init__(self, weight=None, ignore_index=None, points_per_cloud=None):
         super().__init__()
-        if points_per_cloud is not None:
-            if int(points_per_cloud) < 1:
-                raise ValueError("points_per_cloud >= 1")
-            points_per_cloud = int(points_per_cloud)
         self.register_buffer("weight", None if weight is None else torch.as_tensor(weight).detach().clone().reshape(-1))
         self.ignore_index = ignore_index
-        self.points_per_cloud = points_per_cloud
+        self.points_per_cloud = _checked_points_per_cloud(points_per_cloud)
 
     def forward(self, log_probs: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         if log_probs.dim() != 2:
@@ -313,11 +330,7 @@ class GeneralizedSoftDiceLoss(torch.nn.Module):
         super().__init__()
         self.p, self.smooth, self.reduction = p, smooth, reduction  # accepted and unused, as in the reference
         self.ignore_index = ignore_index
-        if points_per_cloud is not None:
-            if int(points_per_cloud) < 1:
-                raise ValueError("points_per_cloud >= 1")
-            points_per_cloud = int(points_per_cloud)
-        self.points_per_cloud = points_per_cloud
+        self.points_per_cloud = _checked_points_per_cloud(points_per_cloud)
 
     def _forward_clouds_torch(self, output, target):
         """The single-cloud form batched as [B_full, C, n0] plus a [1, C, rest] term for a shorter last cloud; shapes depend on sizes
@@ -346,9 +359,8 @@ class GeneralizedSoftDiceLoss(torch.nn.Module):
 
     def forward(self, output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         target = target.reshape(-1)
-        if _dice_fused_ok(output, target) and (self.points_per_cloud is None or
-                                               -(-output.shape[0] // self.points_per_cloud) <= _LOVASZ_MAX_CLOUDS):
-            return _DiceFunction.apply(output, target.contiguous(), _NO_LABEL if self.ignore_index is None else int(self.ignore_index),
+        if _dice_fused_ok(output, target) and _clouds_ok(output.shape[0], self.points_per_cloud):
+            return _DiceFunction.apply(output, target.contiguous(), _label_or_none(self.ignore_index),
                                        output.shape[0] if self.points_per_cloud is None else self.points_per_cloud)
         if self.points_per_cloud is not None:
             if output.dim() != 2:
@@ -389,15 +401,11 @@ class LovaszSoftmax(torch.nn.Module):
 
     def __init__(self, ignore_index, reduction: str = "mean", points_per_cloud=None):
         super().__init__()
-        if points_per_cloud is not None:
-            if reduction not in ("mean", "sum"):
-                raise ValueError("LovaszSoftmax(points_per_cloud=) needs reduction 'mean' or 'sum': the classes present differ from cloud to cloud")
-            if int(points_per_cloud) < 1:
-                raise ValueError("points_per_cloud >= 1")
-            points_per_cloud = int(points_per_cloud)
+        if points_per_cloud is not None and reduction not in ("mean", "sum"):
+            raise ValueError("LovaszSoftmax(points_per_cloud=) needs reduction 'mean' or 'sum': the classes present differ from cloud to cloud")
         self.ignore_index = ignore_index
         self.reduction = reduction
-        self.points_per_cloud = points_per_cloud
+        self.points_per_cloud = _checked_points_per_cloud(points_per_cloud)
 
     def _keep(self, c, device):
         """[C] mask of the classes that may count, or None (no host scalar: safe inside a stream capture)"""
@@ -439,14 +447,13 @@ class LovaszSoftmax(torch.nn.Module):
         if self.points_per_cloud is not None:
             if self.reduction not in ("mean", "sum"):  # (also when it was reassigned after construction)
                 raise ValueError("LovaszSoftmax(points_per_cloud=) needs reduction 'mean' or 'sum'")
-            if _lovasz_fused_ok(inputs, targets) and -(-inputs.shape[0] // self.points_per_cloud) <= _LOVASZ_MAX_CLOUDS:
-                return _LovaszCloudsFunction.apply(inputs, targets.reshape(-1).contiguous(),
-                                                   _NO_LABEL if self.ignore_index is None else int(self.ignore_index),
+            if _lovasz_fused_ok(inputs, targets) and _clouds_ok(inputs.shape[0], self.points_per_cloud):
+                return _LovaszCloudsFunction.apply(inputs, targets.reshape(-1).contiguous(), _label_or_none(self.ignore_index),
                                                    0 if self.reduction == "mean" else 1, self.points_per_cloud)
             return self._forward_clouds_torch(inputs, targets.reshape(-1))
         if self.reduction in ("mean", "sum") and _lovasz_fused_ok(inputs, targets):
             # equal errors are ordered by point index and the Jaccard gradient is taken in closed form (csrc/ln_lovasz.hip)
-            return _LovaszFunction.apply(inputs, targets.reshape(-1).contiguous(), _NO_LABEL if self.ignore_index is None else int(self.ignore_index),
+            return _LovaszFunction.apply(inputs, targets.reshape(-1).contiguous(), _label_or_none(self.ignore_index),
                                          0 if self.reduction == "mean" else 1)
         probs = inputs.exp()
         n, c = probs.shape
@@ -525,7 +532,7 @@ class Scores:
         clouds = -(-n // n0)
         if FUSED_IOU_COUNTS and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and gt.is_cuda and \
                 gt.dtype == torch.int64 and gt.numel() == n and 1 <= c <= _LOVASZ_MAX_CLASSES and scores.numel() < _LOVASZ_MAX_ELEMENTS and \
-                clouds <= _LOVASZ_MAX_CLOUDS and self.intersection_per_class.is_cuda:
+                _clouds_ok(n, n0) and self.intersection_per_class.is_cuda:
             from . import _lib
             lib = _lib.load()
             scores, gt = scores.contiguous(), gt.contiguous()

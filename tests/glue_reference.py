@@ -1,5 +1,6 @@
-"""fp64 references, per-element error bounds and fp32 emulations for two parts of csrc/ln_glue.hip: weight normalisation
-(k_weight_norm_forward / k_weight_norm_backward) and the fused mean NLL loss (k_nll_partials / k_nll_finish / k_nll_backward).
+"""fp64 references, per-element error bounds and fp32 emulations for the weight normalisation of csrc/ln_glue.hip
+(k_weight_norm_forward / k_weight_norm_backward) and the fused mean NLL loss of one cloud, ln_nll_forward / ln_nll_backward of
+csrc/ln_nll.hip (k_nll_clouds_wave / k_nll_clouds_partials / k_nll_clouds_finish / k_nll_clouds_backward on one cloud).
 Plain NumPy on the CPU, in the vocabulary of dense_reference.py: test_glue_reference.py checks this module without a GPU,
 test_gpu_weight_norm_nll.py holds the kernels to it.
 
@@ -10,6 +11,9 @@ roots and divisions: sqrtf and `/` count one rounding each.  Counts are first-or
 largest k here is about 8200 (the 2^24-element parameter), where the second-order term is 5e-4 of the bound.
 
 Both references take the fp32 inputs converted exactly to fp64."""
+import json
+import os
+
 import numpy as np
 
 from tests.dense_reference import EPS32, assert_within, f32, f64, worst_ratio
@@ -18,6 +22,7 @@ from tests.dense_reference import EPS32, assert_within, f32, f64, worst_ratio
 LN_WN_THREADS = 1024
 LN_WN_MAX_G = 1024
 LN_WN_MAX_ELEMENTS = 1 << 24
+# csrc/ln_nll.hip (LN_NLLC_BLOCKS, LN_NLLC_THREADS, LN_NLLC_ROWS_PER_BLOCK / LN_NLLC_THREADS)
 LN_NLL_BLOCKS = 512
 LN_NLL_THREADS = 256
 LN_NLL_PER_THREAD = 4  # blocks = ceil(n / (256 * 4)), at least 1, at most LN_NLL_BLOCKS
@@ -238,15 +243,16 @@ def nll_blocks(n):
 
 
 def nll_count(n):
-    """Roundings on the way to the loss: `acc +=` ceil(n / (blocks * 256)) times per thread of k_nll_partials, its shuffle tree (6) and
-    (s0 + s1) + (s2 + s3) (3 adds, 2 on any path; counted 3); in k_nll_finish the shuffle tree (6) and the 8 wave totals (8); the
-    division.  The count of live labels is a sum of ones: exact in fp32 up to 2^24."""
+    """Roundings on the way to the loss: `acc +=` ceil(n / (blocks * 256)) times per thread of k_nll_clouds_partials, its shuffle tree (6)
+    and (s0 + s1) + (s2 + s3) (3 adds, 2 on any path; counted 3); in k_nll_clouds_finish the shuffle tree (6) and the 8 wave totals (8); the
+    division.  (Up to 1024 rows the finish, up to 64 the four waves too, are left out: they would add zeros, and the count stays an upper
+    bound.)  The count of live labels is a sum of ones: exact in fp32 up to 2^24."""
     return _ceil_div(max(n, 1), nll_blocks(n) * LN_NLL_THREADS) + 6 + 3 + 6 + 8 + 1
 
 
 def nll_labels(target, classes, ignore_index):
     """(live, clamped): labels equal to ignore_index are skipped (whatever their value, in range or not); the others are clamped to
-    [0, classes - 1] — the semantics of k_nll_partials / k_nll_backward and of the gather formulation in losses.nll_loss_gather."""
+    [0, classes - 1] — the semantics of the kernels of csrc/ln_nll.hip and of the gather formulation in losses.nll_loss_gather."""
     target = np.asarray(target, dtype=np.int64).reshape(-1)
     live = np.ones(target.shape, bool) if ignore_index is None else target != int(ignore_index)
     return live, np.clip(target, 0, classes - 1)
@@ -273,29 +279,34 @@ def nll_loss_bound(n, count, sum_abs):
     return nll_count(n) * EPS32 * sum_abs / count
 
 
-def nll_emulate(lp, target, ignore_index=None):
-    """k_nll_partials + k_nll_finish in fp32 NumPy: (loss, count)."""
-    lp = f32(lp)
-    n, classes = lp.shape
-    target = np.asarray(target, dtype=np.int64).reshape(-1)
-    live, tc = nll_labels(target, classes, ignore_index)
+def nll_emulate_cloud(val, wts):
+    """The fixed-order sum of one cloud (k_nll_clouds_partials + phase 1 of k_nll_clouds_finish; the one-workgroup and the one-wave
+    forms leave out steps that add +0) in fp32: val / wts [len] hold what a row adds to the two accumulators (0 where the label does
+    not count: adding +0 to an accumulator that started at +0 changes no bit).  Returns (N, W) as fp32."""
+    n = val.shape[0]
     blocks = nll_blocks(n)
     per_trip = blocks * LN_NLL_THREADS
     trips = max(_ceil_div(n, per_trip), 1)
-    val = np.zeros(trips * per_trip, np.float32)
-    cnt = np.zeros(trips * per_trip, np.float32)
+    out = []
+    for x in (val, wts):
+        buf = np.zeros(trips * per_trip, np.float32)
+        buf[:n] = x
+        s = _wave_tree(_chain(buf.reshape(trips, blocks, LN_NLL_THREADS // 64, 64)))  # [blocks, 4]
+        partial = np.zeros(LN_NLL_BLOCKS, np.float32)
+        partial[:blocks] = (s[:, 0] + s[:, 1]) + (s[:, 2] + s[:, 3])
+        out.append(_chain(_wave_tree(partial.reshape(LN_NLL_BLOCKS // 64, 64))[:, None])[0])
+    return out
+
+
+def nll_emulate(lp, target, ignore_index=None):
+    """ln_nll_forward in fp32 NumPy, the case of one cloud without weights of nll_clouds_reference.emulate: (loss, count)."""
+    lp = f32(lp)
+    n, classes = lp.shape
+    live, tc = nll_labels(target, classes, ignore_index)
     with np.errstate(all="ignore"):
-        val[:n] = np.where(live, lp[np.arange(n), tc], np.float32(0))  # (a skipped row adds nothing: acc is never -0)
-        cnt[:n] = live
-        acc = _chain(val.reshape(trips, blocks, LN_NLL_THREADS // 64, 64))
-        c = _chain(cnt.reshape(trips, blocks, LN_NLL_THREADS // 64, 64))
-        s, sc = _wave_tree(acc), _wave_tree(c)  # [blocks, 4]
-        partial = np.zeros((2, LN_NLL_BLOCKS), np.float32)
-        partial[0, :blocks] = (s[:, 0] + s[:, 1]) + (s[:, 2] + s[:, 3])
-        partial[1, :blocks] = (sc[:, 0] + sc[:, 1]) + (sc[:, 2] + sc[:, 3])
-        waves = _wave_tree(partial.reshape(2, LN_NLL_BLOCKS // 64, 64))  # [2, 8]
-        a, c = _chain(waves[0][:, None])[0], _chain(waves[1][:, None])[0]
-        c = np.maximum(c, np.float32(1))
+        val = np.where(live, lp[np.arange(n), tc], np.float32(0)).astype(np.float32)  # (a skipped row adds nothing: acc is never -0)
+        a, c = nll_emulate_cloud(val, live.astype(np.float32))
+        c = c if c != 0 else np.float32(1)
         return np.float32(-a / c), np.float32(c)
 
 
@@ -346,6 +357,23 @@ def nll_exact_case(n, classes, ignore_index=-100):
         if not np.array_equal(np.asarray(r).astype(np.float32).astype(np.float64), r):
             return None
     return lp, target, 3.0, ref
+
+
+NLL_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nll_one_cloud_bits.json")
+
+
+def nll_golden_cases():
+    """What ln_nll_forward / ln_nll_backward wrote on an MI355X while they still had kernels of their own in ln_glue.hip, recorded bit for
+    bit: n across every form boundary (wave, one workgroup, partials and finish) x classes x ignore_index, and per n a case with every
+    label ignored (loss -0).  Yields (case, lp, target, grad_loss); case["loss_count"]: two uint32 words, case["grad_sha256"]: of the
+    bytes of the float32 gradient [n, classes]."""
+    with open(NLL_GOLDEN) as f:
+        golden = json.load(f)
+    for case in golden["cases"]:
+        lp, target = nll_random_case(case["n"], case["classes"], case["ignore"], case["seed"])
+        if case["all_ignored"]:
+            target = np.full(case["n"], case["ignore"], np.int64)
+        yield case, lp, target, golden["grad_loss"]
 
 
 # the shapes test_gpu_weight_norm_nll.py runs (test_glue_reference.py runs the emulation at the same ones)

@@ -1,6 +1,6 @@
 """fp64 reference, counted error bounds and an fp32 emulation for the per-cloud, class-weighted NLL loss of csrc/ln_nll.hip
-(ln_nll_forward_clouds / ln_nll_backward_clouds).  Plain NumPy on the CPU, in the vocabulary of glue_reference.py, whose NLL partition
-(nll_blocks) and trees (_wave_tree, _chain) it reuses: test_nll_clouds_reference.py checks this module without a GPU,
+(ln_nll_forward_clouds / ln_nll_backward_clouds).  Plain NumPy on the CPU, in the vocabulary of glue_reference.py, whose fp32 emulation of a
+cloud's sum (nll_emulate_cloud) and partition (nll_blocks) it uses — ln_nll_forward is the one-cloud entry into the same kernels: test_nll_clouds_reference.py checks this module without a GPU,
 test_gpu_nll_clouds.py holds the kernels to it.
 
 Per cloud b (rows [b n0, min((b + 1) n0, n)), B = ceil(n / n0)), over the labels that count (y_i != ignore_index; labels outside
@@ -27,7 +27,7 @@ import numpy as np
 
 from tests.dense_reference import EPS32, assert_within, f32, f64, worst_ratio
 from tests.glue_reference import (LN_ERR_ARG, LN_ERR_UNSUPPORTED, LN_NLL_BLOCKS, LN_NLL_THREADS, LN_OK, NO_LABEL, _ceil_div, _chain,  # noqa: F401
-                                  _wave_tree, nll_blocks, nll_labels)
+                                  _wave_tree, nll_blocks, nll_emulate_cloud, nll_labels)
 
 # csrc/ln_nll.hip
 LN_NLLC_WAVE_ROWS = 64        # clouds up to this many rows: a wave per cloud
@@ -153,24 +153,6 @@ def check(got, lp, target, n0, ignore_index, weight, what="", grad_loss=1.0, ref
 
 
 # ------------------------------------------------------------------------------------------------------------------ fp32 emulation
-def _emulate_cloud(val, wts):
-    """k_nll_partials + k_nll_finish on one cloud, in fp32: val / wts [len] hold what a row adds to the two accumulators (0 where the
-    label does not count: adding +0 to an accumulator that started at +0 changes no bit).  Returns (N, W) as fp32."""
-    n = val.shape[0]
-    blocks = nll_blocks(n)
-    per_trip = blocks * LN_NLL_THREADS
-    trips = max(_ceil_div(n, per_trip), 1)
-    out = []
-    for x in (val, wts):
-        buf = np.zeros(trips * per_trip, np.float32)
-        buf[:n] = x
-        s = _wave_tree(_chain(buf.reshape(trips, blocks, LN_NLL_THREADS // 64, 64)))  # [blocks, 4]
-        partial = np.zeros(LN_NLL_BLOCKS, np.float32)
-        partial[:blocks] = (s[:, 0] + s[:, 1]) + (s[:, 2] + s[:, 3])
-        out.append(_chain(_wave_tree(partial.reshape(LN_NLL_BLOCKS // 64, 64))[:, None])[0])
-    return out
-
-
 def emulate(lp, target, n0, ignore_index=None, weight=None, grad_loss=1.0):
     """The kernels in fp32 NumPy: the same partition, strides, trees and finishing order, every operator rounded to fp32."""
     lp = f32(lp)
@@ -190,7 +172,7 @@ def emulate(lp, target, n0, ignore_index=None, weight=None, grad_loss=1.0):
             val, wts = np.zeros(hi - lo, np.float32), np.zeros(hi - lo, np.float32)
             val[rows - lo] = lp[rows, cls] if w32 is None else w * lp[rows, cls]
             wts[rows - lo] = w
-            N, W = _emulate_cloud(val, wts)
+            N, W = nll_emulate_cloud(val, wts)
             D = W if W != 0 else np.float32(1)
             per_cloud[b], weight_sum[b] = -N / D, D
             d = np.float32(B) * D

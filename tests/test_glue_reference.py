@@ -222,3 +222,15 @@ def test_every_nll_exact_case_is_representable_and_the_emulation_reproduces_it()
         assert np.array_equal(grad.astype(np.float32).astype(np.float64), grad)
         got_loss, got_count = G.nll_emulate(lp, target, -100)
         assert float(got_loss) == loss and float(got_count) == count, (n, classes)
+
+
+def test_nll_emulation_reproduces_the_recorded_bits_of_the_one_cloud_call():
+    """tests/golden/nll_one_cloud_bits.json (glue_reference.nll_golden_cases): the emulation of a cloud's sum gives the two loss_count
+    words the kernels of the earlier, separate one-cloud family wrote, the sign of a zero loss included."""
+    cases = 0
+    for case, lp, target, _ in G.nll_golden_cases():
+        loss, count = G.nll_emulate(lp, target, case["ignore"])
+        got = np.array([loss, count], np.float32).view(np.uint32)
+        assert [int(got[0]), int(got[1])] == case["loss_count"], (case, got)
+        cases += 1
+    assert cases == 9 * (3 * 3 + 1)

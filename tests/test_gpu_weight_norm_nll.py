@@ -1,5 +1,5 @@
-"""Weight normalisation (ln_weight_norm_forward / _backward) and the fused mean NLL loss (ln_nll_forward / _backward) of
-csrc/ln_glue.hip against fp64, element by element (`pytest -m gpu`).
+"""Weight normalisation (ln_weight_norm_forward / _backward, csrc/ln_glue.hip) and the fused mean NLL loss of one cloud (ln_nll_forward /
+_backward, the one-cloud entry of csrc/ln_nll.hip) against fp64, element by element (`pytest -m gpu`).
 
 References, bounds and their counting arguments live in tests/glue_reference.py (checked on the CPU by test_glue_reference.py, which
 also runs an fp32 emulation of the kernels' summation order through the same bounds).  Every raw call writes into buffers that sit
@@ -8,6 +8,8 @@ call.  Each family prints its worst error / bound ratios (`pytest -s`); nothing 
 
 Not held: ||v|| outside 2^-20 .. 2^20 times the drawn scale (n^3 leaves the normal fp32 range around 2^+-42), more than 2^24 live
 labels (the fp32 count stops being exact) and n * classes >= 2^31 (more than 8 GB of log-probabilities)."""
+import hashlib
+
 import numpy as np
 import pytest
 import torch
@@ -309,6 +311,20 @@ def test_nll_exact(n):
         loss_count, grad = nll_run(lp, target, -100, grad_loss, what=f"exact n={n} C={classes}")
         assert_within(loss_count, np.array([loss, count]), 0.0, f"exact n={n} C={classes} loss_count")
         assert_within(grad, grad_ref, 0.0, f"exact n={n} C={classes} grad")
+
+
+def test_nll_reproduces_the_recorded_bits_of_the_earlier_kernels():
+    """tests/golden/nll_one_cloud_bits.json (glue_reference.nll_golden_cases): loss_count word for word, the sign of a zero loss
+    included, and the gradient byte for byte, at every n around the boundaries between the wave, the one-workgroup and the partials +
+    finish forms; n = 0 with null log_probs / target."""
+    cases = 0
+    for case, lp, target, grad_loss in G.nll_golden_cases():
+        loss_count, grad = nll_run(lp, target, case["ignore"], grad_loss, what=str(case))
+        got = loss_count.view(np.uint32)
+        assert [int(got[0]), int(got[1])] == case["loss_count"], (case, got)
+        assert hashlib.sha256(np.ascontiguousarray(grad).tobytes()).hexdigest() == case["grad_sha256"], case
+        cases += 1
+    assert cases == 9 * (3 * 3 + 1)
 
 
 @pytest.mark.parametrize("n", [1, 257, 524289])
