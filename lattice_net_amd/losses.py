@@ -18,7 +18,7 @@ import os
 
 import torch
 
-__all__ = ["GeneralizedSoftDiceLoss", "LovaszSoftmax", "NLLLoss", "Scores", "nll_loss_gather"]
+__all__ = ["GeneralizedSoftDiceLoss", "LovaszSoftmax", "NLLLoss", "Scores", "SegmentationLoss", "log_softmax", "nll_loss_gather"]
 
 
 _NO_LABEL = -(1 << 62)  # "no ignore_index": a value no label takes
@@ -219,6 +219,11 @@ class _NllCloudsFunction(torch.autograd.Function):
                                                       ctx.ignore_index, None if weight is None else _lib.ptr(weight), _lib.ptr(grad),
                                                       _lib.stream_ptr(g.device)), "ln_nll_backward_clouds")
         return grad, None, None, None, None
+
+
+def log_softmax(logits: torch.Tensor) -> torch.Tensor:
+    """torch.log_softmax(logits, 1) of [N, C] logits: the one place where the losses of this module turn logits into log-probabilities."""
+    return torch.log_softmax(logits, 1)
 
 
 def _nll_clouds_torch(log_probs, target, ignore_index, weight, points_per_cloud):
@@ -482,6 +487,35 @@ class LovaszSoftmax(torch.nn.Module):
         if self.reduction == "sum":
             return total
         return total / present.sum().clamp(min=1)
+
+
+class SegmentationLoss(torch.nn.Module):
+    """The loss of the training step from LOGITS [N, C] (ln_train.py:128-158):
+        lovasz_weight LovaszSoftmax(ignore_index)(lp, t) + nll_weight NLLLoss(weight=class_weight, ignore_index=)(lp, t),  lp = log_softmax(logits),
+    points_per_cloud as in the two modules: the mean over the clouds of a cloud-major batch.  A loss whose weight is 0 is not computed.
+    LovaszSoftmax and NLLLoss are composed over losses.log_softmax, so each takes its kernels wherever it does on its own; any device,
+    any float dtype, inside a stream capture."""
+
+    def __init__(self, ignore_index, lovasz_weight=0.5, nll_weight=0.5, class_weight=None, points_per_cloud=None):
+        super().__init__()
+        self.ignore_index = ignore_index
+        self.lovasz_weight, self.nll_weight = float(lovasz_weight), float(nll_weight)
+        self.points_per_cloud = _checked_points_per_cloud(points_per_cloud)
+        self.lovasz = LovaszSoftmax(ignore_index, "mean", points_per_cloud=points_per_cloud)
+        self.nll = NLLLoss(weight=class_weight, ignore_index=ignore_index, points_per_cloud=points_per_cloud)
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if logits.dim() != 2:
+            raise ValueError("SegmentationLoss expects [N, C] logits")
+        target = target.reshape(-1)
+        lp = log_softmax(logits)
+        total = None
+        if self.lovasz_weight != 0:
+            total = self.lovasz_weight * self.lovasz(lp, target)
+        if self.nll_weight != 0:
+            term = self.nll_weight * self.nll(lp, target)
+            total = term if total is None else total + term
+        return lp.sum() * 0.0 if total is None else total
 
 
 class Scores:
