@@ -42,6 +42,7 @@ extern "C" {
 #define LN_STATUS_BUCKET_OVERFLOW 4 /* bucketed build: one LDS-staged bucket filled up; nothing of this build is valid,
                                        re-run it with LN_BUILD_ATOMIC_PATH (whose inserts spill past a full bucket) */
 #define LN_STATUS_CLOUD_BAND 8      /* a cloud of a batch leaves its key band (set by ln_cloud_key_extents, never by a build) */
+#define LN_STATUS_CLOUD_STARTS 16   /* LnTableClouds.batch_point_starts is not an ascending list from 0 to n (set by ln_cloud_point_starts_check) */
 
 #define LN_MAX_POS_DIM 6
 #define LN_SLOT_MAP_INTS 32 /* ints behind LnTable.slot_map */
@@ -96,7 +97,7 @@ typedef struct LnTable {
                                       buckets (LN_STATUS_BUCKET_OVERFLOW -> rebuild on the atomic path, whose inserts spill); a fitting
                                       one comes from the host's calibration (Lattice.balanced_region_planes).  csrc/ln_common.h */
     int bucket_slots_max;          /* with a slot map: the largest of its slots-per-bucket entries (sizes the LDS of the bucket pass) */
-    int batch_points;              /* 0, or > 0: the positions handed to a build / retrieval of this table are a BATCH of independent clouds
+    int batch_points;              /* 0, > 0, or LN_BATCH_POINT_STARTS (clouds of unequal sizes, see LnTableClouds below).  > 0: the positions handed to a build / retrieval of this table are a BATCH of independent clouds
                                       of batch_points points each (cloud c = point index / batch_points).  Cloud c's lattice keys are then
                                       shifted by c * batch_key_step on the first coordinate — a multiple of pos_dim + 1, i.e. a translation
                                       of the lattice onto itself — so that the clouds' vertex sets are disjoint in ONE table and every kernel
@@ -107,6 +108,24 @@ typedef struct LnTable {
     int* row_regions;              /* NULL, or LN_XCD_GROUPS + 1 device ints a bucketed build over a space-ordered table fills: the first row
                                       of each of the 8 top-level kd regions and the row count — the `row_partition` argument of the convolutions */
 } LnTable;
+
+/* A batch of clouds of UNEQUAL sizes: an LnTable with a tail.  LnTable itself keeps its layout; a table whose batch_points is
+ * LN_BATCH_POINT_STARTS is the first member of an LnTableClouds, and every entry point that takes the cloud of a point from the table
+ * (ln_build_splat, ln_distribute, ln_slice_no_precomputation, ln_cloud_key_extents) reads the tail: pass &clouds.table.  Any other
+ * batch_points (0: no batch, > 0: equal sizes) means a plain LnTable, nothing behind it is read, and everything is what it was.
+ *   batch_point_starts  batch_clouds + 1 device ints: ascending, starts[0] = 0, starts[batch_clouds] = n; cloud c is the points
+ *                       [starts[c], starts[c + 1]) and may be empty.  The cloud of point p is upper_bound(starts, p) - 1, found by a
+ *                       binary search (csrc/ln_simplex.h); batch_key_step keeps its meaning.  A kernel only compares against these ints
+ *                       and clamps what it takes from them to [0, n]: a list that breaks the rules gives wrong clouds, never an access
+ *                       out of bounds (ln_cloud_point_starts_check tells).
+ *   batch_clouds        >= 1.
+ * A null list or batch_clouds < 1 behind LN_BATCH_POINT_STARTS is LN_ERR_ARG, nothing launched. */
+#define LN_BATCH_POINT_STARTS (-1) /* LnTable.batch_points: the sizes come from the LnTableClouds this table heads */
+typedef struct LnTableClouds {
+    LnTable table;
+    const int* batch_point_starts;
+    int batch_clouds;
+} LnTableClouds;
 
 /* Adjacency "group -> the tokens that touch it" in CSR form, cut into segments of at most 16
  * entries (the unit of work of ln_csr_reduce_rows).  A group is a hash slot for the CSR that
@@ -552,6 +571,12 @@ int ln_distribute_centre(const float* distributed, const int* splat_idx, const f
 int ln_distribute_centre_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
                                 long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts, int clouds,
                                 float* out, void* stream);
+/* ln_distribute_centre_clouds for clouds of unequal sizes (LnTableClouds.batch_point_starts): token t belongs to point t / tokens_per_point
+ * (tokens_per_point = lattice pos_dim + 1 >= 1) and the point to cloud upper_bound(point_starts, point) - 1, point_starts device int32
+ * [clouds + 1] as in LnTable.  Everything else, the refusals included, as above; point_starts == NULL is LN_ERR_ARG. */
+int ln_distribute_centre_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                      long long tokens, int width, int pos_dim, int tokens_per_point, const int* point_starts,
+                                      const int* row_starts, int clouds, float* out, void* stream);
 
 /* The vertex-side reduction of PointNetModule (lattice_modules.py:688-712: scatter_max, scatter_add of ones, index_select of the
  * winning tokens' barycentric weights, cat, masked_fill(nr_points < 4), keep mask of vertex 0) over the token adjacency `csr`:
@@ -711,15 +736,18 @@ int ln_nll_backward_clouds(const long long* target, const float* grad_loss, cons
                            int classes, long long ignore_index, const float* class_weight, float* grad_log_probs, void* stream);
 
 /* Band check of a batch of clouds in one table (LnTable.batch_points / batch_key_step): a launch sequence of its own, queued on `stream`
- * behind the build of `t` from the same positions and sigmas; the build kernels are not involved.  B = ceil(n / batch_points) clouds.
+ * behind the build of `t` from the same positions and sigmas; the build kernels are not involved.  B = ceil(n / batch_points) clouds, or,
+ * for a table that heads an LnTableClouds, its batch_clouds clouds with the point ranges of its batch_point_starts (every cloud reduces
+ * its own range, clamped to [0, n]).
  * extents [B, 2] int32 receives, per cloud, the smallest and the largest FIRST key coordinate over the d + 1 simplex vertices of every
  * point of the cloud, before the cloud's shift (an empty cloud keeps (INT_MAX, INT_MIN)); integer atomics only: order-independent and
  * bitwise reproducible.  With half = batch_key_step >> 1, cloud c is inside its band when -half + guard <= lo_c and hi_c < half - guard;
  * an empty cloud is inside.  *first_bad receives the smallest offending cloud, INT_MAX when there is none.  On a violation
  * LN_STATUS_CLOUD_BAND is ORed into *t->status and, when t->host_counters is set, the report word of the build is stored again with the
- * bit in it (*t->nr_filled | *t->status << 32 | host_seq << 40: pass the LnTable the build was given).  Three launches, no host
- * synchronisation, no allocation: safe inside a stream capture.
- * Refused, nothing launched or written: a null table, buffer or sigmas, a table without a batch (batch_points <= 0), n < 0, guard < 0,
+ * bit in it (*t->nr_filled | *t->status << 32 | host_seq << 40: pass the LnTable the build was given).  For an LnTableClouds, the
+ * report word is stored again as well when *t->status holds LN_STATUS_CLOUD_STARTS (ln_cloud_point_starts_check queued in front of this
+ * call): both bits travel to the host the same way.  Three launches, no host synchronisation, no allocation: safe inside a stream capture.
+ * Refused, nothing launched or written: a null table, buffer or sigmas, a table without a batch (batch_points == 0), n < 0, guard < 0,
  * guard >= half — LN_ERR_ARG; pos_dim outside 1..LN_MAX_POS_DIM, B > 65535 (the cloud is the y coordinate of the grid) —
  * LN_ERR_UNSUPPORTED.  n == 0 launches and writes nothing.
  *
@@ -738,6 +766,11 @@ int ln_nll_backward_clouds(const long long* target, const float* grad_loss, cons
  *  larger dilations or more levels need (1 + 2^L)(d + 1) + dilation 2^L d. */
 int ln_cloud_key_extents(const LnTable* t, const float* positions_raw, const float* sigmas_host, int n, int guard, int* extents,
                          int* first_bad, void* stream);
+/* Verifies on the device what LnTableClouds.batch_point_starts promises about `starts` (device int32 [clouds + 1]) for n points: starts[0] == 0,
+ * starts[clouds] == n, starts[c] <= starts[c + 1].  One launch of one workgroup; on a violation LN_STATUS_CLOUD_STARTS is ORed into
+ * *status (device int32, the table's status word), else nothing is written.  No host synchronisation, no allocation: safe inside a
+ * stream capture.  Refused, nothing launched or written: null starts or status, clouds < 1, n < 0 — LN_ERR_ARG. */
+int ln_cloud_point_starts_check(const int* starts, int clouds, int n, int* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ LN_STATUS_TABLE_FULL = 1
 LN_STATUS_KEY_RANGE = 2
 LN_STATUS_BUCKET_OVERFLOW = 4
 LN_STATUS_CLOUD_BAND = 8
+LN_STATUS_CLOUD_STARTS = 16
 LN_BUILD_WRITE_IDX = 1
 LN_BUILD_CLEAR_FIRST = 2
 LN_BUILD_ATOMIC_PATH = 4
@@ -56,6 +57,24 @@ class LnTable(C.Structure):
         ("batch_key_step", C.c_int),
         ("row_regions", C.c_void_p),
     ]
+
+
+LN_BATCH_POINT_STARTS = -1  # LnTable.batch_points of a table that heads an LnTableClouds
+
+
+class LnTableClouds(C.Structure):
+    """Mirror of `struct LnTableClouds`: an LnTable with the point starts of a batch of clouds of unequal sizes behind it.  Pass
+    C.byref(x.table) where an LnTable is wanted; x.table.batch_points is LN_BATCH_POINT_STARTS."""
+
+    _fields_ = [
+        ("table", LnTable),
+        ("batch_point_starts", C.c_void_p),
+        ("batch_clouds", C.c_int),
+    ]
+
+    def __init__(self, table_fields=(), batch_point_starts=None, batch_clouds=0):
+        super().__init__(LnTable(*table_fields), batch_point_starts, batch_clouds)
+        self.table.batch_points = LN_BATCH_POINT_STARTS
 
 
 class LnCsr(C.Structure):
@@ -142,6 +161,7 @@ SIGNATURES = {
     "ln_weight_norm_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ln_distribute_centre": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp]),
     "ln_distribute_centre_clouds": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _ll, _vp, _i, _vp, _vp]),
+    "ln_distribute_centre_cloud_starts": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "ln_pointnet_reduce_workspace_bytes": (_sz, [_i, _i]),
     "ln_pointnet_reduce_forward": (_i, [_CSR, _vp, _ll, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "ln_pointnet_reduce_forward_clouds": (_i, [_CSR, _vp, _ll, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp]),
@@ -180,6 +200,7 @@ SIGNATURES = {
     "ln_batch_norm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_cloud_key_extents": (_i, [_T, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "ln_cloud_point_starts_check": (_i, [_vp, _i, _i, _vp, _vp]),
     "ln_slice_classify_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ln_slice_classify_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }

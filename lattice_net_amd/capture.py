@@ -304,6 +304,8 @@ class CapturedNetworkStep:
             nr, status = Lattice.decode_report(word[0])
             if status & (_lib.LN_STATUS_BUCKET_OVERFLOW | _lib.LN_STATUS_TABLE_FULL | _lib.LN_STATUS_KEY_RANGE):
                 raise _lib.LatticeNetHipError(f"replayed build of lattice level {level} failed (status bits {status}): redo this cloud eagerly")
+            if status & _lib.LN_STATUS_CLOUD_STARTS:
+                raise _lib.LatticeNetHipError(f"replayed build of lattice level {level}: " + Lattice.CLOUD_STARTS_MESSAGE)
             if status & _lib.LN_STATUS_CLOUD_BAND:
                 raise _lib.LatticeNetHipError(f"replayed build of lattice level {level}: " + Lattice.band_violation_message(word))
             if nr > bound:

@@ -13,6 +13,7 @@
 //        out[t, :D] = d[t, :D] - sums[idx[t]] / max(count[idx[t]], 1),  out[t, D:] = d[t, D:]     (idx[t] > 0; zeros otherwise)
 //    in one pass instead of div / clamp / index_select / sub / cat / eq / masked_fill.
 #include "ln_common.h"
+#include "ln_simplex.h"
 
 #define LN_WN_THREADS 1024
 #define LN_WN_MAX_G 1024
@@ -196,4 +197,49 @@ extern "C" int ln_distribute_centre_clouds(const float* distributed, const int* 
         LN_LAUNCH("k_distribute_centre_clouds", k_distribute_centre_clouds<long long>, grid, dim3(256), 0, (hipStream_t)stream, distributed,
                   splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_cloud, row_starts, clouds, out);
     return ln_check_launch("ln_distribute_centre_clouds");
+}
+
+// Clouds of unequal sizes (LnTableClouds.batch_point_starts): the cloud of token t is that of its point t / tokens_per_point, found by the
+// binary search of the key pass (ln_cloud_of_point: reads inside the list and returns a cloud in [0, clouds) whatever the list holds).
+template <typename IDX>
+__global__ void __launch_bounds__(256)
+    k_distribute_centre_cloud_starts(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
+                                     const int* __restrict__ counts, long long tokens, int width, int pos_dim, int tokens_per_point,
+                                     const int* __restrict__ point_starts, const int* __restrict__ row_starts, int clouds,
+                                     float* __restrict__ out) {
+    const long long i64 = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i64 >= tokens * width) return;
+    const IDX i = (IDX)i64;
+    const IDX t = i / (IDX)width;
+    const int c = int(i - t * (IDX)width);
+    const int first = row_starts[ln_cloud_of_point(point_starts, clouds, int(t / (IDX)tokens_per_point))];
+    const int row = idx[t];
+    float x = 0.f;
+    if (row >= 0 && row != first) {
+        x = d[i64];
+        if (c < pos_dim) x -= sums[(size_t)row * pos_dim + c] / (float)max(counts[row], 1);
+    }
+    out[i64] = x;
+}
+
+extern "C" int ln_distribute_centre_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                                 long long tokens, int width, int pos_dim, int tokens_per_point, const int* point_starts,
+                                                 const int* row_starts, int clouds, float* out, void* stream) {
+    LN_REQUIRE(tokens >= 0 && width >= 1 && pos_dim >= 0 && pos_dim <= width && tokens_per_point >= 1, LN_ERR_ARG,
+               "ln_distribute_centre_cloud_starts: bad sizes");
+    LN_REQUIRE(tokens / tokens_per_point <= 0x7fffffffll, LN_ERR_ARG, "ln_distribute_centre_cloud_starts: more than 2^31 points");
+    LN_REQUIRE(clouds >= 1 && clouds <= LN_CLOUDS_MAX, LN_ERR_UNSUPPORTED, "ln_distribute_centre_cloud_starts: 1 <= clouds <= %d (got %d)",
+               LN_CLOUDS_MAX, clouds);
+    LN_REQUIRE(point_starts != nullptr, LN_ERR_ARG, "ln_distribute_centre_cloud_starts: null point_starts");
+    if (tokens == 0) return LN_OK;
+    LN_REQUIRE(distributed && splat_idx && position_sums && counts && row_starts && out, LN_ERR_ARG,
+               "ln_distribute_centre_cloud_starts: null buffer");
+    const dim3 grid(ln_div_up(tokens * width, 256));
+    if (tokens * width <= 0x7fffffffll)
+        LN_LAUNCH("k_distribute_centre_cloud_starts", k_distribute_centre_cloud_starts<int>, grid, dim3(256), 0, (hipStream_t)stream, distributed,
+                  splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_point, point_starts, row_starts, clouds, out);
+    else
+        LN_LAUNCH("k_distribute_centre_cloud_starts", k_distribute_centre_cloud_starts<long long>, grid, dim3(256), 0, (hipStream_t)stream,
+                  distributed, splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_point, point_starts, row_starts, clouds, out);
+    return ln_check_launch("ln_distribute_centre_cloud_starts");
 }

@@ -618,7 +618,8 @@ __global__ void __launch_bounds__(256) k_cloud_row_starts(LnTable t, int rows_up
 
 extern "C" int ln_cloud_row_starts(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream) {
     LN_REQUIRE(t && t->keys && t->nr_filled && t->pos_dim >= 1 && t->pos_dim <= LN_MAX_POS_DIM, LN_ERR_ARG, "ln_cloud_row_starts: null table");
-    LN_REQUIRE(t->batch_points > 0 && t->batch_key_step >= 2, LN_ERR_ARG, "ln_cloud_row_starts: the table holds no batch of clouds");
+    LN_REQUIRE((t->batch_points > 0 || t->batch_points == LN_BATCH_POINT_STARTS) && t->batch_key_step >= 2, LN_ERR_ARG,
+               "ln_cloud_row_starts: the table holds no batch of clouds");
     LN_REQUIRE(clouds >= 1 && clouds <= LN_GN_MAX_SEGMENTS, LN_ERR_UNSUPPORTED, "ln_cloud_row_starts: 1 <= clouds <= %d (got %d)",
                LN_GN_MAX_SEGMENTS, clouds);
     LN_REQUIRE(rows_upper >= 0 && row_starts && order_flag, LN_ERR_ARG, "ln_cloud_row_starts: null output or negative rows_upper");

@@ -112,6 +112,54 @@ LN_HD void ln_simplex_of_cloud(LnSimplex<D>& s, long long point, int batch_point
     if (batch_points > 0) s.rem0[0] += int(point / batch_points) * batch_key_step;
 }
 
+// Clouds of unequal sizes (LnTableClouds.batch_point_starts): the cloud of point p is upper_bound(starts, p) - 1 over the clouds + 1 ascending
+// ints, i.e. the last c with starts[c] <= p (empty clouds, starts[c] == starts[c + 1], are stepped over).  A binary search that keeps
+// starts[lo] <= p < starts[hi]: ceil(log2(clouds)) dependent loads (6 for 64 clouds, at most 16) of a list of a few cache lines that every
+// wave of the launch reads; points are cloud-major, so all lanes of a wave but those around a boundary walk the same path and a load is
+// one line for the wave.  It only ever reads starts[1 .. clouds - 1] and returns a cloud in [0, clouds): whatever the list holds, nothing
+// is read out of bounds and no key leaves the clouds' bands.
+LN_HD int ln_cloud_of_point(const int* starts, int clouds, int point) {
+    int lo = 0, hi = clouds;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (starts[mid] <= point)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// What the kernels get of an LnTableClouds: the list and its length, by value beside the LnTable (whose layout does not change).
+struct LnCloudStarts {
+    const int* starts;  // nullptr: no list (no batch, or equal sizes from LnTable.batch_points)
+    int clouds;
+};
+
+// On the host: the tail of the LnTableClouds that `t` heads, if its batch_points says so.
+inline LnCloudStarts ln_cloud_starts_of(const LnTable* t) {
+    if (t->batch_points != LN_BATCH_POINT_STARTS) return LnCloudStarts{nullptr, 0};
+    const LnTableClouds* c = reinterpret_cast<const LnTableClouds*>(t);
+    return LnCloudStarts{c->batch_point_starts, c->batch_clouds};
+}
+// (a table tagged LN_BATCH_POINT_STARTS must bring a list: every entry point that reads it checks this first)
+inline bool ln_cloud_starts_ok(const LnTable* t) {
+    const LnCloudStarts cs = ln_cloud_starts_of(t);
+    return t->batch_points != LN_BATCH_POINT_STARTS || (cs.starts != nullptr && cs.clouds >= 1);
+}
+
+// The form the kernels call.  RAGGED is a template parameter of the three kernels and the HOST picks the instance from cs.starts: measured
+// on an MI355X, a uniform branch on the pointer inside one kernel cost k_point_keys 0.3 - 0.45 us of 28.9 (C3 build, no batch), although the
+// branch is never taken there.  The instance without the list never looks at `cs` and is instruction for instruction the kernel it was
+// before the list existed; only a table with the list runs the search.
+template <int D, bool RAGGED>
+LN_HD void ln_simplex_of_cloud(LnSimplex<D>& s, int point, const LnTable& t, const LnCloudStarts& cs) {
+    if constexpr (RAGGED)
+        s.rem0[0] += ln_cloud_of_point(cs.starts, cs.clouds, point) * t.batch_key_step;
+    else
+        ln_simplex_of_cloud<D>(s, point, t.batch_points, t.batch_key_step);
+}
+
 // LatticeGPU.cuh:798-806: first d coordinates of simplex vertex `remainder`.
 template <int D>
 LN_HD void ln_vertex_key(const LnSimplex<D>& s, int remainder, int* key) {

@@ -82,7 +82,7 @@ LnProfEvents ln_prof_next(const char* name) {
     return ev;
 }
 
-extern "C" const char* ln_kernel_names(void) { return "k_bn_apply,k_bn_apply_eval,k_bn_backward_eval,k_bucket_rows,k_canon_idx,k_canon_mark,k_canon_segs,k_canon_slots,k_cloud_band_verdict,k_cloud_extents_init,k_cloud_key_extents,k_cloud_row_starts,k_conv_backward_fused,k_conv_generic,k_conv_generic_f16,k_conv_mfma,k_conv_mfma_f16,k_conv_split_bank,k_conv_sum_partials,k_csr_count,k_csr_fill,k_csr_group_sizes,k_csr_reduce_segments,k_csr_scan_local,k_csr_scan_top,k_csr_copy_tokens,k_csr_segment_max,k_csr_segment_max_decode,k_csr_sort_groups,k_dice_backward,k_dice_finish,k_dice_partials,k_distribute_centre,k_distribute_centre_clouds,k_finalize,k_gather_backward,k_gather_forward,k_gn_apply,k_gn_apply_segments,k_gn_backward_apply,k_gn_backward_apply_segments,k_gn_param_grads_segments,k_gn_stats,k_gn_stats_segments,k_grad_filter_f16,k_grad_filter_generic,k_grad_filter_mfma,k_grad_filter_mfma_f16,k_im2row,k_im2rowindices,k_insert_coarse,k_insert_points,k_iou_counts_clouds,k_iou_finish_clouds,k_linear_act_backward_w,k_linear_act_backward_x,k_linear_act_forward,k_linear_reduce_slabs,k_lovasz_backward,k_lovasz_cloud_mean,k_lovasz_dot,k_lovasz_fg_count,k_lovasz_finish,k_lovasz_hist,k_lovasz_keys,k_lovasz_scan,k_lovasz_scatter,k_mark_first,k_max_centre_backward,k_max_centre_forward,k_max_centre_sum,k_neighbours,k_nll_clouds_backward,k_nll_clouds_finish,k_nll_clouds_partials,k_nll_clouds_wave,k_point_keys,k_pointnet_reduce_backward,k_pointnet_reduce_decode,k_pointnet_reduce_decode_clouds,k_reduce_and_neighbours,k_reduce_slabs,k_rehash_clear,k_rehash_rows,k_retrieve_points,k_row2im,k_sc_reduce_slabs,k_sc_scatter_atomic,k_scan_blocks,k_scatter_point_rows,k_seg_min,k_slice_classify_backward,k_slice_classify_forward,k_slice_forward,k_slice_forward_f16,k_table_clear,k_weight_norm_backward,k_weight_norm_forward,ln_k_arena_init"; }
+extern "C" const char* ln_kernel_names(void) { return "k_bn_apply,k_bn_apply_eval,k_bn_backward_eval,k_bucket_rows,k_canon_idx,k_canon_mark,k_canon_segs,k_canon_slots,k_cloud_band_verdict,k_cloud_extents_init,k_cloud_key_extents,k_cloud_key_extents_ranges,k_cloud_point_starts_check,k_cloud_row_starts,k_conv_backward_fused,k_conv_generic,k_conv_generic_f16,k_conv_mfma,k_conv_mfma_f16,k_conv_split_bank,k_conv_sum_partials,k_csr_count,k_csr_fill,k_csr_group_sizes,k_csr_reduce_segments,k_csr_scan_local,k_csr_scan_top,k_csr_copy_tokens,k_csr_segment_max,k_csr_segment_max_decode,k_csr_sort_groups,k_dice_backward,k_dice_finish,k_dice_partials,k_distribute_centre,k_distribute_centre_cloud_starts,k_distribute_centre_clouds,k_finalize,k_gather_backward,k_gather_forward,k_gn_apply,k_gn_apply_segments,k_gn_backward_apply,k_gn_backward_apply_segments,k_gn_param_grads_segments,k_gn_stats,k_gn_stats_segments,k_grad_filter_f16,k_grad_filter_generic,k_grad_filter_mfma,k_grad_filter_mfma_f16,k_im2row,k_im2rowindices,k_insert_coarse,k_insert_points,k_iou_counts_clouds,k_iou_finish_clouds,k_linear_act_backward_w,k_linear_act_backward_x,k_linear_act_forward,k_linear_reduce_slabs,k_lovasz_backward,k_lovasz_cloud_mean,k_lovasz_dot,k_lovasz_fg_count,k_lovasz_finish,k_lovasz_hist,k_lovasz_keys,k_lovasz_scan,k_lovasz_scatter,k_mark_first,k_max_centre_backward,k_max_centre_forward,k_max_centre_sum,k_neighbours,k_nll_clouds_backward,k_nll_clouds_finish,k_nll_clouds_partials,k_nll_clouds_wave,k_point_keys,k_pointnet_reduce_backward,k_pointnet_reduce_decode,k_pointnet_reduce_decode_clouds,k_reduce_and_neighbours,k_reduce_slabs,k_rehash_clear,k_rehash_rows,k_retrieve_points,k_row2im,k_sc_reduce_slabs,k_sc_scatter_atomic,k_scan_blocks,k_scatter_point_rows,k_seg_min,k_slice_classify_backward,k_slice_classify_forward,k_slice_forward,k_slice_forward_f16,k_table_clear,k_weight_norm_backward,k_weight_norm_forward,ln_k_arena_init"; }
 
 extern "C" int ln_profile_begin(const char* kernel_names, int max_samples) {
     LN_REQUIRE(kernel_names && strlen(kernel_names) + 3 < sizeof(g_prof.names) && max_samples > 0, LN_ERR_ARG, "ln_profile_begin: bad args");
@@ -343,11 +343,11 @@ __device__ __forceinline__ int ln_insert(const LnTable& t, const int* key, int& 
 // One thread per TOKEN (point, remainder): the d+1 lanes of a point recompute the same cheap simplex
 // arithmetic, but every hash probe chain runs in its own lane, which gives (d+1)x the memory-level
 // parallelism of the reference's thread-per-point loop, and idx / w stores are lane-linear.
-template <int D>
+template <int D, bool RAGGED>
 __global__ void __launch_bounds__(256)
     k_insert_points(LnTable t, const float* __restrict__ pos_raw, LnScale<D> sc, int n, int* __restrict__ tok_slot,
                     int* __restrict__ tok_pos, float* __restrict__ w, const float* __restrict__ vals, int val_dim,
-                    float* __restrict__ distributed) {
+                    float* __restrict__ distributed, LnCloudStarts cs) {
     const long long tk = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int p = int(tk / (D + 1));
     const int r = int(tk - (long long)p * (D + 1));
@@ -357,7 +357,7 @@ __global__ void __launch_bounds__(256)
     for (int i = 0; i < D; ++i) pr[i] = pos_raw[(size_t)p * D + i];
     LnSimplex<D> s;
     ln_simplex<D>(pr, sc, s);
-    ln_simplex_of_cloud<D>(s, p, t.batch_points, t.batch_key_step);
+    ln_simplex_of_cloud<D, RAGGED>(s, p, t, cs);
     int key[D];
     ln_vertex_key<D>(s, r, key);
     int pos;
@@ -408,13 +408,13 @@ __global__ void __launch_bounds__(256)
 // TH = 1024 (d <= 3): the SAME 512-point tile — i.e. the same number of (block, bucket) cursor atomics — on four times the waves: two
 // threads per point, each owning half of its d+1 tokens (both evaluate the point's simplex: a few hundred ALU operations against a
 // chain of returning LDS atomics and global round trips that four waves per SIMD overlap where one could not).
-template <int D, int TH>
+template <int D, int TH, bool RAGGED>
 __global__ void __launch_bounds__(TH)
     k_point_keys(LnTable t, const float* __restrict__ pos_raw, LnScale<D> sc, int n, int sb, int nbk, int capb,
                  int* __restrict__ part_tok, unsigned long long* __restrict__ part_pk, int* __restrict__ tok_slot,
                  float* __restrict__ w, const float* __restrict__ vals, int val_dim, float* __restrict__ distributed,
                  int* __restrict__ seg_count, int seg_regions, float* __restrict__ clear_values, long long clear_values_elems,
-                 unsigned int* __restrict__ pub) {
+                 unsigned int* __restrict__ pub, LnCloudStarts cs) {
     constexpr bool SPLIT = TH == 1024;                        // two threads per point
     constexpr int PTS = TH == 256 ? LN_KEYS_PTS_PER_THREAD : 1;   // points a thread touches (TH = 512: one whole point per thread)
     constexpr int RH = SPLIT ? (D + 2) / 2 : D + 1;           // tokens of a point a thread owns
@@ -448,7 +448,7 @@ __global__ void __launch_bounds__(TH)
         for (int i = 0; i < D; ++i) pr[i] = pos_raw[(size_t)p * D + i];
         LnSimplex<D> s;
         ln_simplex<D>(pr, sc, s);
-        ln_simplex_of_cloud<D>(s, p, t.batch_points, t.batch_key_step);
+        ln_simplex_of_cloud<D, RAGGED>(s, p, t, cs);
 #pragma unroll
         for (int k = 0; k < RH; ++k) {
             const int r = r_first + k;
@@ -1316,6 +1316,7 @@ static int ln_build_points(const LnTable* t, const float* positions_raw, const f
     const int write_idx = flags & LN_BUILD_WRITE_IDX;
     LN_REQUIRE(n >= 0, LN_ERR_ARG, "%s: n=%d", who, n);
     LN_REQUIRE(positions_raw != nullptr || n == 0, LN_ERR_ARG, "%s: null positions", who);
+    LN_REQUIRE(ln_cloud_starts_ok(t), LN_ERR_ARG, "%s: LN_BATCH_POINT_STARTS without a list of point starts", who);
     LN_REQUIRE(!write_idx || n == 0 || (idx && w), LN_ERR_ARG, "%s: write_idx set but idx/w null", who);
     const long long tokens = (long long)n * (t->pos_dim + 1);
     BuildWs ws;
@@ -1339,6 +1340,7 @@ static int ln_build_points(const LnTable* t, const float* positions_raw, const f
     }
     if (n == 0) return LN_OK;
     hipStream_t st = (hipStream_t)stream;
+    const LnCloudStarts cs = ln_cloud_starts_of(t);
     int* tok_slot = write_idx ? idx : ws.tok_slot;  // atomic path: idx doubles as the token->slot scratch
     LN_DISPATCH_D(t->pos_dim, {
         LnScale<D> sc = ln_make_scale<D>(sigmas_host);
@@ -1350,14 +1352,17 @@ static int ln_build_points(const LnTable* t, const float* positions_raw, const f
             int* dropped_idx = write_idx ? idx : (int*)nullptr;  // tokens that never reach a bucket get idx = -1 in pass 1
             // the same 512-point tile (the same number of cursor atomics) on 512 threads (a whole point each); measured against 1024
             // (half a point each) and 256 (two points each)
-            if (D <= 3)
-                LN_LAUNCH("k_point_keys", (k_point_keys<D, (D <= 3 ? 512 : 256)>), dim3(ln_div_up(n, 512)), dim3(512), 0, st, *t, positions_raw, sc, n, sb,
-                          nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed,
-                          csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub);
-            else
-                LN_LAUNCH("k_point_keys", (k_point_keys<D, 256>), dim3(ln_div_up(n, LN_KEYS_PTS_PER_BLOCK)), dim3(256), 0, st, *t, positions_raw, sc, n, sb,
-                          nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed,
-                          csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub);
+            if (D <= 3) {
+                if (cs.starts)
+                    LN_LAUNCH("k_point_keys", (k_point_keys<D, (D <= 3 ? 512 : 256), true>), dim3(ln_div_up(n, 512)), dim3(512), 0, st, *t, positions_raw, sc, n, sb, nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed, csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub, cs);
+                else
+                    LN_LAUNCH("k_point_keys", (k_point_keys<D, (D <= 3 ? 512 : 256), false>), dim3(ln_div_up(n, 512)), dim3(512), 0, st, *t, positions_raw, sc, n, sb, nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed, csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub, cs);
+            } else {
+                if (cs.starts)
+                    LN_LAUNCH("k_point_keys", (k_point_keys<D, 256, true>), dim3(ln_div_up(n, LN_KEYS_PTS_PER_BLOCK)), dim3(256), 0, st, *t, positions_raw, sc, n, sb, nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed, csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub, cs);
+                else
+                    LN_LAUNCH("k_point_keys", (k_point_keys<D, 256, false>), dim3(ln_div_up(n, LN_KEYS_PTS_PER_BLOCK)), dim3(256), 0, st, *t, positions_raw, sc, n, sb, nbk, ws.capb, ws.part_tok, ws.part_pk, dropped_idx, write_idx ? w : (float*)nullptr, vals, val_dim, distributed, csr->seg_count, csr->planes ? LN_XCD_GROUPS : 1, clear_values, clear_values_elems, ws.pub, cs);
+            }
             // Workgroup size of the bucket pass.  1024 threads finish a bucket soonest (C3, 256 buckets of 1 875 tokens: 19.9 us against 22.7
             // on 512 threads), but one such workgroup takes half a CU's wave slots; with several scans in flight the narrower workgroups
             // pack beside the other scans' kernels: C3 1407 -> 1441 Mpoints/s, C4 (3 100 tokens per bucket) 947 -> 980, C2 with 16 clouds
@@ -1374,8 +1379,10 @@ static int ln_build_points(const LnTable* t, const float* positions_raw, const f
             if (rc == LN_OK && (flags & LN_BUILD_CANONICAL_ROWS)) rc = ln_canonicalize_impl<D>(*t, dropped_idx, tokens, csr, ws, st);
             if (rc == LN_OK && (flags & LN_BUILD_SORTED_CSR)) rc = ln_csr_sort_groups(*csr, t->capacity, ws.tok_slot, st);
         } else {
-            LN_LAUNCH("k_insert_points", k_insert_points<D>, dim3(ln_div_up(tokens, 256)), dim3(256), 0, st, *t, positions_raw, sc, n, tok_slot,
-                      ws.tok_pos, write_idx ? w : (float*)nullptr, vals, val_dim, distributed);
+            if (cs.starts)
+                LN_LAUNCH("k_insert_points", (k_insert_points<D, true>), dim3(ln_div_up(tokens, 256)), dim3(256), 0, st, *t, positions_raw, sc, n, tok_slot, ws.tok_pos, write_idx ? w : (float*)nullptr, vals, val_dim, distributed, cs);
+            else
+                LN_LAUNCH("k_insert_points", (k_insert_points<D, false>), dim3(ln_div_up(tokens, 256)), dim3(256), 0, st, *t, positions_raw, sc, n, tok_slot, ws.tok_pos, write_idx ? w : (float*)nullptr, vals, val_dim, distributed, cs);
             rc = ln_rank_and_finalize<D>(*t, tok_slot, ws.tok_pos, write_idx ? idx : (int*)nullptr, tokens, ws, *csr, st);
             // (tok_pos is free again behind the fill: the scratch of the sort; tok_slot may be the caller's idx)
             if (rc == LN_OK && (flags & LN_BUILD_SORTED_CSR)) rc = ln_csr_sort_groups(*csr, t->capacity, ws.tok_pos, st);
@@ -1519,10 +1526,10 @@ extern "C" int ln_neighbours(const LnTable* query, int query_rows_upper, const L
 // ------------------------------------------------------------------------------------------
 // simplex retrieval for slice_no_precomputation (LatticeGPU.cuh:2598-2750, index part)
 // ------------------------------------------------------------------------------------------
-template <int D>
+template <int D, bool RAGGED>
 __global__ void __launch_bounds__(256)
     k_retrieve_points(LnTable t, const float* __restrict__ pos_raw, LnScale<D> sc, int n, int* __restrict__ idx,
-                      float* __restrict__ w) {
+                      float* __restrict__ w, LnCloudStarts cs) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     float pr[D];
@@ -1530,7 +1537,7 @@ __global__ void __launch_bounds__(256)
     for (int i = 0; i < D; ++i) pr[i] = pos_raw[(size_t)p * D + i];
     LnSimplex<D> s;
     ln_simplex<D>(pr, sc, s);
-    ln_simplex_of_cloud<D>(s, p, t.batch_points, t.batch_key_step);
+    ln_simplex_of_cloud<D, RAGGED>(s, p, t, cs);
 #pragma unroll
     for (int r = 0; r <= D; ++r) {
         int key[D];
@@ -1546,10 +1553,14 @@ int ln_retrieve_points(const LnTable* t, const float* positions_raw, const float
     int rc = ln_check_table(t, "ln_slice_no_precomputation");
     if (rc) return rc;
     if (n <= 0) return LN_OK;
+    LN_REQUIRE(ln_cloud_starts_ok(t), LN_ERR_ARG, "ln_slice_no_precomputation: LN_BATCH_POINT_STARTS without a list of point starts");
+    const LnCloudStarts cs = ln_cloud_starts_of(t);
     LN_DISPATCH_D(t->pos_dim, {
         LnScale<D> sc = ln_make_scale<D>(sigmas_host);
-        LN_LAUNCH("k_retrieve_points", k_retrieve_points<D>, dim3(ln_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, *t, positions_raw,
-                           sc, n, idx, w);
+        if (cs.starts)
+            LN_LAUNCH("k_retrieve_points", (k_retrieve_points<D, true>), dim3(ln_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, *t, positions_raw, sc, n, idx, w, cs);
+        else
+            LN_LAUNCH("k_retrieve_points", (k_retrieve_points<D, false>), dim3(ln_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, *t, positions_raw, sc, n, idx, w, cs);
     });
     return ln_check_launch("ln_slice_no_precomputation(retrieve)");
 }

@@ -144,8 +144,27 @@ def set_hash_capacity_policy(policy: str) -> str:
     return prev
 
 
-def cloud_point_ranges(nr_points: int, points_per_cloud: int, rows_per_point: int = 1):
-    """[0, n0 k, 2 n0 k, ..., nr_points k]: first row of every cloud of a batch in a matrix with k rows per point (and the end)."""
+def _checked_cloud_lengths(lengths) -> tuple:
+    """The per-cloud lengths of set_cloud_batch([...]) as a tuple of ints: at least one cloud, no negative length (0 is a legal cloud)."""
+    out = tuple(int(x) for x in lengths)
+    if not out or min(out) < 0 or any(int(x) != x for x in lengths):
+        raise ValueError("per-cloud lengths: a non-empty sequence of integers >= 0")
+    if sum(out) >= 2 ** 31:
+        raise ValueError("per-cloud lengths: fewer than 2^31 points in all")
+    return out
+
+
+def cloud_point_ranges(nr_points: int, points_per_cloud, rows_per_point: int = 1):
+    """[0, n0 k, 2 n0 k, ..., nr_points k]: first row of every cloud of a batch in a matrix with k rows per point (and the end).
+    `points_per_cloud` may be a sequence of per-cloud lengths (clouds of unequal sizes, a length may be 0) that sum to nr_points:
+    [0, l0 k, (l0 + l1) k, ..., nr_points k]."""
+    if not isinstance(points_per_cloud, int) and hasattr(points_per_cloud, "__len__"):
+        lengths = _checked_cloud_lengths(points_per_cloud)
+        if nr_points < 0 or rows_per_point < 1:
+            raise ValueError("nr_points >= 0, rows_per_point >= 1")
+        if sum(lengths) != nr_points:
+            raise ValueError(f"the per-cloud lengths sum to {sum(lengths)} points, not to nr_points = {nr_points}")
+        return [x * rows_per_point for x in itertools.accumulate(lengths, initial=0)]
     if points_per_cloud < 1 or nr_points < 0 or rows_per_point < 1:
         raise ValueError("points_per_cloud >= 1, nr_points >= 0, rows_per_point >= 1")
     clouds = -(-nr_points // points_per_cloud)
@@ -273,6 +292,7 @@ class _TableStorage:
         self.nbr_cache = {}
         self.csr_cache = {}
         self.batch_clouds = 0  # clouds of the batch the last build from positions inserted (Lattice.set_cloud_batch), 0: none
+        self.point_starts = None  # device int32 [B + 1] that build read the clouds' point ranges from (unequal sizes), kept alive here
         self.rows_first_occurrence = False  # that build numbered the rows by first occurrence (row order "canonical")
         self.replay = None  # [rebuild on the atomic path, then the work queued behind the build], see Lattice._build
         self.planes = None  # int32[8] device tensor (7 planes + padding): kd split of key space for the NEXT build that clears, None = no regions
@@ -321,6 +341,7 @@ class _TableStorage:
         s.nbr_cache = {}
         s.csr_cache = {}
         s.batch_clouds, s.rows_first_occurrence = self.batch_clouds, self.rows_first_occurrence
+        s.point_starts = self.point_starts
         s.replay = None
         s.planes = self.planes
         s.plane_values, s.leaf_shares = self.plane_values, self.leaf_shares
@@ -366,15 +387,20 @@ class _BandCheck:
 _BAND_REPORTS = {}
 
 
-def suggest_quotient_step(positions: torch.Tensor, sigmas, points_per_cloud: int, guard: Optional[int] = None) -> int:
+def suggest_quotient_step(positions: torch.Tensor, sigmas, points_per_cloud, guard: Optional[int] = None) -> int:
     """Set-up-time helper (synchronises): the smallest quotient_step, a multiple of 16 cells, whose band holds every cloud of
     `positions` ([n, d] float32 on the device, cloud-major, `points_per_cloud` points each) with `guard` (default 16 (d + 1)) under
-    `sigmas`.  Runs the extents kernel of the band check."""
+    `sigmas`.  Runs the extents kernel of the band check.  `points_per_cloud` may be a sequence of per-cloud lengths that sum to n."""
     if positions.dtype != torch.float32 or positions.dim() != 2 or not positions.is_contiguous():
         raise ValueError("positions should be a contiguous [n, d] float32 tensor")
     _require_cuda(positions, "positions")
     n, d = positions.shape
     sigmas = [float(s) for s in sigmas]
+    starts = None
+    if not isinstance(points_per_cloud, int) and hasattr(points_per_cloud, "__len__"):
+        ranges = cloud_point_ranges(n, points_per_cloud)
+        starts = torch.tensor(ranges, dtype=torch.int32, device=positions.device)
+        points_per_cloud = max(max(b - a for a, b in zip(ranges, ranges[1:])), 1)
     if len(sigmas) != d or d > _lib.LN_MAX_POS_DIM or int(points_per_cloud) < 1:
         raise ValueError("one sigma per position dimension (at most 6) and points_per_cloud >= 1")
     guard = 16 * (d + 1) if guard is None else int(guard)
@@ -382,12 +408,14 @@ def suggest_quotient_step(positions: torch.Tensor, sigmas, points_per_cloud: int
         raise ValueError("guard >= 0")
     if n == 0:
         return 16
-    clouds = -(-n // int(points_per_cloud))
+    clouds = -(-n // int(points_per_cloud)) if starts is None else starts.numel() - 1
     step = ((1 << 30) // (16 * (d + 1))) * 16 * (d + 1)  # a band no packable cloud leaves: only the extents are wanted
     words = torch.zeros((2 * clouds + 3,), dtype=torch.int32, device=positions.device)  # extents | first_bad | nr_filled | status
     base = words.data_ptr()
     t = _lib.LnTable(1, d, None, None, None, None, None, base + 4 * (2 * clouds + 1), base + 4 * (2 * clouds + 2), None, 0, _lib.LN_KEYS_LATTICE, 0,
                      None, 0, int(points_per_cloud), step, None)
+    if starts is not None:
+        t = _lib.LnTableClouds([getattr(t, f[0]) for f in _lib.LnTable._fields_], _lib.ptr(starts), clouds).table
     _lib.check(_lib.load().ln_cloud_key_extents(C.byref(t), _lib.ptr(positions), _lib.host_floats(sigmas), n, min(guard, (step >> 1) - 1), base,
                                                 base + 8 * clouds, _lib.stream_ptr(positions.device)), "ln_cloud_key_extents")
     ext = words[: 2 * clouds].view(clouds, 2).tolist()
@@ -410,6 +438,8 @@ class HashTable:
         self._val_dim_hint = 0
         self._static_rows = None  # capture-safe mode (Lattice.set_static_rows): fixed row bound instead of the host readback
         self._batch = (0, 0)  # (points per cloud, key step) of a batch of independent clouds in this table (Lattice.set_cloud_batch)
+        self._cloud_lengths = None  # clouds of unequal sizes (set_cloud_batch([...])): the lengths, and the device int32 [B + 1] of their
+        self._cloud_starts = None   # first points (LnTableClouds.batch_point_starts), one tensor shared with clones and coarser levels
         self._per_cloud_norm = False  # GroupNorm blocks take their statistics per cloud of the batch (set_cloud_batch(per_cloud_norm=True))
         self._per_cloud_invalid_vertex = False  # Distribute / PointNet drop the first vertex of every cloud (set_cloud_batch(per_cloud_invalid_vertex=True))
         self._band = None  # band check of the batch (set_cloud_batch(check_band=True)): a _BandCheck shared with clones and coarser levels
@@ -464,7 +494,8 @@ class HashTable:
                 self._pinned = torch.zeros((4,), dtype=torch.int32, pin_memory=True)
             self._pinned_np = self._pinned.numpy().view("int64")  # same memory: the host polls the build's 64-bit report word
             self._readback_event = torch.cuda.Event()
-        key = (s.uid, self._counters.data_ptr(), self._static_rows, s.hashed(), None if s.slot_map is None else s.slot_map.data_ptr(), self._batch)
+        key = (s.uid, self._counters.data_ptr(), self._static_rows, s.hashed(), None if s.slot_map is None else s.slot_map.data_ptr(), self._batch,
+               None if self._cloud_starts is None else self._cloud_starts.data_ptr())
         if getattr(self, "_c_table_key", None) == key:
             return self._c_table
         self._c_table_key = key
@@ -472,10 +503,14 @@ class HashTable:
         return self._c_table
 
     def _make_c_table(self, s) -> _lib.LnTable:
-        return _lib.LnTable(s.hashed(), s.pos_dim, s.slot_keys.data_ptr(), s.slot_tok.data_ptr(), s.slot_cnt.data_ptr(), s.entries.data_ptr(),
-                            s.keys.data_ptr(), self._counters.data_ptr(), self._counters.data_ptr() + 4, self._pinned.data_ptr(), 0,
-                            s.key_format, self._static_rows or 0, _lib.ptr(s.slot_map), s.slot_map_sb_max, int(self._batch[0]), int(self._batch[1]),
-                            _lib.ptr(s.row_regions) if s.slot_map is not None else None)
+        fields = (s.hashed(), s.pos_dim, s.slot_keys.data_ptr(), s.slot_tok.data_ptr(), s.slot_cnt.data_ptr(), s.entries.data_ptr(),
+                  s.keys.data_ptr(), self._counters.data_ptr(), self._counters.data_ptr() + 4, self._pinned.data_ptr(), 0,
+                  s.key_format, self._static_rows or 0, _lib.ptr(s.slot_map), s.slot_map_sb_max, int(self._batch[0]), int(self._batch[1]),
+                  _lib.ptr(s.row_regions) if s.slot_map is not None else None)
+        if self._cloud_starts is None:
+            return _lib.LnTable(*fields)
+        # clouds of unequal sizes: the LnTable at the head of an LnTableClouds (a view of its memory, which it keeps alive)
+        return _lib.LnTableClouds(fields, _lib.ptr(self._cloud_starts), len(self._cloud_lengths)).table
 
     def clear(self, lazy: bool = False):  # HashTable.cu:49-57, one launch instead of four fill_ kernels
         """`lazy=True` only records that a clear is due: the next build issues it inside its own C call (no host
@@ -669,6 +704,7 @@ class Lattice:
         ht._pos_dim_hint, ht._val_dim_hint = oh.pos_dim(), oh.val_dim()
         ht._static_rows = oh._static_rows
         ht._batch = oh._batch
+        ht._cloud_lengths, ht._cloud_starts = oh._cloud_lengths, oh._cloud_starts
         ht._per_cloud_norm = oh._per_cloud_norm
         ht._per_cloud_invalid_vertex = oh._per_cloud_invalid_vertex
         ht._band, ht._band_launch = oh._band, oh._band_launch
@@ -708,7 +744,14 @@ class Lattice:
             raise ValueError("positions_raw is not contiguous, call .contiguous() on it")
         if pos_dim > _lib.LN_MAX_POS_DIM:
             raise ValueError(f"pos_dim {pos_dim} unsupported (max {_lib.LN_MAX_POS_DIM})")
+        self._check_cloud_rows(positions_raw.shape[0])
         _require_cuda(positions_raw, "positions")
+
+    def _check_cloud_rows(self, n: int):
+        """Clouds of unequal sizes (set_cloud_batch([...])): the positions handed to this lattice are the whole batch."""
+        lengths = self.m_hash_table._cloud_lengths
+        if lengths is not None and sum(lengths) != n:
+            raise ValueError(f"the per-cloud lengths of set_cloud_batch sum to {sum(lengths)} points but the positions have {n} rows")
 
     def _check_values(self, values: torch.Tensor):  # Lattice.cu:171-175
         if values.dtype not in (torch.float32, torch.float16) or values.dim() != 2 or not values.is_contiguous():
@@ -759,9 +802,14 @@ class Lattice:
             w = torch.empty((n * (d + 1),), dtype=torch.float32, device=dev)
         tokens = n * (d + 1)
         st = ht._storage
+        lengths = ht._cloud_lengths
+        self._check_cloud_rows(n)
+        if lengths is not None and ht._cloud_starts is None:  # (set_cloud_batch ran where no device was to be had)
+            ht._cloud_starts = torch.tensor(list(itertools.accumulate(lengths, initial=0)), dtype=torch.int32, device=dev)
+        batch_clouds = len(lengths) if lengths is not None else (-(-n // ht._batch[0]) if ht._batch[0] else 0)
         check_band = bool(ht._band_launch and ht._band is not None and ht._batch[0] and n > 0)
         if check_band:  # (host arithmetic, before anything is queued)
-            ht._band.check_key_range(d, ht._batch[1] // (d + 1), -(-n // ht._batch[0]))
+            ht._band.check_key_range(d, ht._batch[1] // (d + 1), batch_clouds)
         clear_vals, do_clear = ht.take_pending_clear()  # begin_splat's clear rides in the same C call
         self._choose_hash_capacity(tokens, fresh=do_clear)
         if do_clear:
@@ -814,7 +862,8 @@ class Lattice:
             if check_band:
                 self._queue_band_check(t, positions_raw, n)
             st.touch()
-            st.batch_clouds = -(-n // ht._batch[0]) if ht._batch[0] else 0
+            st.batch_clouds = batch_clouds
+            st.point_starts = ht._cloud_starts
             st.rows_first_occurrence = bool(flags & _lib.LN_BUILD_CANONICAL_ROWS)
             st.rows_follow_space = bool(st.slot_map is not None and do_clear and not (flags & (_lib.LN_BUILD_ATOMIC_PATH | _lib.LN_BUILD_CANONICAL_ROWS)))
             ht.m_nr_filled_is_dirty = True
@@ -881,11 +930,16 @@ class Lattice:
         band = ht._band
         bp, step = ht._batch
         d = positions_raw.shape[1]
-        clouds = -(-n // bp)
+        clouds = len(ht._cloud_lengths) if ht._cloud_lengths is not None else -(-n // bp)
         stream = self._stream()
         buf = band.bufs.get((stream, clouds))
         if buf is None:
             buf = band.bufs[(stream, clouds)] = torch.empty((2 * clouds + 1,), dtype=torch.int32, device=self._dev())
+        if ht._cloud_starts is not None:
+            # the list is built and verified on the host; the device-side check is one more small launch in front of the band check,
+            # whose verdict carries its bit to the report word (a list overwritten on the device is caught where it is read)
+            _lib.check(_lib.load().ln_cloud_point_starts_check(_lib.ptr(ht._cloud_starts), clouds, n, ht._counters.data_ptr() + 4, stream),
+                       "ln_cloud_point_starts_check")
         _lib.check(_lib.load().ln_cloud_key_extents(C.byref(t), _lib.ptr(positions_raw), self._sigmas_host(), n, band.guard, buf.data_ptr(),
                                                     buf.data_ptr() + 8 * clouds, stream), "ln_cloud_key_extents")
         ht._band_last = (buf, clouds)
@@ -1386,6 +1440,8 @@ class Lattice:
         bp, step = self.m_hash_table._batch
         # (a batch of clouds: the key step halves with every coarser level, so that fine key x 2^-1 lands in the same cloud's block)
         ht._batch = (bp, (step // (2 * (d + 1))) * (d + 1)) if bp else (0, 0)
+        # (clouds of unequal sizes: a coarser level built from the same positions has the same point ranges)
+        ht._cloud_lengths, ht._cloud_starts = self.m_hash_table._cloud_lengths, self.m_hash_table._cloud_starts
         ht._per_cloud_norm = self.m_hash_table._per_cloud_norm
         ht._per_cloud_invalid_vertex = self.m_hash_table._per_cloud_invalid_vertex
         ht._band = self.m_hash_table._band  # (inherited, but no launch: the finest level's verdict with the guard covers this level)
@@ -1702,7 +1758,7 @@ class Lattice:
         # coarse_bounds[k]: bound of the lattice k + 1 levels coarser than this one (create_coarse_verts hands them down)
         ht._static_levels = None if coarse_bounds is None else {self.m_lvl + 1 + k: int(b) for k, b in enumerate(coarse_bounds)}
 
-    def set_cloud_batch(self, points_per_cloud: Optional[int], quotient_step: int = 1 << 13, per_cloud_norm: bool = False,
+    def set_cloud_batch(self, points_per_cloud, quotient_step: int = 1 << 13, per_cloud_norm: bool = False,
                         per_cloud_invalid_vertex: bool = False, check_band: bool = False, guard: Optional[int] = None):
         """The multi-cloud launch form for small clouds.  From now on the positions handed to this lattice are a BATCH of independent
         clouds of `points_per_cloud` points each (cloud c = rows c * points_per_cloud ... of the positions tensor; None / 0 switches it
@@ -1713,6 +1769,16 @@ class Lattice:
         sum over the clouds.  The clouds stay within quotient_step / 2 lattice cells of the origin on the first axis (a cell is
         ~0.8 (d + 1) sigma wide... see README 'Key range'; 8192 cells and 64 clouds fit the 2^20 cells of d <= 3): checked with
         check_band=True.  Coarser levels created from this lattice inherit the batch with the step halved per level.
+
+        Clouds of unequal sizes: `points_per_cloud` may be a sequence of per-cloud lengths (>= 0; a cloud may be empty) instead of an
+        int.  Cloud c is then the rows [l_0 + ... + l_(c-1), l_0 + ... + l_c) of the positions tensor.  The first points of the clouds
+        go to one device int32 tensor (LnTableClouds.batch_point_starts), made here, once, and shared with clones and coarser levels; the
+        build, the retrieval, the band check and the per-cloud invalid vertex of DistributeLatticeModule find the cloud of a point by a
+        binary search on it, and everything on the vertex side works from cloud_row_starts() as before.  Every positions tensor handed
+        to a build must have sum(lengths) rows (ValueError).  The lengths are fixed until the next set_cloud_batch: a captured step
+        replays with the same tensor.  cloud_lengths() returns them, cloud_point_starts() the row ranges of per-point and per-token
+        matrices; points_per_cloud() raises.  The per-cloud losses and metrics (losses.py, Scores) still take equal sizes: slice
+        log_probs[starts[c]:starts[c + 1]] per cloud.  An int keeps its meaning and its bits.
 
         `check_band=True`: every build from positions into this lattice (splat, distribute, just_create_verts; eager, under
         set_static_rows and inside a stream capture) queues ln_cloud_key_extents behind itself: three small launches, no
@@ -1746,6 +1812,12 @@ class Lattice:
         False nothing changes."""
         d = self.pos_dim() if self.m_hash_table.is_initialized() else len(self.m_sigmas)
         band = None
+        lengths = None
+        if points_per_cloud is not None and not isinstance(points_per_cloud, int) and hasattr(points_per_cloud, "__len__"):
+            lengths = _checked_cloud_lengths(points_per_cloud)
+            if (per_cloud_norm or per_cloud_invalid_vertex) and len(lengths) > Lattice.MAX_BATCH_CLOUDS:
+                raise ValueError(f"{len(lengths)} clouds: per_cloud_norm and per_cloud_invalid_vertex take at most {Lattice.MAX_BATCH_CLOUDS}")
+            points_per_cloud = max(max(lengths), 1)  # (LnTable.batch_points > 0 marks the batch; the kernels take the ranges from the list)
         if not points_per_cloud:
             self.m_hash_table._batch = (0, 0)
         else:
@@ -1758,6 +1830,10 @@ class Lattice:
                     raise ValueError(f"guard {band.guard} must be in [0, {half}): half a key step of quotient_step {int(quotient_step)} x (d + 1)")
                 band.check_key_range(d, int(quotient_step), 1)
             self.m_hash_table._batch = (int(points_per_cloud), int(quotient_step) * (d + 1))
+        self.m_hash_table._cloud_lengths = lengths
+        # (made here and not by the first build: that build may already be inside a stream capture, where no host list can be copied)
+        self.m_hash_table._cloud_starts = None if lengths is None or not torch.cuda.is_available() else torch.tensor(
+            list(itertools.accumulate(lengths, initial=0)), dtype=torch.int32, device=self._dev())
         self.m_hash_table._band = band
         self.m_hash_table._band_launch = band is not None
         self.m_hash_table._per_cloud_norm = bool(per_cloud_norm) and bool(points_per_cloud)
@@ -1766,6 +1842,8 @@ class Lattice:
             self.m_hash_table._storage.touch()
 
     MAX_BATCH_CLOUDS = 64  # LN_GN_MAX_SEGMENTS of csrc/ln_norm.hip
+    CLOUD_STARTS_MESSAGE = ("the per-cloud point starts of the batch (LnTableClouds.batch_point_starts, Lattice.set_cloud_batch([...])) are not an "
+                            "ascending list from 0 to the number of points: the clouds of this build are wrong")
 
     def _cloud_batch_size(self) -> int:
         """Clouds in the batch the last build of this table inserted.  Raises, without device work, where cloud_row_starts() has no
@@ -1818,8 +1896,24 @@ class Lattice:
         return self.cloud_row_starts() if self.m_hash_table._per_cloud_norm else None
 
     def points_per_cloud(self) -> int:
-        """Points of one cloud of the batch (set_cloud_batch), 0: no batch."""
+        """Points of one cloud of the batch (set_cloud_batch), 0: no batch.  Clouds of unequal sizes have no such number: ValueError."""
+        if self.m_hash_table._cloud_lengths is not None:
+            raise ValueError("points_per_cloud: the clouds of this batch have unequal sizes (set_cloud_batch([...])); use cloud_lengths() "
+                             "or cloud_point_starts(), and slice per cloud for the per-cloud losses, which take equal sizes")
         return self.m_hash_table._batch[0]
+
+    def cloud_lengths(self, nr_points: Optional[int] = None) -> list:
+        """Points of every cloud of the batch (set_cloud_batch): the lengths it was given, or, for equal sizes, what `nr_points` points
+        split into (the last cloud what is left); [] without a batch."""
+        ht = self.m_hash_table
+        if ht._cloud_lengths is not None:
+            return list(ht._cloud_lengths)
+        if not ht._batch[0]:
+            return []
+        if nr_points is None:
+            raise ValueError("cloud_lengths: a batch of equal sizes needs nr_points")
+        r = cloud_point_ranges(int(nr_points), ht._batch[0])
+        return [b - a for a, b in zip(r, r[1:])]
 
     def per_cloud_invalid_row_starts(self) -> Optional[torch.Tensor]:
         """cloud_row_starts() when this lattice holds a batch with per_cloud_invalid_vertex on, else None: what DistributeLatticeModule
@@ -1833,8 +1927,11 @@ class Lattice:
 
     def cloud_point_starts(self, nr_points: int, rows_per_point: int = 1) -> torch.Tensor:
         """Row ranges of the clouds in a per-point (rows_per_point = 1) or per-token (pos_dim + 1) matrix of `nr_points` points: cloud c
-        owns the rows [c n0 k, (c + 1) n0 k), the last cloud what is left.  For group_norm_rows(..., row_starts=...)."""
-        return torch.tensor(cloud_point_ranges(nr_points, self.m_hash_table._batch[0], rows_per_point), dtype=torch.int32, device=self._dev())
+        owns the rows [c n0 k, (c + 1) n0 k), the last cloud what is left; clouds of unequal sizes own [starts[c] k, starts[c + 1] k)
+        and `nr_points` must be their sum.  For group_norm_rows(..., row_starts=...)."""
+        ht = self.m_hash_table
+        per_cloud = ht._batch[0] if ht._cloud_lengths is None else ht._cloud_lengths
+        return torch.tensor(cloud_point_ranges(nr_points, per_cloud, rows_per_point), dtype=torch.int32, device=self._dev())
 
     def set_region_planes(self, planes, leaf_shares=None):
         """kd split planes of key space (7 ints: 1 + 2 + 4 thresholds in heap order, see LnCsr.planes) or None.  With planes, the builds
@@ -1921,6 +2018,8 @@ class Lattice:
             raise _lib.LatticeNetHipError(f"hash table overflow: capacity {ht.capacity()} is too small for this cloud")
         if status & _lib.LN_STATUS_KEY_RANGE:
             raise _lib.LatticeNetHipError("a lattice key does not fit the packed 64-bit slot format (README: 'Key range')")
+        if status & _lib.LN_STATUS_CLOUD_STARTS:
+            raise _lib.LatticeNetHipError(Lattice.CLOUD_STARTS_MESSAGE)
         if status & _lib.LN_STATUS_CLOUD_BAND:
             raise _lib.LatticeNetHipError(Lattice.band_violation_message(arr))
         if bound is not None and nr > bound:
@@ -1963,6 +2062,8 @@ class Lattice:
                     f"a lattice key does not fit the packed 64-bit slot format: pos_dim {d} leaves {bits} bits per coordinate, i.e. "
                     f"lattice coordinates within +-{reach} (about +-{reach / (d + 1) / 0.8165:.0f} sigmas from the "
                     "origin per axis); centre the positions or use larger sigmas (README: 'Key range')")
+            if status & _lib.LN_STATUS_CLOUD_STARTS:
+                raise _lib.LatticeNetHipError(Lattice.CLOUD_STARTS_MESSAGE)
             if status & _lib.LN_STATUS_CLOUD_BAND:
                 raise _lib.LatticeNetHipError(Lattice.band_violation_message(getattr(ht, "_pinned_np", None)))
             ht.m_nr_filled = nr

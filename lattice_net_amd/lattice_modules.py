@@ -317,6 +317,15 @@ class DistributeLatticeModule(torch.nn.Module):  # lattice_modules.py:52-96
             distributed_lattice._scatter_rows(distributed, splatting_indices, _unit_weights(distributed.device, tokens), sums, pos_dim, 1, width)
             counts = distributed_lattice.vertex_point_counts(splatting_indices)
             centred = torch.empty_like(distributed)
+            point_starts = getattr(getattr(distributed_lattice, "m_hash_table", None), "_cloud_starts", None) if starts is not None else None
+            if point_starts is not None:  # clouds of unequal sizes: the cloud of a token comes from the batch's point starts
+                _lib.check(_lib.load().ln_distribute_centre_cloud_starts(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums),
+                                                                         _lib.ptr(counts), tokens, width, pos_dim,
+                                                                         distributed_lattice.pos_dim() + 1, _lib.ptr(point_starts),
+                                                                         _lib.ptr(starts), starts.numel() - 1, _lib.ptr(centred),
+                                                                         _lib.stream_ptr(distributed.device)),
+                           "ln_distribute_centre_cloud_starts")
+                return distributed_lattice, centred, splatting_indices, splatting_weights
             if starts is not None:  # a batch of clouds: the first vertex of every cloud is its "invalid" vertex
                 tokens_per_cloud = distributed_lattice.points_per_cloud() * (distributed_lattice.pos_dim() + 1)
                 _lib.check(_lib.load().ln_distribute_centre_clouds(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums),
