@@ -10,6 +10,7 @@
 //     the K order inside a neighbour is permuted (k = q*V/4 + 4s + j), which only reorders the fp32 accumulation.
 //   * W_e is staged per slot into LDS in that fragment order: 8 bytes per lane per MFMA, lane-linear.
 #include "ln_common.h"
+#include "ln_conv_f16_plan.h"
 
 #include <hip/hip_fp16.h>
 
@@ -231,43 +232,10 @@ __global__ void __launch_bounds__(1024)
         }
 }
 
-// sub-tiles per workgroup of k_conv_f16_tiled: the launch runs in rounds of 256 CUs x (workgroups that fit a CU's LDS); the T with the
-// cheapest rounds(T) * T wins, larger T (fewer bank stagings) on ties.
-static int ln_f16_subtiles(int m, size_t lds_bytes) {
-    const int per_cu = lds_bytes * 2 <= 150 * 1024 ? 2 : 1;
-    const int tiles = (m + 63) / 64;
-    int best = 1, best_cost = 1 << 30;
-    for (int t = 1; t <= 4; ++t) {
-        if (per_cu * t * 4 > 32) break;  // wave slots of a CU
-        // (one workgroup per CU: a single sub-tile would leave the CU with four waves — 39 us instead of 21 at C5 — unless the lattice
-        // is too small to give every CU more)
-        if (per_cu == 1 && t < 3 && tiles >= 3 * 256) continue;
-        const int wgs = (tiles + t - 1) / t;
-        const int cost = ((wgs + 256 * per_cu - 1) / (256 * per_cu)) * t;
-        if (cost <= best_cost) {
-            best = t;
-            best_cost = cost;
-        }
-    }
-    return best;
-}
-
-template <bool FLIP, bool WT>
-static bool ln_conv_f16_tiled(const int* nbr, const _Float16* values, const _Float16* filter, int m, int E, int val_dim, int nr_filters,
-                              _Float16* out, hipStream_t st) {
-    if (E != 9 || ((reinterpret_cast<uintptr_t>(values) | reinterpret_cast<uintptr_t>(filter)) & 15) != 0) return false;
-#define LN_F16_TILED(VV, NN)                                                                                                         \
-    if (val_dim == VV && nr_filters == 16 * NN) {                                                                                    \
-        /* (at 64 channels: + the re-shaping regions of up to 16 waves and the ids, see the kernel) */                               \
-        const int t = ln_f16_subtiles(m, (size_t)9 * VV * 16 * NN * 2 + (VV == 64 ? 16 * 2048 + 256 * 9 * 4 : 0));          \
-        LN_LAUNCH("k_conv_mfma_f16", (k_conv_f16_tiled<VV, NN, FLIP, WT>), dim3(ln_div_up(m, 64 * t)), dim3(256 * t), 0, st, nbr, values, \
-                  filter, m, out);                                                                                                   \
-        return true;                                                                                                                 \
-    }
-    LN_F16_TILED(32, 2) LN_F16_TILED(64, 4) LN_F16_TILED(32, 4) LN_F16_TILED(64, 2)
-#undef LN_F16_TILED
-    return false;
-}
+// the arrays of k_conv_f16_tiled that ln_f16_tiled_lds counts: s_x[16][16 * 8] of halfx8 (one region per wave), s_nbr[256 * E]
+static_assert(LN_F16_TILED_MAX_WAVES == 1024 / 64 && LN_F16_TILED_MAX_WAVES == 16 && LN_F16_TILED_REGION_BYTES == 16 * 8 * sizeof(halfx8) &&
+                  LN_F16_TILED_MAX_ROWS == 1024 / 4 && LN_F16_TILED_MAX_ROWS == 256,
+              "ln_conv_f16_plan.h counts the LDS of k_conv_f16_tiled from these");
 
 // any shape: one thread per output element, fp32 accumulation
 __global__ void __launch_bounds__(256)
@@ -290,54 +258,56 @@ __global__ void __launch_bounds__(256)
     out[g] = (_Float16)acc;
 }
 
+// ---- executors of ln_conv_f16_plan.h: the plan decides form, chunks, grid and block; the switches below only name the instance ----
 template <int V, bool FLIP, bool WT>
-static void ln_conv_f16_launch_v(int nr_filters, const int* nbr, const _Float16* values, const _Float16* filter, int m, int E, _Float16* out,
-                                 hipStream_t st) {
-    const dim3 grid(ln_div_up(m, 64)), block(256);
-    constexpr int NT_MAX = (V * 128 * 2 <= 32 * 1024) ? 8 : 4;  // LDS of one slot's filter slice
-    int f_off = 0;
-    while (f_off < nr_filters) {
-        const int left = (nr_filters - f_off) / 16;
-        if (NT_MAX >= 8 && left >= 8) {
+static void ln_conv_f16_launch_v(const LnF16FwdPlan& p, const int* nbr, const _Float16* values, const _Float16* filter, int m, int E, int nr_filters,
+                                 _Float16* out, hipStream_t st) {
+    const dim3 grid(p.grid), block(p.block);
+    constexpr int NT_MAX = ln_f16_nt_max(V);
+    static_assert(ln_f16_per_slot_lds(V, NT_MAX) == sizeof(_Float16) * V * 16 * NT_MAX && ln_f16_per_slot_lds(V, NT_MAX) <= LN_F16_SLOT_LDS_MAX,
+                  "s_b[V * F] of the widest chunk");
+    for (int k = 0; k < p.n; ++k) {
+        const LnF16Seg c = ln_f16_chunk(p, k);
+        const int f_off = c.off;
+        if (c.nt == 8) {
             if constexpr (NT_MAX >= 8) LN_LAUNCH("k_conv_mfma_f16", (k_conv_mfma_f16<V, 8, FLIP, WT>), grid, block, 0, st, nbr, values, filter, m, E, out, nr_filters, f_off);
-            f_off += 128;
-        } else if (left >= 4) {
+        } else if (c.nt == 4) {
             LN_LAUNCH("k_conv_mfma_f16", (k_conv_mfma_f16<V, 4, FLIP, WT>), grid, block, 0, st, nbr, values, filter, m, E, out, nr_filters, f_off);
-            f_off += 64;
-        } else if (left >= 2) {
+        } else if (c.nt == 2) {
             LN_LAUNCH("k_conv_mfma_f16", (k_conv_mfma_f16<V, 2, FLIP, WT>), grid, block, 0, st, nbr, values, filter, m, E, out, nr_filters, f_off);
-            f_off += 32;
         } else {
             LN_LAUNCH("k_conv_mfma_f16", (k_conv_mfma_f16<V, 1, FLIP, WT>), grid, block, 0, st, nbr, values, filter, m, E, out, nr_filters, f_off);
-            f_off += 16;
         }
     }
 }
 
 template <bool FLIP, bool WT>
-static int ln_conv_f16_dispatch(const int* nbr, const _Float16* values, const _Float16* filter, int m, int E, int val_dim, int nr_filters,
-                                _Float16* out, hipStream_t st) {
-    bool done = ln_conv_f16_tiled<FLIP, WT>(nbr, values, filter, m, E, val_dim, nr_filters, out, st);
-    if (done) return ln_check_launch("ln_conv_forward_f16");
-    if (nr_filters % 16 == 0 && (reinterpret_cast<uintptr_t>(values) & 7) == 0) {
-        done = true;
-        switch (val_dim) {
-            case 16: ln_conv_f16_launch_v<16, FLIP, WT>(nr_filters, nbr, values, filter, m, E, out, st); break;
-            case 32: ln_conv_f16_launch_v<32, FLIP, WT>(nr_filters, nbr, values, filter, m, E, out, st); break;
-            case 64: ln_conv_f16_launch_v<64, FLIP, WT>(nr_filters, nbr, values, filter, m, E, out, st); break;
-            case 96: ln_conv_f16_launch_v<96, FLIP, WT>(nr_filters, nbr, values, filter, m, E, out, st); break;
-            case 128: ln_conv_f16_launch_v<128, FLIP, WT>(nr_filters, nbr, values, filter, m, E, out, st); break;
-            case 256: ln_conv_f16_launch_v<256, FLIP, WT>(nr_filters, nbr, values, filter, m, E, out, st); break;
-            default: done = false; break;
+static int ln_conv_f16_run(const LnF16FwdPlan& p, const int* nbr, const _Float16* values, const _Float16* filter, int m, int E, int val_dim,
+                           int nr_filters, _Float16* out, hipStream_t st) {
+    if (p.form == LN_F16_FWD_TILED) {
+#define LN_F16_TILED(VV, NN)                                                                                                       \
+    if (p.V == VV && p.nt == NN)                                                                                                   \
+        LN_LAUNCH("k_conv_mfma_f16", (k_conv_f16_tiled<VV, NN, FLIP, WT>), dim3(p.grid), dim3(p.block), 0, st, nbr, values, filter, m, out);
+        LN_F16_TILED(32, 2) LN_F16_TILED(64, 4) LN_F16_TILED(32, 4) LN_F16_TILED(64, 2)
+#undef LN_F16_TILED
+    } else if (p.form == LN_F16_FWD_SLOTS) {
+        switch (p.V) {
+            case 16: ln_conv_f16_launch_v<16, FLIP, WT>(p, nbr, values, filter, m, E, nr_filters, out, st); break;
+            case 32: ln_conv_f16_launch_v<32, FLIP, WT>(p, nbr, values, filter, m, E, nr_filters, out, st); break;
+            case 64: ln_conv_f16_launch_v<64, FLIP, WT>(p, nbr, values, filter, m, E, nr_filters, out, st); break;
+            case 96: ln_conv_f16_launch_v<96, FLIP, WT>(p, nbr, values, filter, m, E, nr_filters, out, st); break;
+            case 128: ln_conv_f16_launch_v<128, FLIP, WT>(p, nbr, values, filter, m, E, nr_filters, out, st); break;
+            default: ln_conv_f16_launch_v<256, FLIP, WT>(p, nbr, values, filter, m, E, nr_filters, out, st); break;
         }
-    }
-    if (!done) {
-        const long long work = (long long)m * nr_filters;
-        LN_LAUNCH("k_conv_generic_f16", k_conv_generic_f16, dim3(ln_div_up(work, 256)), dim3(256), 0, st, nbr, values, filter, work, E, val_dim,
-                  nr_filters, FLIP ? 1 : 0, WT ? 1 : 0, out);
+    } else {
+        LN_LAUNCH("k_conv_generic_f16", k_conv_generic_f16, dim3(p.grid), dim3(p.block), 0, st, nbr, values, filter, p.work, E, val_dim, nr_filters,
+                  FLIP ? 1 : 0, WT ? 1 : 0, out);
     }
     return ln_check_launch("ln_conv_forward_f16");
 }
+static_assert(ln_f16_per_slot_v(16) && ln_f16_per_slot_v(32) && ln_f16_per_slot_v(64) && ln_f16_per_slot_v(96) && ln_f16_per_slot_v(128) &&
+                  ln_f16_per_slot_v(256),
+              "the per-slot instances above are the plan's channel counts");
 
 extern "C" int ln_conv_forward_f16(const int* nbr, const void* values_neigh, const void* filter, int m, int filter_extent, int val_dim,
                                    int nr_filters, int flags, void* out, void* stream) {
@@ -349,12 +319,14 @@ extern "C" int ln_conv_forward_f16(const int* nbr, const void* values_neigh, con
     const _Float16* v = static_cast<const _Float16*>(values_neigh);
     const _Float16* w = static_cast<const _Float16*>(filter);
     _Float16* o = static_cast<_Float16*>(out);
-    switch (flags) {
-        case 0: return ln_conv_f16_dispatch<false, false>(nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
-        case LN_CONV_FLIP_NEIGHBOURS: return ln_conv_f16_dispatch<true, false>(nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
-        case LN_CONV_TRANSPOSED_FILTER: return ln_conv_f16_dispatch<false, true>(nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
-        default: return ln_conv_f16_dispatch<true, true>(nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
+    const LnF16FwdPlan p = ln_f16_forward_plan(LnF16FwdIn{m, filter_extent, val_dim, nr_filters, flags, unsigned(reinterpret_cast<uintptr_t>(v) & 15),
+                                                          unsigned(reinterpret_cast<uintptr_t>(w) & 15)});
+    if (p.flip) {
+        if (p.wt) return ln_conv_f16_run<true, true>(p, nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
+        return ln_conv_f16_run<true, false>(p, nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
     }
+    if (p.wt) return ln_conv_f16_run<false, true>(p, nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
+    return ln_conv_f16_run<false, false>(p, nbr, v, w, m, filter_extent, val_dim, nr_filters, o, st);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -366,8 +338,6 @@ extern "C" int ln_conv_forward_f16(const int* nbr, const void* values_neigh, con
 // v_mfma_f32_16x16x32_f16).  Each wave owns whole 16x16 output
 // tiles D[v, f]; partial [V, F] blocks per row chunk go to slabs, summed by ln_reduce_slabs_async (ln_conv.hip, deterministic).
 // ------------------------------------------------------------------------------------------
-#define LN_GF16_ROWS 512
-#define LN_GF16_SUB 64
 template <int VT, int FT>
 __global__ void __launch_bounds__(256)
     k_grad_filter_mfma_f16(const int* __restrict__ nbr, const _Float16* __restrict__ values, const _Float16* __restrict__ grad_out, int m,
@@ -469,7 +439,7 @@ __global__ void __launch_bounds__(256)
 }
 
 // any shape (fallback): lanes own (v, f) pairs, rows staged through LDS as floats
-#define LN_GF16_GSUB 32
+static_assert(LN_GF16_PAIRS == 16 * 256, "MAXP pairs on each of 256 threads");
 __global__ void __launch_bounds__(256)
     k_grad_filter_f16(const int* __restrict__ nbr, const _Float16* __restrict__ values, const _Float16* __restrict__ grad_out, int m, int E,
                       int V, int F, float* __restrict__ partial) {
@@ -520,8 +490,7 @@ __global__ void __launch_bounds__(256)
 }
 
 extern "C" size_t ln_conv_grad_filter_f16_workspace_bytes(int m, int filter_extent, int val_dim, int nr_filters) {
-    if (m <= 0) return 256;
-    return (size_t)ln_div_up(m, LN_GF16_ROWS) * filter_extent * val_dim * nr_filters * sizeof(float) + 256;
+    return ln_f16_gf_workspace_bytes(m, filter_extent, val_dim, nr_filters);
 }
 
 extern "C" int ln_conv_grad_filter_f16(const int* nbr, const void* values_neigh, const void* grad_out, int m, int filter_extent, int val_dim,
@@ -534,39 +503,29 @@ extern "C" int ln_conv_grad_filter_f16(const int* nbr, const void* values_neigh,
         (void)ln_zero_async(grad_filter, (size_t)total * sizeof(float), st);
         return ln_check_launch("ln_conv_grad_filter_f16");
     }
-    LN_REQUIRE(workspace && workspace_bytes >= ln_conv_grad_filter_f16_workspace_bytes(m, filter_extent, val_dim, nr_filters), LN_ERR_WORKSPACE,
+    LN_REQUIRE(workspace && workspace_bytes >= ln_f16_gf_workspace_bytes(m, filter_extent, val_dim, nr_filters), LN_ERR_WORKSPACE,
                "ln_conv_grad_filter_f16: workspace too small");
-    const int chunks = ln_div_up(m, LN_GF16_ROWS);
+    const LnF16GfPlan p = ln_f16_gf_plan(LnF16GfIn{m, filter_extent, val_dim, nr_filters, unsigned(reinterpret_cast<uintptr_t>(values_neigh) & 15),
+                                                   unsigned(reinterpret_cast<uintptr_t>(grad_out) & 15)});
+    LN_REQUIRE(p.form != LN_F16_GF_UNSUPPORTED, LN_ERR_UNSUPPORTED, "ln_conv_grad_filter_f16: val_dim %d + nr_filters %d = %d too large", val_dim, nr_filters, val_dim + nr_filters);
     float* partial = static_cast<float*>(workspace);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(values_neigh) | reinterpret_cast<uintptr_t>(grad_out)) & 7) == 0;
-    if (val_dim % 16 == 0 && nr_filters % 16 == 0 && aligned) {
-        const dim3 grid(chunks, filter_extent), block(256);
-        const _Float16* vv = static_cast<const _Float16*>(values_neigh);
-        const _Float16* gg = static_cast<const _Float16*>(grad_out);
-        for (int v_off = 0; v_off < val_dim;) {
-            const int vleft = (val_dim - v_off) / 16;
-            const int vt = vleft >= 4 ? 4 : (vleft >= 2 ? 2 : 1);
-            for (int f_off = 0; f_off < nr_filters;) {
-                const int fleft = (nr_filters - f_off) / 16;
-                const int ft = fleft >= 4 ? 4 : (fleft >= 2 ? 2 : 1);
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
+    const _Float16* vv = static_cast<const _Float16*>(values_neigh);
+    const _Float16* gg = static_cast<const _Float16*>(grad_out);
+    if (p.form == LN_F16_GF_MFMA) {
+        for (int k = 0; k < p.n; ++k) {
+            const LnF16GfTile t = ln_f16_gf_tile(p, val_dim, nr_filters, k);
 #define LN_GF16_CASE(A, B)                                                                                                          \
-    if (vt == A && ft == B)                                                                                                         \
+    if (t.vt == A && t.ft == B)                                                                                                     \
         LN_LAUNCH("k_grad_filter_mfma_f16", (k_grad_filter_mfma_f16<A, B>), grid, block, 0, st, nbr, vv, gg, m, filter_extent, partial, val_dim, \
-                  v_off, nr_filters, f_off);
-                LN_GF16_CASE(1, 1) LN_GF16_CASE(1, 2) LN_GF16_CASE(1, 4) LN_GF16_CASE(2, 1) LN_GF16_CASE(2, 2) LN_GF16_CASE(2, 4)
-                LN_GF16_CASE(4, 1) LN_GF16_CASE(4, 2) LN_GF16_CASE(4, 4)
+                  t.v_off, nr_filters, t.f_off);
+            LN_GF16_CASE(1, 1) LN_GF16_CASE(1, 2) LN_GF16_CASE(1, 4) LN_GF16_CASE(2, 1) LN_GF16_CASE(2, 2) LN_GF16_CASE(2, 4)
+            LN_GF16_CASE(4, 1) LN_GF16_CASE(4, 2) LN_GF16_CASE(4, 4)
 #undef LN_GF16_CASE
-                f_off += ft * 16;
-            }
-            v_off += vt * 16;
         }
     } else {
-        const size_t lds = sizeof(float) * LN_GF16_GSUB * ((size_t)val_dim + nr_filters);
-        LN_REQUIRE(lds <= 64 * 1024, LN_ERR_UNSUPPORTED, "ln_conv_grad_filter_f16: val_dim + nr_filters = %d too large", val_dim + nr_filters);
-        LN_LAUNCH("k_grad_filter_f16", k_grad_filter_f16, dim3(chunks, filter_extent, ln_div_up((long long)val_dim * nr_filters, 4096)), dim3(256),
-                  lds, st, nbr, static_cast<const _Float16*>(values_neigh), static_cast<const _Float16*>(grad_out), m, filter_extent, val_dim,
-                  nr_filters, partial);
+        LN_LAUNCH("k_grad_filter_f16", k_grad_filter_f16, grid, block, p.lds, st, nbr, vv, gg, m, filter_extent, val_dim, nr_filters, partial);
     }
-    (void)ln_reduce_slabs_async(partial, chunks, total, grad_filter, st);  // (147 slabs of 147 KB at C5: one serial pass per output took 35 us)
+    (void)ln_reduce_slabs_async(partial, p.chunks, total, grad_filter, st);  // (147 slabs of 147 KB at C5: one serial pass per output took 35 us)
     return ln_check_launch("ln_conv_grad_filter_f16");
 }

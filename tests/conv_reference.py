@@ -53,6 +53,22 @@ def two_lattice_lists(mq, mn, E, rng, row0_unreferenced=False):
     return _one_list(mq, mn, E, rng, lo), _one_list(mn, mq, E, rng, lo)
 
 
+def small_list(rows, into, E, rng, row0_unreferenced=False):
+    """[rows, E] int32 for ANY row count from 1 on (_one_list needs 88 rows for what it plants): the cases at the edges of the kernels'
+    own row tiles (1, 15 .. 17, 63 .. 65 rows).  Ids drawn independently in [lo, into) (lo = 1 with `row0_unreferenced`), about one
+    entry in eight absent (as in _one_permutation: absent neighbours inside every partial tile); planted: row 0 without an absent
+    neighbour and naming the largest id into - 1 in its last slot, and, where there is more than one row, row rows - 1 wholly absent."""
+    lo = 1 if row0_unreferenced else 0
+    assert rows >= 1 and into >= lo + 2 and E >= 1
+    n = rng.integers(lo, into, (rows, E)).astype(np.int32)
+    n[rng.random((rows, E)) < 0.125] = -1
+    n[0] = rng.integers(lo, into, E)
+    n[0, E - 1] = into - 1
+    if rows > 1:
+        n[rows - 1] = -1
+    return n
+
+
 def _one_permutation(rows, into, rng, lo):
     """[rows, 1] int32: every id of [lo, into) at most once, the other rows absent (about one in eight, and all that the ids do not
     reach); rows 0 and rows - 2 present, the ids `lo` and into - 1 named, row rows - 1 absent."""

@@ -258,3 +258,30 @@ def test_references_agree_with_autograd_at_other_extents(extent):
     refs = (C.forward(nbr_q, vals, W), C.grad_filter(nbr_q, vals, G), C.grad_values(nbr_n, G, W))
     for name, g, (ref, bound) in zip(("forward", "grad_filter", "grad_values"), _autograd_products(nbr_q, nbr_n, vals, W, G), refs):
         assert C.within(g, ref, bound, 1e-13, name) <= 1.0
+
+
+@pytest.mark.parametrize("unreferenced", [False, True])
+def test_small_list_holds_what_it_plants_from_one_row_on(unreferenced):
+    """C.small_list at the row counts of the kernels' tile edges: the first row complete, the last row wholly absent where there is
+    more than one, the largest id named, every id in range, and the references take such a list (one row gives one full row)."""
+    into = 37
+    for rows in (1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 511, 512, 513, 577):
+        for e in (1, 9):
+            nbr = C.small_list(rows, into, e, np.random.default_rng(rows + e), unreferenced)
+            assert nbr.shape == (rows, e) and nbr.dtype == np.int32
+            p = C.list_properties(nbr, into)
+            assert p["in_range"] and p["has_largest"] and bool(np.all(nbr[0] >= 0)) and nbr[0, e - 1] == into - 1, p
+            assert not (unreferenced and p["has_zero"]), p
+            if rows > 1:
+                assert bool(np.all(nbr[-1] == -1)) and p["all_absent_rows"] >= 1
+            else:
+                assert p["all_absent_rows"] == 0 and p["full_rows"] == 1
+            if rows >= 15 and e == 9:  # about one entry in eight: absent neighbours inside the tile, not only in the planted last row
+                inner = nbr[1:-1]
+                assert 0.04 < float(np.mean(inner < 0)) < 0.25, float(np.mean(inner < 0))
+    nbr = C.small_list(1, into, E, np.random.default_rng(0))
+    vals, W, G = C.operands("exact", 1, into, E, V, F, np.random.default_rng(1))
+    ref, bound = C.forward(nbr, vals, W)
+    assert ref.shape == (1, F) and np.array_equal(ref[0], sum(vals[nbr[0, e]].astype(np.float64) @ W[e * V:(e + 1) * V] for e in range(E)))
+    gw, _ = C.grad_filter(nbr, vals, G)
+    assert np.array_equal(gw, np.concatenate([np.outer(vals[nbr[0, e]], G[0]) for e in range(E)]).astype(np.float64))
