@@ -1,12 +1,14 @@
-// GroupNorm (+ fused ReLU) on the native [M, C] lattice-value layout, forward and backward.
-// The reference runs torch.nn.GroupNorm on a transposed [1, C, M] view (lattice_modules.py:585-616), which on a
-// row-major value matrix costs two transposed copies in each direction; the LNN blocks (GnRelu1x1, GnReluConv,
-// GnReluFinefy, ...) apply it before every operator, so it sits between any two lattice kernels of the U-Net.
-//   statistics : per-channel partial sums over a slab of rows per workgroup (lanes run along the channels of a row:
-//                coalesced), combined across workgroups with one fp64 atomic per (workgroup, channel)
-//   apply      : every workgroup rebuilds the per-channel scale/shift from the C channel sums in LDS, then one
-//                float4 pass over its slab
+// GroupNorm and BatchNorm (+ fused ReLU) on the native [M, C] lattice-value layout, forward and backward, in three forms: GroupNorm over
+// the whole matrix, BatchNorm (GroupNorm with one channel per group, plus running statistics) and GroupNorm per row range (the clouds of
+// a batch).  The reference runs torch.nn.GroupNorm on a transposed [1, C, M] view (lattice_modules.py:585-616), two transposed copies in
+// each direction; the LNN blocks apply it before every operator, so it sits between any two lattice kernels of the U-Net.
+//   statistics : per-channel partial sums over a slab of rows per workgroup (lanes run along the channels of a row: coalesced),
+//                combined across workgroups with one fp64 atomic per (workgroup, channel) into LN_GN_REPLICAS accumulator copies
+//   apply      : every workgroup rebuilds the per-channel scale/shift from the C channel sums in LDS, then one float4 pass over its rows
 // Backward uses the same two shapes: per-channel sums of gy*x and gy, then dx = gy*gamma*rstd + x*c2[g] + c3[g].
+// Every step has ONE device body, and a kernel is a shell that resolves its rows and its slabs and calls them: ln_gn_stats_rows (the
+// sums), ln_gn_replica_sums, ln_gn_channel_affine, ln_gn_affine_rows (y), ln_gn_masked (the ReLU mask), ln_gn_backward_rows (c2 / c3 and
+// dx), ln_gn_live_rows / ln_gn_zero_next / ln_gn_zero_tail (the prologue).  A change to a formula is made in one place for every form.
 // Every fp32 sum that involves x is a sum of x - p over the LN_GN_PASSES rows of ONE thread, with the pivot p the first of these
 // rows: sum (x-p)^2 and sum gy*(x-p) have the size of the spread of those rows, not of their offset from zero, and a pivot that is an
 // outlier spoils 16 rows' worth of a sum it is itself a term of, never the whole statistic.  Each thread then puts its pivot back in
@@ -17,7 +19,39 @@
 #define LN_GN_MAX_C 1024
 #define LN_GN_PASSES 16
 #define LN_GN_REPLICAS 32  // accumulator copies: memory-side atomics serialise per cache line, so spread the workgroups
+#define LN_BN_SUM_BATCH 8  // replica loads in flight in the BatchNorm kernels (ln_gn_replica_sums)
 #define LN_GN_MAX_SEGMENTS 64  // row ranges of one call (the clouds of a batch: Lattice.set_cloud_batch)
+
+// The rows that count, 0 <= live <= m (static-rows mode: the tensors are taller than the lattice, *rows_dev rows of them are its rows;
+// the rows behind them are excluded from the statistics and written as zeros).  With no live row the forms differ, on purpose: the
+// whole-matrix kernels take their statistics with a count of 1 (all sums are zero) and publish them, the per-range kernels leave
+// mean_rstd / scale_shift of an empty range untouched.
+__device__ __forceinline__ int ln_gn_live_rows(int m, const int* __restrict__ rows_dev) { return max(0, rows_dev ? min(m, *rows_dev) : m); }
+
+// the accumulators of the NEXT call (nobody is using them now: stream order), one share per blockIdx.y, zeroed by its first workgroup
+__device__ __forceinline__ void ln_gn_zero_next(double* __restrict__ zero_next, int zero_count) {
+    if (!zero_next || blockIdx.x != 0) return;
+    const int share = (zero_count + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int end = min(zero_count, ((int)blockIdx.y + 1) * share);
+    for (int i = (int)blockIdx.y * share + threadIdx.x; i < end; i += 256) zero_next[i] = 0.0;
+}
+
+// zeros in the rows of `out` from `live` to m_tensor, spread over the linear_blocks workgroups of the grid
+__device__ __forceinline__ void ln_gn_zero_tail(float* __restrict__ out, int live, int m_tensor, int c, long long linear_block, long long linear_blocks) {
+    const long long tensor4 = (long long)m_tensor * c / 4;  // c % 4 == 0 checked by the host
+    for (long long i = (long long)live * c / 4 + linear_block * 256 + threadIdx.x; i < tensor4; i += linear_blocks * 256)
+        reinterpret_cast<float4*>(out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// gy' of the fused ReLU: the incoming gradient where the forward output x * a + b is positive, zero elsewhere (a NaN output included)
+__device__ __forceinline__ float ln_gn_masked(float g, float x, float a, float b) { return x * a + b > 0.f ? g : 0.f; }
+
+__device__ __forceinline__ void ln_gn_masked_grad(float4& g, const float4& xv, const float* s_a, const float* s_b, int col) {
+    g.x = ln_gn_masked(g.x, xv.x, s_a[col], s_b[col]);
+    g.y = ln_gn_masked(g.y, xv.y, s_a[col + 1], s_b[col + 1]);
+    g.z = ln_gn_masked(g.z, xv.z, s_a[col + 2], s_b[col + 2]);
+    g.w = ln_gn_masked(g.w, xv.w, s_a[col + 3], s_b[col + 3]);
+}
 
 // acc[c*2 + 0] += sum_rows p(row, c), acc[c*2 + 1] += sum_rows q(row, c)
 //   forward  (gy == nullptr): p = x,  q = x*x
@@ -60,10 +94,10 @@ __device__ __forceinline__ void ln_gn_stats_rows(const float* __restrict__ x, co
             if (gy) {
                 float4 g = gv[k];
                 if (relu) {
-                    if (!(xv[k].x * a.x + b.x > 0.f)) g.x = 0.f;
-                    if (!(xv[k].y * a.y + b.y > 0.f)) g.y = 0.f;
-                    if (!(xv[k].z * a.z + b.z > 0.f)) g.z = 0.f;
-                    if (!(xv[k].w * a.w + b.w > 0.f)) g.w = 0.f;
+                    g.x = ln_gn_masked(g.x, xv[k].x, a.x, b.x);
+                    g.y = ln_gn_masked(g.y, xv[k].y, a.y, b.y);
+                    g.z = ln_gn_masked(g.z, xv[k].z, a.z, b.z);
+                    g.w = ln_gn_masked(g.w, xv[k].w, a.w, b.w);
                 }
                 p.x += g.x * (xv[k].x - pv.x); p.y += g.y * (xv[k].y - pv.y); p.z += g.z * (xv[k].z - pv.z); p.w += g.w * (xv[k].w - pv.w);
                 q.x += g.x; q.y += g.y; q.z += g.z; q.w += g.w;
@@ -104,14 +138,30 @@ __device__ __forceinline__ void ln_gn_stats_rows(const float* __restrict__ x, co
     }
 }
 
-__global__ void __launch_bounds__(256)
-    k_gn_stats(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift, int relu, int m, int c,
-               double* __restrict__ acc, const int* __restrict__ rows_dev) {
-    if (rows_dev) m = min(m, *rows_dev);  // static-rows mode: the tensors are taller than the lattice, only its rows count
-    ln_gn_stats_rows(x, gy, scale_shift, relu, 0, m, c, acc, blockIdx.x);
+// The two fp64 sums of channel `col` over the accumulator replicas, added in replica order, BATCH loads of each in flight at a time.  The
+// GroupNorm bodies take all LN_GN_REPLICAS at once (one round trip in the prologue of every workgroup; the registers are free again at the
+// barrier that follows).  k_bn_apply and k_bn_backward_eval use the sums in the loop that loads them, where 64 loads in flight cost 156
+// VGPRs and with them the occupancy of the float4 pass (8 -> 3 waves, 7.5 -> 9.3 us at [120000, 32] on an MI355X): LN_BN_SUM_BATCH there.
+template <int BATCH>
+__device__ __forceinline__ void ln_gn_replica_sums(const double* __restrict__ acc, int c, int col, double& s0, double& s1) {
+    s0 = 0.0;
+    s1 = 0.0;
+    for (int r0 = 0; r0 < LN_GN_REPLICAS; r0 += BATCH) {
+        double v0[BATCH], v1[BATCH];
+#pragma unroll
+        for (int r = 0; r < BATCH; ++r) {
+            v0[r] = acc[(size_t)(r0 + r) * 2 * c + 2 * col];
+            v1[r] = acc[(size_t)(r0 + r) * 2 * c + 2 * col + 1];
+        }
+#pragma unroll
+        for (int r = 0; r < BATCH; ++r) {
+            s0 += v0[r];
+            s1 += v1[r];
+        }
+    }
 }
 
-// per-channel scale a[c] = gamma*rstd[g], shift b[c] = beta - mean[g]*a[c] from the channel sums; block 0 also
+// per-channel scale a[c] = gamma*rstd[g], shift b[c] = beta - mean[g]*a[c] from the channel sums over m rows; block 0 also
 // publishes mean/rstd per group and scale/shift per channel for the backward pass
 __device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ acc, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, int m, int c, int groups, float eps, float* s_a,
@@ -119,19 +169,9 @@ __device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ 
     if (m < 1) m = 1;  // (an empty lattice under a static row bound: all sums are zero)
     const int cg = c / groups;
     __shared__ double s_sum[LN_GN_MAX_C], s_sq[LN_GN_MAX_C];
-    for (int col = threadIdx.x; col < c; col += 256) {  // channel sums over the accumulator replicas
-        double v0[LN_GN_REPLICAS], v1[LN_GN_REPLICAS];
-#pragma unroll
-        for (int r = 0; r < LN_GN_REPLICAS; ++r) {
-            v0[r] = acc[(size_t)r * 2 * c + 2 * col];
-            v1[r] = acc[(size_t)r * 2 * c + 2 * col + 1];
-        }
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int r = 0; r < LN_GN_REPLICAS; ++r) {
-            a0 += v0[r];
-            a1 += v1[r];
-        }
+    for (int col = threadIdx.x; col < c; col += 256) {
+        double a0, a1;
+        ln_gn_replica_sums<LN_GN_REPLICAS>(acc, c, col, a0, a1);
         s_sum[col] = a0;
         s_sq[col] = a1;
     }
@@ -163,23 +203,11 @@ __device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ 
     }
 }
 
-__global__ void __launch_bounds__(256)
-    k_gn_apply(const float* __restrict__ x, const double* __restrict__ acc, const float* __restrict__ gamma, const float* __restrict__ beta,
-               int m, int c, int groups, float eps, int relu, float* __restrict__ y, float* __restrict__ mean_rstd,
-               float* __restrict__ scale_shift, double* __restrict__ zero_next, int zero_count, const int* __restrict__ rows_dev) {
-    __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
-    const int m_tensor = m;
-    if (rows_dev) m = min(m, *rows_dev);  // rows beyond the lattice: excluded from the statistics, written as zeros
-    if (zero_next && blockIdx.x == 0)  // the accumulators of the NEXT call (nobody is using them now: stream order)
-        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
-    ln_gn_channel_affine(acc, gamma, beta, m, c, groups, eps, s_a, s_b, mean_rstd, scale_shift);
-    __syncthreads();
-    const long long total4 = (long long)m * c / 4;  // c % 4 == 0 checked by the host
-    const long long tensor4 = (long long)m_tensor * c / 4;
+// y = act(x * a[c] + b[c]) over the float4 [first4, last4) of the matrix, the workgroups of blockIdx.y side by side
+__device__ __forceinline__ void ln_gn_affine_rows(const float* __restrict__ x, const float* s_a, const float* s_b, long long first4, long long last4,
+                                                  int c, int relu, float* __restrict__ y) {
     const long long stride = (long long)gridDim.x * 256;
-    for (long long i = total4 + (long long)blockIdx.x * 256 + threadIdx.x; i < tensor4; i += stride)
-        reinterpret_cast<float4*>(y)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
+    for (long long i = first4 + (long long)blockIdx.x * 256 + threadIdx.x; i < last4; i += stride) {
         const int col = int((i * 4) % c);
         float4 v = reinterpret_cast<const float4*>(x)[i];
         v.x = v.x * s_a[col] + s_b[col];
@@ -196,33 +224,20 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// dx = gy' * gamma * rstd + x * c2[g] + c3[g];   block 0 writes dgamma = (ds - db*mean)*rstd, dbeta = db   (all of it in fp64)
-__global__ void __launch_bounds__(256)
-    k_gn_backward_apply(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
-                        const float* __restrict__ gamma, const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m,
-                        int c, int groups, int relu, float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                        double* __restrict__ zero_next, int zero_count, const int* __restrict__ rows_dev) {
-    const int m_tensor = m;
-    if (rows_dev) m = min(m, *rows_dev);
-    if (m < 1) m = 1;
-    if (zero_next && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
+// dx = gy' * gamma * rstd + x * c2[g] + c3[g] over the float4 [first4, last4) of the matrix, from the channel sums of ln_gn_stats_rows
+// over `count` rows (acc, mean_rstd, scale_shift: those of the rows in question).  The first workgroup of the rows also leaves the terms
+// of the parameter gradients in LDS, in fp64: term_gamma[col] = (ds - db*mean)*rstd, term_beta[col] = db, each written by the thread that
+// owns `col` in a loop `col = threadIdx.x; col < c; col += 256` (which may read them back without a barrier).
+__device__ __forceinline__ void ln_gn_backward_rows(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
+                                                    const float* __restrict__ gamma, const float* __restrict__ mean_rstd,
+                                                    const float* __restrict__ scale_shift, int count, long long first4, long long last4, int c,
+                                                    int groups, int relu, float* __restrict__ dx, double*& term_gamma, double*& term_beta) {
     __shared__ float s_gr[LN_GN_MAX_C], s_c2[LN_GN_MAX_C], s_c3[LN_GN_MAX_C], s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
-    const int cg = c / groups;
     __shared__ double s_ds[LN_GN_MAX_C], s_db[LN_GN_MAX_C];
-    for (int col = threadIdx.x; col < c; col += 256) {  // channel sums over the accumulator replicas
-        double v0[LN_GN_REPLICAS], v1[LN_GN_REPLICAS];
-#pragma unroll
-        for (int r = 0; r < LN_GN_REPLICAS; ++r) {
-            v0[r] = acc[(size_t)r * 2 * c + 2 * col];
-            v1[r] = acc[(size_t)r * 2 * c + 2 * col + 1];
-        }
-        double ds = 0.0, db = 0.0;
-#pragma unroll
-        for (int r = 0; r < LN_GN_REPLICAS; ++r) {
-            ds += v0[r];
-            db += v1[r];
-        }
+    const int cg = c / groups;
+    for (int col = threadIdx.x; col < c; col += 256) {
+        double ds, db;
+        ln_gn_replica_sums<LN_GN_REPLICAS>(acc, c, col, ds, db);
         s_ds[col] = ds;
         s_db[col] = db;
     }
@@ -237,7 +252,7 @@ __global__ void __launch_bounds__(256)
             sum1 += s_ds[cc] * gm;
             sum2 += s_db[cc] * gm;
         }
-        const double cnt = (double)m * cg;
+        const double cnt = (double)count * cg;
         const double c2 = (sum2 * mean - sum1) * (double)rstd * rstd * rstd / cnt;
         const double c3 = -c2 * mean - sum2 * (double)rstd / cnt;
         s_gr[col] = (gamma ? gamma[col] : 1.f) * rstd;
@@ -245,27 +260,21 @@ __global__ void __launch_bounds__(256)
         s_c3[col] = (float)c3;
         s_a[col] = scale_shift[col];
         s_b[col] = scale_shift[c + col];
-        if (blockIdx.x == 0) {
-            if (dgamma) dgamma[col] = (float)((s_ds[col] - s_db[col] * mean) * rstd);
-            if (dbeta) dbeta[col] = (float)s_db[col];
-        }
     }
     __syncthreads();
-    const long long total4 = (rows_dev ? (long long)min(m_tensor, *rows_dev) : (long long)m) * c / 4;
-    const long long tensor4 = (long long)m_tensor * c / 4;
+    if (blockIdx.x == 0)  // (behind the barrier: nobody reads another channel's sum any more)
+        for (int col = threadIdx.x; col < c; col += 256) {
+            const float mean = mean_rstd[col / cg], rstd = mean_rstd[groups + col / cg];
+            s_ds[col] = (s_ds[col] - s_db[col] * mean) * rstd;
+        }
+    term_gamma = s_ds;
+    term_beta = s_db;
     const long long stride = (long long)gridDim.x * 256;
-    for (long long i = total4 + (long long)blockIdx.x * 256 + threadIdx.x; i < tensor4; i += stride)
-        reinterpret_cast<float4*>(dx)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
+    for (long long i = first4 + (long long)blockIdx.x * 256 + threadIdx.x; i < last4; i += stride) {
         const int col = int((i * 4) % c);
         const float4 xv = reinterpret_cast<const float4*>(x)[i];
         float4 g = reinterpret_cast<const float4*>(gy)[i];
-        if (relu) {
-            if (!(xv.x * s_a[col] + s_b[col] > 0.f)) g.x = 0.f;
-            if (!(xv.y * s_a[col + 1] + s_b[col + 1] > 0.f)) g.y = 0.f;
-            if (!(xv.z * s_a[col + 2] + s_b[col + 2] > 0.f)) g.z = 0.f;
-            if (!(xv.w * s_a[col + 3] + s_b[col + 3] > 0.f)) g.w = 0.f;
-        }
+        if (relu) ln_gn_masked_grad(g, xv, s_a, s_b, col);
         float4 o;
         o.x = g.x * s_gr[col] + xv.x * s_c2[col] + s_c3[col];
         o.y = g.y * s_gr[col + 1] + xv.y * s_c2[col + 1] + s_c3[col + 1];
@@ -275,139 +284,49 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-static int ln_gn_check(const char* who, int m, int c, int groups) {
-    LN_REQUIRE(m >= 1 && c >= 4 && c <= LN_GN_MAX_C && c % 4 == 0, LN_ERR_UNSUPPORTED, "%s: need 1 <= rows, channels %% 4 == 0 and <= %d (got %d x %d)",
-               who, LN_GN_MAX_C, m, c);
-    LN_REQUIRE(groups >= 1 && c % groups == 0, LN_ERR_ARG, "%s: %d groups do not divide %d channels", who, groups, c);
-    return LN_OK;
+__global__ void __launch_bounds__(256)
+    k_gn_stats(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift, int relu, int m, int c,
+               double* __restrict__ acc, const int* __restrict__ rows_dev) {
+    ln_gn_stats_rows(x, gy, scale_shift, relu, 0, ln_gn_live_rows(m, rows_dev), c, acc, blockIdx.x);
 }
 
-static int ln_gn_stats_grid(int m, int c) {
-    const int rows_per_pass = 256 / (c / 4);
-    return ln_div_up(m, rows_per_pass * LN_GN_PASSES);
+__global__ void __launch_bounds__(256)
+    k_gn_apply(const float* __restrict__ x, const double* __restrict__ acc, const float* __restrict__ gamma, const float* __restrict__ beta,
+               int m, int c, int groups, float eps, int relu, float* __restrict__ y, float* __restrict__ mean_rstd,
+               float* __restrict__ scale_shift, double* __restrict__ zero_next, int zero_count, const int* __restrict__ rows_dev) {
+    __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
+    const int live = ln_gn_live_rows(m, rows_dev);
+    ln_gn_zero_next(zero_next, zero_count);
+    ln_gn_channel_affine(acc, gamma, beta, live, c, groups, eps, s_a, s_b, mean_rstd, scale_shift);
+    __syncthreads();
+    ln_gn_zero_tail(y, live, m, c, blockIdx.x, gridDim.x);
+    ln_gn_affine_rows(x, s_a, s_b, 0, (long long)live * c / 4, c, relu, y);
 }
 
-static int ln_gn_apply_grid(int m, int c) {
-    const long long total4 = (long long)m * c / 4;
-    int grid = ln_div_up(total4, 256 * 4);
-    if (grid > 2048) grid = 2048;
-    return grid < 1 ? 1 : grid;
+// block 0 rounds the terms of ln_gn_backward_rows to dgamma, dbeta
+__global__ void __launch_bounds__(256)
+    k_gn_backward_apply(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
+                        const float* __restrict__ gamma, const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m,
+                        int c, int groups, int relu, float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                        double* __restrict__ zero_next, int zero_count, const int* __restrict__ rows_dev) {
+    const int live = ln_gn_live_rows(m, rows_dev);
+    ln_gn_zero_next(zero_next, zero_count);
+    ln_gn_zero_tail(dx, live, m, c, blockIdx.x, gridDim.x);
+    double *term_gamma, *term_beta;
+    ln_gn_backward_rows(x, gy, acc, gamma, mean_rstd, scale_shift, max(live, 1), 0, (long long)live * c / 4, c, groups, relu, dx, term_gamma,
+                        term_beta);
+    if (blockIdx.x == 0)
+        for (int col = threadIdx.x; col < c; col += 256) {
+            if (dgamma) dgamma[col] = (float)term_gamma[col];
+            if (dbeta) dbeta[col] = (float)term_beta[col];
+        }
 }
 
-extern "C" size_t ln_group_norm_workspace_bytes(int channels) { return (size_t)LN_GN_REPLICAS * 2 * channels * sizeof(double); }
-
-extern "C" int ln_group_norm_forward_rows(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
-                                          int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
-                                          void* next_workspace, size_t next_workspace_bytes, const int* rows_device, void* stream);
-extern "C" int ln_group_norm_forward(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
-                                     int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
-                                     void* next_workspace, size_t next_workspace_bytes, void* stream) {
-    return ln_group_norm_forward_rows(x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace, workspace_bytes,
-                                      next_workspace, next_workspace_bytes, nullptr, stream);
-}
-extern "C" int ln_group_norm_forward_rows(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
-                                          int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
-                                          void* next_workspace, size_t next_workspace_bytes, const int* rows_device, void* stream) {
-    int rc = ln_gn_check("ln_group_norm_forward", m, channels, groups);
-    if (rc) return rc;
-    LN_REQUIRE(x && y && mean_rstd && scale_shift && workspace && workspace_bytes >= ln_group_norm_workspace_bytes(channels), LN_ERR_ARG,
-               "ln_group_norm_forward: null buffer or workspace too small");
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-               LN_ERR_ARG, "ln_group_norm_forward: x / y must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    double* acc = static_cast<double*>(workspace);
-    // next_workspace != NULL: the caller alternates two workspaces and promises `workspace` is zero (it was `next_workspace` of
-    // the previous call on this stream, or freshly zeroed); this call zero-fills `next_workspace` on its way out.
-    if (!next_workspace && ln_zero_async(acc, ln_group_norm_workspace_bytes(channels), st) != LN_OK)
-        return ln_check_launch("ln_group_norm_forward(memset)");
-    LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, 0, m,
-              channels, acc, rows_device);
-    LN_LAUNCH("k_gn_apply", k_gn_apply, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, acc, gamma, beta, m, channels, groups, eps, relu, y,
-              mean_rstd, scale_shift, static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device);
-    return ln_check_launch("ln_group_norm_forward");
-}
-
-extern "C" int ln_group_norm_backward_rows(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
-                                           const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
-                                           float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
-                                           size_t next_workspace_bytes, const int* rows_device, void* stream);
-extern "C" int ln_group_norm_backward(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
-                                      const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
-                                      float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, void* stream) {
-    return ln_group_norm_backward_rows(x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x, grad_gamma, grad_beta, workspace,
-                                       workspace_bytes, next_workspace, next_workspace_bytes, nullptr, stream);
-}
-extern "C" int ln_group_norm_backward_rows(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
-                                           const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
-                                           float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
-                                           size_t next_workspace_bytes, const int* rows_device, void* stream) {
-    int rc = ln_gn_check("ln_group_norm_backward", m, channels, groups);
-    if (rc) return rc;
-    LN_REQUIRE(x && grad_y && mean_rstd && scale_shift && grad_x && workspace && workspace_bytes >= ln_group_norm_workspace_bytes(channels),
-               LN_ERR_ARG, "ln_group_norm_backward: null buffer or workspace too small");
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0, LN_ERR_ARG,
-               "ln_group_norm_backward: x / grad_y / grad_x must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    double* acc = static_cast<double*>(workspace);
-    if (!next_workspace && ln_zero_async(acc, ln_group_norm_workspace_bytes(channels), st) != LN_OK)
-        return ln_check_launch("ln_group_norm_backward(memset)");
-    LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, grad_y, scale_shift, relu, m, channels, acc, rows_device);
-    LN_LAUNCH("k_gn_backward_apply", k_gn_backward_apply, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, grad_y, acc, gamma, mean_rstd,
-              scale_shift, m, channels, groups, relu, grad_x, grad_gamma, grad_beta, static_cast<double*>(next_workspace),
-              int(next_workspace_bytes / sizeof(double)), rows_device);
-    return ln_check_launch("ln_group_norm_backward");
-}
-
-// ---- BatchNorm (+ fused ReLU) over the same [M, C] layout: GroupNorm with one channel per group, plus running statistics ----------
+// ---- BatchNorm: GroupNorm with one channel per group, plus running statistics --------------------------------------------------------
 // Training: k_gn_stats gives the fp64 channel sums exactly as for GroupNorm (same summation, same bounds), k_bn_apply turns them into
 // scale / shift and moves the running statistics on the device; the backward is k_gn_backward_apply at groups == channels.
 // Evaluation: the statistics are the running ones, constants of the step: one launch forward; backward dx = gy' * a, and the
 // parameter gradients from the same k_gn_stats sums.
-
-// the two fp64 sums of channel `col` over the accumulator replicas, added in replica order (the order of ln_gn_channel_affine), eight
-// loads in flight at a time
-__device__ __forceinline__ void ln_bn_channel_sums(const double* __restrict__ acc, int c, int col, double& s0, double& s1) {
-    s0 = 0.0;
-    s1 = 0.0;
-    for (int r0 = 0; r0 < LN_GN_REPLICAS; r0 += 8) {
-        double v0[8], v1[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            v0[r] = acc[(size_t)(r0 + r) * 2 * c + 2 * col];
-            v1[r] = acc[(size_t)(r0 + r) * 2 * c + 2 * col + 1];
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            s0 += v0[r];
-            s1 += v1[r];
-        }
-    }
-}
-
-// y = act(x * a[c] + b[c]) over the first m rows, zeros in the rows from m to m_tensor
-__device__ __forceinline__ void ln_bn_apply_rows(const float* __restrict__ x, const float* s_a, const float* s_b, int m, int m_tensor, int c,
-                                                 int relu, float* __restrict__ y) {
-    const long long total4 = (long long)m * c / 4;  // c % 4 == 0 checked by the host
-    const long long tensor4 = (long long)m_tensor * c / 4;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = total4 + (long long)blockIdx.x * 256 + threadIdx.x; i < tensor4; i += stride)
-        reinterpret_cast<float4*>(y)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
-        const int col = int((i * 4) % c);
-        float4 v = reinterpret_cast<const float4*>(x)[i];
-        v.x = v.x * s_a[col] + s_b[col];
-        v.y = v.y * s_a[col + 1] + s_b[col + 1];
-        v.z = v.z * s_a[col + 2] + s_b[col + 2];
-        v.w = v.w * s_a[col + 3] + s_b[col + 3];
-        if (relu) {
-            v.x = fmaxf(v.x, 0.f);
-            v.y = fmaxf(v.y, 0.f);
-            v.z = fmaxf(v.z, 0.f);
-            v.w = fmaxf(v.w, 0.f);
-        }
-        reinterpret_cast<float4*>(y)[i] = v;
-    }
-}
 
 // Training forward.  Every workgroup rebuilds a = gamma * rstd, b = beta - mean * a from the fp64 channel sums (biased variance, clamped
 // at 0; n = live rows); block 0 publishes mean_rstd / scale_shift and, with n >= 2, moves the running statistics (unbiased variance),
@@ -418,14 +337,12 @@ __global__ void __launch_bounds__(256)
                float* __restrict__ y, float* __restrict__ mean_rstd, float* __restrict__ scale_shift, double* __restrict__ zero_next,
                int zero_count, const int* __restrict__ rows_dev) {
     __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
-    const int m_tensor = m;
-    if (rows_dev) m = max(0, min(m, *rows_dev));  // rows beyond the lattice: excluded from the statistics, written as zeros
-    if (zero_next && blockIdx.x == 0)  // the accumulators of the NEXT call (nobody is using them now: stream order)
-        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
-    const double cnt = m < 1 ? 1.0 : (double)m;  // (an empty lattice under a static row bound: all sums are zero)
+    const int live = ln_gn_live_rows(m, rows_dev);
+    ln_gn_zero_next(zero_next, zero_count);
+    const double cnt = live < 1 ? 1.0 : (double)live;  // (an empty lattice under a static row bound: all sums are zero)
     for (int col = threadIdx.x; col < c; col += 256) {
         double s, ss;
-        ln_bn_channel_sums(acc, c, col, s, ss);
+        ln_gn_replica_sums<LN_BN_SUM_BATCH>(acc, c, col, s, ss);
         const double mean = s / cnt;
         double var = ss / cnt - mean * mean;  // (fp64 sums of fp32 data: the cancellation costs 2^-53 mean^2 / var)
         if (var < 0.0) var = 0.0;
@@ -439,14 +356,15 @@ __global__ void __launch_bounds__(256)
             mean_rstd[c + col] = rstd;
             scale_shift[col] = a;
             scale_shift[c + col] = b;
-            if (running_mean && m >= 2) {  // (one row has no unbiased variance: nothing moves)
+            if (running_mean && live >= 2) {  // (one row has no unbiased variance: nothing moves)
                 running_mean[col] = (float)((1.0 - momentum) * (double)running_mean[col] + momentum * mean);
                 running_var[col] = (float)((1.0 - momentum) * (double)running_var[col] + momentum * (var * (cnt / (cnt - 1.0))));
             }
         }
     }
     __syncthreads();
-    ln_bn_apply_rows(x, s_a, s_b, m, m_tensor, c, relu, y);
+    ln_gn_zero_tail(y, live, m, c, blockIdx.x, gridDim.x);
+    ln_gn_affine_rows(x, s_a, s_b, 0, (long long)live * c / 4, c, relu, y);
 }
 
 // Evaluation forward: a = gamma / sqrt(running_var + eps) (rstd formed in fp64, rounded once), b = beta - running_mean * a (fp64, rounded
@@ -457,10 +375,8 @@ __global__ void __launch_bounds__(256)
                     float* __restrict__ y, float* __restrict__ mean_rstd, float* __restrict__ scale_shift, double* __restrict__ zero_next,
                     int zero_count, const int* __restrict__ rows_dev) {
     __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
-    const int m_tensor = m;
-    if (rows_dev) m = max(0, min(m, *rows_dev));
-    if (zero_next && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
+    const int live = ln_gn_live_rows(m, rows_dev);
+    ln_gn_zero_next(zero_next, zero_count);
     for (int col = threadIdx.x; col < c; col += 256) {
         const float mean = running_mean[col];
         const float rstd = (float)(1.0 / sqrt((double)running_var[col] + (double)eps));
@@ -476,113 +392,41 @@ __global__ void __launch_bounds__(256)
         }
     }
     __syncthreads();
-    ln_bn_apply_rows(x, s_a, s_b, m, m_tensor, c, relu, y);
+    ln_gn_zero_tail(y, live, m, c, blockIdx.x, gridDim.x);
+    ln_gn_affine_rows(x, s_a, s_b, 0, (long long)live * c / 4, c, relu, y);
 }
 
-// Evaluation backward: dx = gy' * a;  block 0 writes dgamma = (ds - db * running_mean) * rstd, dbeta = db in fp64 from the k_gn_stats
-// sums (acc == nullptr: no parameter gradient is wanted and no sums were taken).
+// Evaluation backward: dx = gy' * a (its own loop: no c2 / c3, and x is read only for the mask);  block 0 writes
+// dgamma = (ds - db * running_mean) * rstd, dbeta = db in fp64 from the k_gn_stats sums (acc == nullptr: no parameter gradient is wanted
+// and no sums were taken).
 __global__ void __launch_bounds__(256)
     k_bn_backward_eval(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
                        const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m, int c, int relu,
                        float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta, double* __restrict__ zero_next,
                        int zero_count, const int* __restrict__ rows_dev) {
     __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
-    const int m_tensor = m;
-    if (rows_dev) m = max(0, min(m, *rows_dev));
-    if (zero_next && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < zero_count; i += 256) zero_next[i] = 0.0;
+    const int live = ln_gn_live_rows(m, rows_dev);
+    ln_gn_zero_next(zero_next, zero_count);
     for (int col = threadIdx.x; col < c; col += 256) {
         s_a[col] = scale_shift[col];
         s_b[col] = scale_shift[c + col];
         if (acc && blockIdx.x == 0) {
             double ds, db;
-            ln_bn_channel_sums(acc, c, col, ds, db);
+            ln_gn_replica_sums<LN_BN_SUM_BATCH>(acc, c, col, ds, db);
             if (dgamma) dgamma[col] = (float)((ds - db * (double)mean_rstd[col]) * (double)mean_rstd[c + col]);
             if (dbeta) dbeta[col] = (float)db;
         }
     }
     __syncthreads();
-    const long long total4 = (long long)m * c / 4;
-    const long long tensor4 = (long long)m_tensor * c / 4;
+    ln_gn_zero_tail(dx, live, m, c, blockIdx.x, gridDim.x);
+    const long long total4 = (long long)live * c / 4;
     const long long stride = (long long)gridDim.x * 256;
-    for (long long i = total4 + (long long)blockIdx.x * 256 + threadIdx.x; i < tensor4; i += stride)
-        reinterpret_cast<float4*>(dx)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
         const int col = int((i * 4) % c);
         float4 g = reinterpret_cast<const float4*>(gy)[i];
-        if (relu) {
-            const float4 xv = reinterpret_cast<const float4*>(x)[i];
-            if (!(xv.x * s_a[col] + s_b[col] > 0.f)) g.x = 0.f;
-            if (!(xv.y * s_a[col + 1] + s_b[col + 1] > 0.f)) g.y = 0.f;
-            if (!(xv.z * s_a[col + 2] + s_b[col + 2] > 0.f)) g.z = 0.f;
-            if (!(xv.w * s_a[col + 3] + s_b[col + 3] > 0.f)) g.w = 0.f;
-        }
+        if (relu) ln_gn_masked_grad(g, reinterpret_cast<const float4*>(x)[i], s_a, s_b, col);
         reinterpret_cast<float4*>(dx)[i] = make_float4(g.x * s_a[col], g.y * s_a[col + 1], g.z * s_a[col + 2], g.w * s_a[col + 3]);
     }
-}
-
-extern "C" size_t ln_batch_norm_workspace_bytes(int channels) { return ln_group_norm_workspace_bytes(channels); }
-
-extern "C" int ln_batch_norm_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int m,
-                                     int channels, float eps, double momentum, int training, int relu, float* y, float* mean_rstd,
-                                     float* scale_shift, void* workspace, size_t workspace_bytes, void* next_workspace,
-                                     size_t next_workspace_bytes, const int* rows_device, void* stream) {
-    int rc = ln_gn_check("ln_batch_norm_forward", m, channels, channels);
-    if (rc) return rc;
-    LN_REQUIRE(x && y && mean_rstd && scale_shift, LN_ERR_ARG, "ln_batch_norm_forward: null buffer");
-    LN_REQUIRE(!running_mean == !running_var, LN_ERR_ARG, "ln_batch_norm_forward: running_mean and running_var come together or not at all");
-    LN_REQUIRE(training || running_mean, LN_ERR_ARG, "ln_batch_norm_forward: evaluation mode needs the running statistics");
-    LN_REQUIRE(!training || (workspace && workspace_bytes >= ln_batch_norm_workspace_bytes(channels)), LN_ERR_ARG,
-               "ln_batch_norm_forward: null or too small workspace");
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(next_workspace) & 7) == 0,
-               LN_ERR_ARG, "ln_batch_norm_forward: x / y must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    double* zero_next = static_cast<double*>(next_workspace);
-    const int zero_count = int(next_workspace_bytes / sizeof(double));
-    if (!training) {  // the running statistics are the statistics: no sums, `workspace` is not touched
-        LN_LAUNCH("k_bn_apply_eval", k_bn_apply_eval, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, gamma, beta,
-                  (const float*)running_mean, (const float*)running_var, m, channels, eps, relu, y, mean_rstd, scale_shift, zero_next, zero_count,
-                  rows_device);
-        return ln_check_launch("ln_batch_norm_forward");
-    }
-    double* acc = static_cast<double*>(workspace);
-    if (!next_workspace && ln_zero_async(acc, ln_batch_norm_workspace_bytes(channels), st) != LN_OK)
-        return ln_check_launch("ln_batch_norm_forward(memset)");
-    LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, 0, m,
-              channels, acc, rows_device);
-    LN_LAUNCH("k_bn_apply", k_bn_apply, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, (const double*)acc, gamma, beta, running_mean,
-              running_var, m, channels, eps, momentum, relu, y, mean_rstd, scale_shift, zero_next, zero_count, rows_device);
-    return ln_check_launch("ln_batch_norm_forward");
-}
-
-extern "C" int ln_batch_norm_backward(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd, const float* scale_shift,
-                                      int m, int channels, int training, int relu, float* grad_x, float* grad_gamma, float* grad_beta,
-                                      void* workspace, size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes,
-                                      const int* rows_device, void* stream) {
-    int rc = ln_gn_check("ln_batch_norm_backward", m, channels, channels);
-    if (rc) return rc;
-    LN_REQUIRE(x && grad_y && mean_rstd && scale_shift && grad_x && workspace && workspace_bytes >= ln_batch_norm_workspace_bytes(channels),
-               LN_ERR_ARG, "ln_batch_norm_backward: null buffer or workspace too small");
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0 &&
-                   ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(next_workspace)) & 7) == 0,
-               LN_ERR_ARG, "ln_batch_norm_backward: x / grad_y / grad_x must be 16-byte aligned");
-    if (training)  // GroupNorm with one channel per group: the same sums, the same formula (the arguments were checked above)
-        return ln_group_norm_backward_rows(x, grad_y, gamma, mean_rstd, scale_shift, m, channels, channels, relu, grad_x, grad_gamma, grad_beta,
-                                           workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device, stream);
-    hipStream_t st = (hipStream_t)stream;
-    double* acc = static_cast<double*>(workspace);
-    const bool sums = grad_gamma || grad_beta;  // (without parameter gradients dx = gy' * a needs no sum: `workspace` stays as it is)
-    if (sums) {
-        if (!next_workspace && ln_zero_async(acc, ln_batch_norm_workspace_bytes(channels), st) != LN_OK)
-            return ln_check_launch("ln_batch_norm_backward(memset)");
-        LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, grad_y, scale_shift, relu, m, channels, acc,
-                  rows_device);
-    }
-    LN_LAUNCH("k_bn_backward_eval", k_bn_backward_eval, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, grad_y,
-              sums ? (const double*)acc : (const double*)nullptr, mean_rstd, scale_shift, m, channels, relu, grad_x, grad_gamma, grad_beta,
-              static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device);
-    return ln_check_launch("ln_batch_norm_backward");
 }
 
 // ---- GroupNorm per row range: a batch of clouds in one table (LnTable.batch_points) ------------------------------------------------
@@ -616,26 +460,10 @@ __global__ void __launch_bounds__(256) k_cloud_row_starts(LnTable t, int rows_up
     for (int s = prev + 1; s <= cur; ++s) row_starts[s] = r;  // (clouds without a vertex start where the next one does)
 }
 
-extern "C" int ln_cloud_row_starts(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream) {
-    LN_REQUIRE(t && t->keys && t->nr_filled && t->pos_dim >= 1 && t->pos_dim <= LN_MAX_POS_DIM, LN_ERR_ARG, "ln_cloud_row_starts: null table");
-    LN_REQUIRE((t->batch_points > 0 || t->batch_points == LN_BATCH_POINT_STARTS) && t->batch_key_step >= 2, LN_ERR_ARG,
-               "ln_cloud_row_starts: the table holds no batch of clouds");
-    LN_REQUIRE(clouds >= 1 && clouds <= LN_GN_MAX_SEGMENTS, LN_ERR_UNSUPPORTED, "ln_cloud_row_starts: 1 <= clouds <= %d (got %d)",
-               LN_GN_MAX_SEGMENTS, clouds);
-    LN_REQUIRE(rows_upper >= 0 && row_starts && order_flag, LN_ERR_ARG, "ln_cloud_row_starts: null output or negative rows_upper");
-    hipStream_t st = (hipStream_t)stream;
-    if (ln_zero_async(order_flag, sizeof(int), st) != LN_OK) return ln_check_launch("ln_cloud_row_starts(memset)");
-    LN_LAUNCH("k_cloud_row_starts", k_cloud_row_starts, dim3(ln_div_up((long long)rows_upper + 1, 256)), dim3(256), 0, st, *t, rows_upper, clouds,
-              row_starts, order_flag);
-    return ln_check_launch("ln_cloud_row_starts");
-}
-
 // rows [lo, hi) of range s, clamped to 0 <= lo <= hi <= live whatever row_starts holds (nothing is indexed outside the tensors); live = the rows that count
 __device__ __forceinline__ void ln_gn_segment(const int* __restrict__ row_starts, int segments, int s, int m, const int* __restrict__ rows_dev,
                                               int& live, int& lo, int& hi) {
-    live = min(m, row_starts[segments]);
-    if (rows_dev) live = min(live, *rows_dev);
-    live = max(live, 0);
+    live = ln_gn_live_rows(min(m, row_starts[segments]), rows_dev);
     lo = min(max(row_starts[s], 0), live);
     hi = min(max(row_starts[s + 1], lo), live);
 }
@@ -652,18 +480,11 @@ __global__ void __launch_bounds__(256)
                      blockIdx.x);
 }
 
-// the accumulators of the NEXT call, one share per range (the first workgroup of every range), and zeros in the rows behind the last range
-__device__ __forceinline__ void ln_gn_segments_housekeeping(double* __restrict__ zero_next, int zero_count, int segments, int live, int m, int c,
+// the prologue of the two apply kernels: the next call's accumulators, and zeros in the rows behind the last range (all workgroups of the 2-D grid)
+__device__ __forceinline__ void ln_gn_segments_housekeeping(double* __restrict__ zero_next, int zero_count, int live, int m, int c,
                                                             float* __restrict__ out) {
-    if (zero_next && blockIdx.x == 0) {
-        const int share = (zero_count + segments - 1) / segments;
-        const int end = min(zero_count, ((int)blockIdx.y + 1) * share);
-        for (int i = (int)blockIdx.y * share + threadIdx.x; i < end; i += 256) zero_next[i] = 0.0;
-    }
-    const long long total4 = (long long)live * c / 4, tensor4 = (long long)m * c / 4;
-    const long long stride = (long long)gridDim.x * gridDim.y * 256;
-    for (long long i = total4 + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < tensor4; i += stride)
-        reinterpret_cast<float4*>(out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    ln_gn_zero_next(zero_next, zero_count);
+    ln_gn_zero_tail(out, live, m, c, (long long)blockIdx.y * gridDim.x + blockIdx.x, (long long)gridDim.x * gridDim.y);
 }
 
 __global__ void __launch_bounds__(256)
@@ -675,32 +496,16 @@ __global__ void __launch_bounds__(256)
     const int s = blockIdx.y;
     int live, lo, hi;
     ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
-    ln_gn_segments_housekeeping(zero_next, zero_count, segments, live, m, c, y);
+    ln_gn_segments_housekeeping(zero_next, zero_count, live, m, c, y);
     if (hi == lo) return;  // an empty range: no statistics, no rows
     ln_gn_channel_affine(acc + (size_t)s * LN_GN_REPLICAS * 2 * c, gamma, beta, hi - lo, c, groups, eps, s_a, s_b, mean_rstd + (size_t)s * 2 * groups,
                          scale_shift + (size_t)s * 2 * c);
     __syncthreads();
-    const long long last4 = (long long)hi * c / 4;  // c % 4 == 0 checked by the host
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)lo * c / 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < last4; i += stride) {
-        const int col = int((i * 4) % c);
-        float4 v = reinterpret_cast<const float4*>(x)[i];
-        v.x = v.x * s_a[col] + s_b[col];
-        v.y = v.y * s_a[col + 1] + s_b[col + 1];
-        v.z = v.z * s_a[col + 2] + s_b[col + 2];
-        v.w = v.w * s_a[col + 3] + s_b[col + 3];
-        if (relu) {
-            v.x = fmaxf(v.x, 0.f);
-            v.y = fmaxf(v.y, 0.f);
-            v.z = fmaxf(v.z, 0.f);
-            v.w = fmaxf(v.w, 0.f);
-        }
-        reinterpret_cast<float4*>(y)[i] = v;
-    }
+    ln_gn_affine_rows(x, s_a, s_b, (long long)lo * c / 4, (long long)hi * c / 4, c, relu, y);
 }
 
-// k_gn_backward_apply over range blockIdx.y.  The parameter gradients are sums over the ranges: the first workgroup of range s leaves its
-// terms, (ds - db mean_s) rstd_s and db in fp64, in parts[s * 2 C ...] (zeros for an empty range); k_gn_param_grads_segments adds them.
+// ln_gn_backward_rows over range blockIdx.y.  The parameter gradients are sums over the ranges: the first workgroup of range s leaves its
+// terms in parts[s * 2 C ...], in fp64 (zeros for an empty range); k_gn_param_grads_segments adds them.
 __global__ void __launch_bounds__(256)
     k_gn_backward_apply_segments(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
                                  const float* __restrict__ gamma, const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m,
@@ -709,69 +514,21 @@ __global__ void __launch_bounds__(256)
     const int s = blockIdx.y;
     int live, lo, hi;
     ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
-    ln_gn_segments_housekeeping(zero_next, zero_count, segments, live, m, c, dx);
+    ln_gn_segments_housekeeping(zero_next, zero_count, live, m, c, dx);
     parts += (size_t)s * 2 * c;
     if (hi == lo) {
         if (blockIdx.x == 0)
             for (int i = threadIdx.x; i < 2 * c; i += 256) parts[i] = 0.0;
         return;
     }
-    acc += (size_t)s * LN_GN_REPLICAS * 2 * c;
-    mean_rstd += (size_t)s * 2 * groups;
-    scale_shift += (size_t)s * 2 * c;
-    __shared__ float s_gr[LN_GN_MAX_C], s_c2[LN_GN_MAX_C], s_c3[LN_GN_MAX_C], s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
-    const int cg = c / groups;
-    __shared__ double s_ds[LN_GN_MAX_C], s_db[LN_GN_MAX_C];
-    for (int col = threadIdx.x; col < c; col += 256) {  // channel sums over the accumulator replicas, in replica order
-        double ds, db;
-        ln_bn_channel_sums(acc, c, col, ds, db);
-        s_ds[col] = ds;
-        s_db[col] = db;
-    }
-    __syncthreads();
-    for (int col = threadIdx.x; col < c; col += 256) {
-        const int g = col / cg;
-        const float mean = mean_rstd[g], rstd = mean_rstd[groups + g];
-        double sum1 = 0.0, sum2 = 0.0;  // sum over the group's channels of ds*gamma, db*gamma
-        for (int k = 0; k < cg; ++k) {
-            const int cc = g * cg + k;
-            const double gm = gamma ? (double)gamma[cc] : 1.0;
-            sum1 += s_ds[cc] * gm;
-            sum2 += s_db[cc] * gm;
+    double *term_gamma, *term_beta;
+    ln_gn_backward_rows(x, gy, acc + (size_t)s * LN_GN_REPLICAS * 2 * c, gamma, mean_rstd + (size_t)s * 2 * groups, scale_shift + (size_t)s * 2 * c,
+                        hi - lo, (long long)lo * c / 4, (long long)hi * c / 4, c, groups, relu, dx, term_gamma, term_beta);
+    if (blockIdx.x == 0)
+        for (int col = threadIdx.x; col < c; col += 256) {
+            parts[col] = term_gamma[col];
+            parts[c + col] = term_beta[col];
         }
-        const double cnt = (double)(hi - lo) * cg;
-        const double c2 = (sum2 * mean - sum1) * (double)rstd * rstd * rstd / cnt;
-        const double c3 = -c2 * mean - sum2 * (double)rstd / cnt;
-        s_gr[col] = (gamma ? gamma[col] : 1.f) * rstd;
-        s_c2[col] = (float)c2;
-        s_c3[col] = (float)c3;
-        s_a[col] = scale_shift[col];
-        s_b[col] = scale_shift[c + col];
-        if (blockIdx.x == 0) {
-            parts[col] = (s_ds[col] - s_db[col] * mean) * rstd;
-            parts[c + col] = s_db[col];
-        }
-    }
-    __syncthreads();
-    const long long last4 = (long long)hi * c / 4;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)lo * c / 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < last4; i += stride) {
-        const int col = int((i * 4) % c);
-        const float4 xv = reinterpret_cast<const float4*>(x)[i];
-        float4 g = reinterpret_cast<const float4*>(gy)[i];
-        if (relu) {
-            if (!(xv.x * s_a[col] + s_b[col] > 0.f)) g.x = 0.f;
-            if (!(xv.y * s_a[col + 1] + s_b[col + 1] > 0.f)) g.y = 0.f;
-            if (!(xv.z * s_a[col + 2] + s_b[col + 2] > 0.f)) g.z = 0.f;
-            if (!(xv.w * s_a[col + 3] + s_b[col + 3] > 0.f)) g.w = 0.f;
-        }
-        float4 o;
-        o.x = g.x * s_gr[col] + xv.x * s_c2[col] + s_c3[col];
-        o.y = g.y * s_gr[col + 1] + xv.y * s_c2[col + 1] + s_c3[col + 1];
-        o.z = g.z * s_gr[col + 2] + xv.z * s_c2[col + 2] + s_c3[col + 2];
-        o.w = g.w * s_gr[col + 3] + xv.w * s_c2[col + 3] + s_c3[col + 3];
-        reinterpret_cast<float4*>(dx)[i] = o;
-    }
 }
 
 // dgamma[col] = sum_s parts[s][col], dbeta[col] = sum_s parts[s][C + col]: fp64, ranges added in order, one rounding to fp32
@@ -791,21 +548,180 @@ __global__ void __launch_bounds__(256)
     if (out) out[i < c ? i : i - c] = (float)sum;
 }
 
+static int ln_gn_check(const char* who, int m, int c, int groups) {
+    LN_REQUIRE(m >= 1 && c >= 4 && c <= LN_GN_MAX_C && c % 4 == 0, LN_ERR_UNSUPPORTED, "%s: need 1 <= rows, channels %% 4 == 0 and <= %d (got %d x %d)",
+               who, LN_GN_MAX_C, m, c);
+    LN_REQUIRE(groups >= 1 && c % groups == 0, LN_ERR_ARG, "%s: %d groups do not divide %d channels", who, groups, c);
+    return LN_OK;
+}
+
+// The buffers of a call: its [M, C] matrices (x, y forward; x, grad_y, grad_x backward) non-null and 16-byte aligned for the float4 passes,
+// mean_rstd / scale_shift non-null, `workspace` non-null with at least `need` bytes (need == 0: a call that takes no sums and leaves
+// `workspace` alone), both workspaces 8-byte aligned.
+static int ln_norm_check_buffers(const char* who, const void* x, const void* grad_y, const void* out, const void* mean_rstd, const void* scale_shift,
+                                 const void* workspace, size_t workspace_bytes, size_t need, const void* next_workspace, bool backward) {
+    LN_REQUIRE(x && out && mean_rstd && scale_shift && (grad_y || !backward), LN_ERR_ARG, "%s: null buffer", who);
+    LN_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), LN_ERR_ARG, "%s: null workspace, or smaller than %zu bytes", who, need);
+    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0, LN_ERR_ARG,
+               "%s: the [rows, channels] matrices must be 16-byte aligned", who);
+    LN_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(next_workspace)) & 7) == 0, LN_ERR_ARG,
+               "%s: the workspaces must be 8-byte aligned", who);
+    return LN_OK;
+}
+
+static int ln_gn_stats_grid(int m, int c) {
+    const int rows_per_pass = 256 / (c / 4);
+    return ln_div_up(m, rows_per_pass * LN_GN_PASSES);
+}
+
+static int ln_gn_apply_grid(int m, int c) {
+    const long long total4 = (long long)m * c / 4;
+    int grid = ln_div_up(total4, 256 * 4);
+    if (grid > 2048) grid = 2048;
+    return grid < 1 ? 1 : grid;
+}
+
+extern "C" size_t ln_group_norm_workspace_bytes(int channels) { return (size_t)LN_GN_REPLICAS * 2 * channels * sizeof(double); }
+
+extern "C" int ln_group_norm_forward_rows(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
+                                          int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
+                                          void* next_workspace, size_t next_workspace_bytes, const int* rows_device, void* stream) {
+    int rc = ln_gn_check("ln_group_norm_forward", m, channels, groups);
+    if (rc) return rc;
+    rc = ln_norm_check_buffers("ln_group_norm_forward", x, nullptr, y, mean_rstd, scale_shift, workspace, workspace_bytes,
+                               ln_group_norm_workspace_bytes(channels), next_workspace, false);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double* acc = static_cast<double*>(workspace);
+    // next_workspace != NULL: the caller alternates two workspaces and promises `workspace` is zero (it was `next_workspace` of
+    // the previous call on this stream, or freshly zeroed); this call zero-fills `next_workspace` on its way out.
+    if (!next_workspace && ln_zero_async(acc, ln_group_norm_workspace_bytes(channels), st) != LN_OK)
+        return ln_check_launch("ln_group_norm_forward(memset)");
+    LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, 0, m,
+              channels, acc, rows_device);
+    LN_LAUNCH("k_gn_apply", k_gn_apply, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, acc, gamma, beta, m, channels, groups, eps, relu, y,
+              mean_rstd, scale_shift, static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device);
+    return ln_check_launch("ln_group_norm_forward");
+}
+
+extern "C" int ln_group_norm_forward(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
+                                     int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
+                                     void* next_workspace, size_t next_workspace_bytes, void* stream) {
+    return ln_group_norm_forward_rows(x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace, workspace_bytes,
+                                      next_workspace, next_workspace_bytes, nullptr, stream);
+}
+
+extern "C" int ln_group_norm_backward_rows(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
+                                           const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
+                                           float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
+                                           size_t next_workspace_bytes, const int* rows_device, void* stream) {
+    int rc = ln_gn_check("ln_group_norm_backward", m, channels, groups);
+    if (rc) return rc;
+    rc = ln_norm_check_buffers("ln_group_norm_backward", x, grad_y, grad_x, mean_rstd, scale_shift, workspace, workspace_bytes,
+                               ln_group_norm_workspace_bytes(channels), next_workspace, true);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double* acc = static_cast<double*>(workspace);
+    if (!next_workspace && ln_zero_async(acc, ln_group_norm_workspace_bytes(channels), st) != LN_OK)
+        return ln_check_launch("ln_group_norm_backward(memset)");
+    LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, grad_y, scale_shift, relu, m, channels, acc, rows_device);
+    LN_LAUNCH("k_gn_backward_apply", k_gn_backward_apply, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, grad_y, acc, gamma, mean_rstd,
+              scale_shift, m, channels, groups, relu, grad_x, grad_gamma, grad_beta, static_cast<double*>(next_workspace),
+              int(next_workspace_bytes / sizeof(double)), rows_device);
+    return ln_check_launch("ln_group_norm_backward");
+}
+
+extern "C" int ln_group_norm_backward(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
+                                      const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
+                                      float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, void* stream) {
+    return ln_group_norm_backward_rows(x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x, grad_gamma, grad_beta, workspace,
+                                       workspace_bytes, next_workspace, next_workspace_bytes, nullptr, stream);
+}
+
+extern "C" size_t ln_batch_norm_workspace_bytes(int channels) { return ln_group_norm_workspace_bytes(channels); }
+
+extern "C" int ln_batch_norm_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int m,
+                                     int channels, float eps, double momentum, int training, int relu, float* y, float* mean_rstd,
+                                     float* scale_shift, void* workspace, size_t workspace_bytes, void* next_workspace,
+                                     size_t next_workspace_bytes, const int* rows_device, void* stream) {
+    int rc = ln_gn_check("ln_batch_norm_forward", m, channels, channels);
+    if (rc) return rc;
+    LN_REQUIRE(!running_mean == !running_var, LN_ERR_ARG, "ln_batch_norm_forward: running_mean and running_var come together or not at all");
+    LN_REQUIRE(training || running_mean, LN_ERR_ARG, "ln_batch_norm_forward: evaluation mode needs the running statistics");
+    rc = ln_norm_check_buffers("ln_batch_norm_forward", x, nullptr, y, mean_rstd, scale_shift, workspace, workspace_bytes,
+                               training ? ln_batch_norm_workspace_bytes(channels) : 0, next_workspace, false);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double* zero_next = static_cast<double*>(next_workspace);
+    const int zero_count = int(next_workspace_bytes / sizeof(double));
+    if (!training) {  // the running statistics are the statistics: no sums, `workspace` is not touched
+        LN_LAUNCH("k_bn_apply_eval", k_bn_apply_eval, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, gamma, beta,
+                  (const float*)running_mean, (const float*)running_var, m, channels, eps, relu, y, mean_rstd, scale_shift, zero_next, zero_count,
+                  rows_device);
+        return ln_check_launch("ln_batch_norm_forward");
+    }
+    double* acc = static_cast<double*>(workspace);
+    if (!next_workspace && ln_zero_async(acc, ln_batch_norm_workspace_bytes(channels), st) != LN_OK)
+        return ln_check_launch("ln_batch_norm_forward(memset)");
+    LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, 0, m,
+              channels, acc, rows_device);
+    LN_LAUNCH("k_bn_apply", k_bn_apply, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, (const double*)acc, gamma, beta, running_mean,
+              running_var, m, channels, eps, momentum, relu, y, mean_rstd, scale_shift, zero_next, zero_count, rows_device);
+    return ln_check_launch("ln_batch_norm_forward");
+}
+
+extern "C" int ln_batch_norm_backward(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd, const float* scale_shift,
+                                      int m, int channels, int training, int relu, float* grad_x, float* grad_gamma, float* grad_beta,
+                                      void* workspace, size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes,
+                                      const int* rows_device, void* stream) {
+    int rc = ln_gn_check("ln_batch_norm_backward", m, channels, channels);
+    if (rc) return rc;
+    rc = ln_norm_check_buffers("ln_batch_norm_backward", x, grad_y, grad_x, mean_rstd, scale_shift, workspace, workspace_bytes,
+                               ln_batch_norm_workspace_bytes(channels), next_workspace, true);
+    if (rc) return rc;
+    if (training)  // GroupNorm with one channel per group: the same sums, the same formula (the arguments were checked above)
+        return ln_group_norm_backward_rows(x, grad_y, gamma, mean_rstd, scale_shift, m, channels, channels, relu, grad_x, grad_gamma, grad_beta,
+                                           workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device, stream);
+    hipStream_t st = (hipStream_t)stream;
+    double* acc = static_cast<double*>(workspace);
+    const bool sums = grad_gamma || grad_beta;  // (without parameter gradients dx = gy' * a needs no sum: `workspace` stays as it is)
+    if (sums) {
+        if (!next_workspace && ln_zero_async(acc, ln_batch_norm_workspace_bytes(channels), st) != LN_OK)
+            return ln_check_launch("ln_batch_norm_backward(memset)");
+        LN_LAUNCH("k_gn_stats", k_gn_stats, dim3(ln_gn_stats_grid(m, channels)), dim3(256), 0, st, x, grad_y, scale_shift, relu, m, channels, acc,
+                  rows_device);
+    }
+    LN_LAUNCH("k_bn_backward_eval", k_bn_backward_eval, dim3(ln_gn_apply_grid(m, channels)), dim3(256), 0, st, x, grad_y,
+              sums ? (const double*)acc : (const double*)nullptr, mean_rstd, scale_shift, m, channels, relu, grad_x, grad_gamma, grad_beta,
+              static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device);
+    return ln_check_launch("ln_batch_norm_backward");
+}
+
+extern "C" int ln_cloud_row_starts(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream) {
+    LN_REQUIRE(t && t->keys && t->nr_filled && t->pos_dim >= 1 && t->pos_dim <= LN_MAX_POS_DIM, LN_ERR_ARG, "ln_cloud_row_starts: null table");
+    LN_REQUIRE((t->batch_points > 0 || t->batch_points == LN_BATCH_POINT_STARTS) && t->batch_key_step >= 2, LN_ERR_ARG,
+               "ln_cloud_row_starts: the table holds no batch of clouds");
+    LN_REQUIRE(clouds >= 1 && clouds <= LN_GN_MAX_SEGMENTS, LN_ERR_UNSUPPORTED, "ln_cloud_row_starts: 1 <= clouds <= %d (got %d)",
+               LN_GN_MAX_SEGMENTS, clouds);
+    LN_REQUIRE(rows_upper >= 0 && row_starts && order_flag, LN_ERR_ARG, "ln_cloud_row_starts: null output or negative rows_upper");
+    hipStream_t st = (hipStream_t)stream;
+    if (ln_zero_async(order_flag, sizeof(int), st) != LN_OK) return ln_check_launch("ln_cloud_row_starts(memset)");
+    LN_LAUNCH("k_cloud_row_starts", k_cloud_row_starts, dim3(ln_div_up((long long)rows_upper + 1, 256)), dim3(256), 0, st, *t, rows_upper, clouds,
+              row_starts, order_flag);
+    return ln_check_launch("ln_cloud_row_starts");
+}
+
 // B accumulator slabs, then the B x 2 C parameter-gradient terms of the backward call
 extern "C" size_t ln_group_norm_segments_workspace_bytes(int channels, int segments) {
     return (size_t)segments * (ln_group_norm_workspace_bytes(channels) + 2 * (size_t)channels * sizeof(double));
 }
 
-static int ln_gn_segments_check(const char* who, int m, int c, int groups, int segments, const int* row_starts, void* workspace, size_t workspace_bytes,
-                                void* next_workspace) {
+static int ln_gn_segments_check(const char* who, int m, int c, int groups, int segments, const int* row_starts) {
     int rc = ln_gn_check(who, m, c, groups);
     if (rc) return rc;
     LN_REQUIRE(segments >= 1 && segments <= LN_GN_MAX_SEGMENTS, LN_ERR_UNSUPPORTED, "%s: 1 <= row ranges <= %d (got %d)", who, LN_GN_MAX_SEGMENTS,
                segments);
-    LN_REQUIRE(row_starts && workspace && workspace_bytes >= ln_group_norm_segments_workspace_bytes(c, segments), LN_ERR_ARG,
-               "%s: null row_starts or workspace too small", who);
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(next_workspace)) & 7) == 0, LN_ERR_ARG,
-               "%s: workspaces must be 8-byte aligned", who);
+    LN_REQUIRE(row_starts, LN_ERR_ARG, "%s: null row_starts", who);
     return LN_OK;
 }
 
@@ -816,11 +732,11 @@ extern "C" int ln_group_norm_forward_segments(const float* x, const float* gamma
                                               int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
                                               void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
                                               int segments, void* stream) {
-    int rc = ln_gn_segments_check("ln_group_norm_forward_segments", m, channels, groups, segments, row_starts, workspace, workspace_bytes, next_workspace);
+    int rc = ln_gn_segments_check("ln_group_norm_forward_segments", m, channels, groups, segments, row_starts);
     if (rc) return rc;
-    LN_REQUIRE(x && y && mean_rstd && scale_shift, LN_ERR_ARG, "ln_group_norm_forward_segments: null buffer");
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, LN_ERR_ARG,
-               "ln_group_norm_forward_segments: x / y must be 16-byte aligned");
+    rc = ln_norm_check_buffers("ln_group_norm_forward_segments", x, nullptr, y, mean_rstd, scale_shift, workspace, workspace_bytes,
+                               ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, false);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     double* acc = static_cast<double*>(workspace);
     if (!next_workspace && ln_zero_async(acc, (size_t)segments * ln_group_norm_workspace_bytes(channels), st) != LN_OK)
@@ -837,11 +753,11 @@ extern "C" int ln_group_norm_backward_segments(const float* x, const float* grad
                                                const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
                                                float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
                                                size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream) {
-    int rc = ln_gn_segments_check("ln_group_norm_backward_segments", m, channels, groups, segments, row_starts, workspace, workspace_bytes, next_workspace);
+    int rc = ln_gn_segments_check("ln_group_norm_backward_segments", m, channels, groups, segments, row_starts);
     if (rc) return rc;
-    LN_REQUIRE(x && grad_y && mean_rstd && scale_shift && grad_x, LN_ERR_ARG, "ln_group_norm_backward_segments: null buffer");
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0, LN_ERR_ARG,
-               "ln_group_norm_backward_segments: x / grad_y / grad_x must be 16-byte aligned");
+    rc = ln_norm_check_buffers("ln_group_norm_backward_segments", x, grad_y, grad_x, mean_rstd, scale_shift, workspace, workspace_bytes,
+                               ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, true);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     double* acc = static_cast<double*>(workspace);
     const size_t slabs = (size_t)segments * ln_group_norm_workspace_bytes(channels);

@@ -132,23 +132,59 @@ def _gn_check(rc: int, what: str, device, stream: int):
     _lib.check(rc, what)
 
 
+def _gn_forward(x, weight, bias, num_groups, eps, relu, rows_dev, row_starts=None):
+    """The GroupNorm forward launch, over the whole matrix or (`row_starts`) per row range: x made contiguous, y, mean_rstd [2 groups] and
+    scale_shift [2 C] (one row of each per range with `row_starts`)."""
+    lib = _lib.load()
+    x = x.contiguous()
+    m, c = x.shape
+    ranged = row_starts is not None
+    segments = int(row_starts.numel()) - 1 if ranged else 1
+    y = torch.empty_like(x)
+    mean_rstd = torch.empty((segments, 2 * num_groups) if ranged else (2 * num_groups,), dtype=torch.float32, device=x.device)
+    scale_shift = torch.empty((segments, 2 * c) if ranged else (2 * c,), dtype=torch.float32, device=x.device)
+    stream = _lib.stream_ptr(x.device)
+    nbytes = lib.ln_group_norm_segments_workspace_bytes(c, segments) if ranged else lib.ln_group_norm_workspace_bytes(c)
+    ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, nbytes)
+    args = (_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), m, c, num_groups, float(eps), int(relu), _lib.ptr(y), _lib.ptr(mean_rstd),
+            _lib.ptr(scale_shift), _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev))
+    if ranged:
+        _gn_check(lib.ln_group_norm_forward_segments(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_forward_segments", x.device, stream)
+    else:
+        _gn_check(lib.ln_group_norm_forward_rows(*args, stream), "ln_group_norm_forward", x.device, stream)
+    return x, y, mean_rstd, scale_shift
+
+
+def _gn_backward(grad_y, x, weight, mean_rstd, scale_shift, num_groups, relu, has_bias, rows_dev, row_starts=None):
+    """The GroupNorm backward launch that goes with _gn_forward: grad_x, grad_weight and grad_bias (None where there is no parameter)."""
+    lib = _lib.load()
+    grad_y = grad_y.contiguous()
+    m, c = x.shape
+    ranged = row_starts is not None
+    segments = int(row_starts.numel()) - 1 if ranged else 1
+    grad_x = torch.empty_like(x)
+    grad_w = torch.empty((c,), dtype=torch.float32, device=x.device) if weight is not None else None
+    grad_b = torch.empty((c,), dtype=torch.float32, device=x.device) if has_bias else None
+    stream = _lib.stream_ptr(x.device)
+    nbytes = lib.ln_group_norm_segments_workspace_bytes(c, segments) if ranged else lib.ln_group_norm_workspace_bytes(c)
+    ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, nbytes)
+    args = (_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(weight), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), m, c, num_groups, int(relu),
+            _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b), _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev))
+    if ranged:
+        _gn_check(lib.ln_group_norm_backward_segments(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_backward_segments", x.device,
+                  stream)
+    else:
+        _gn_check(lib.ln_group_norm_backward_rows(*args, stream), "ln_group_norm_backward", x.device, stream)
+    return grad_x, grad_w, grad_b
+
+
 class GroupNormReluFunction(torch.autograd.Function):
     """GroupNorm (+ optional fused ReLU) over an [M, C] value matrix on the HIP kernels of csrc/ln_norm.hip
     (ln_group_norm_forward / _backward): statistics per group over all vertices x the group's channels."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, num_groups, eps, relu, rows_dev=None):
-        lib = _lib.load()
-        x = x.contiguous()
-        m, c = x.shape
-        y = torch.empty_like(x)
-        mean_rstd = torch.empty((2 * num_groups,), dtype=torch.float32, device=x.device)
-        scale_shift = torch.empty((2 * c,), dtype=torch.float32, device=x.device)
-        stream = _lib.stream_ptr(x.device)
-        ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_group_norm_workspace_bytes(c))
-        _gn_check(lib.ln_group_norm_forward_rows(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), m, c, num_groups, float(eps), int(relu),
-                                                 _lib.ptr(y), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), _lib.ptr(ws), ws.numel() * 8,
-                                                 _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev), stream), "ln_group_norm_forward", x.device, stream)
+        x, y, mean_rstd, scale_shift = _gn_forward(x, weight, bias, num_groups, eps, relu, rows_dev)
         ctx.rows_dev = rows_dev  # device-side row count of the lattice (static-rows mode), None otherwise
         ctx.save_for_backward(x, weight, mean_rstd, scale_shift)
         ctx.args = (num_groups, bool(relu), bias is not None)
@@ -156,21 +192,7 @@ class GroupNormReluFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_y):
-        lib = _lib.load()
-        x, weight, mean_rstd, scale_shift = ctx.saved_tensors
-        num_groups, relu, has_bias = ctx.args
-        grad_y = grad_y.contiguous()
-        m, c = x.shape
-        grad_x = torch.empty_like(x)
-        grad_w = torch.empty((c,), dtype=torch.float32, device=x.device) if weight is not None else None
-        grad_b = torch.empty((c,), dtype=torch.float32, device=x.device) if has_bias else None
-        stream = _lib.stream_ptr(x.device)
-        ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_group_norm_workspace_bytes(c))
-        _gn_check(lib.ln_group_norm_backward_rows(_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(weight), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), m, c,
-                                                  num_groups, int(relu), _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b), _lib.ptr(ws),
-                                                  ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(ctx.rows_dev), stream),
-                  "ln_group_norm_backward", x.device, stream)
-        return grad_x, grad_w, grad_b, None, None, None, None
+        return (*_gn_backward(grad_y, *ctx.saved_tensors, *ctx.args, ctx.rows_dev), None, None, None, None)
 
 
 class GroupNormSegmentsFunction(torch.autograd.Function):
@@ -181,19 +203,7 @@ class GroupNormSegmentsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, num_groups, eps, relu, rows_dev, row_starts):
-        lib = _lib.load()
-        x = x.contiguous()
-        m, c = x.shape
-        segments = int(row_starts.numel()) - 1
-        y = torch.empty_like(x)
-        mean_rstd = torch.empty((segments, 2 * num_groups), dtype=torch.float32, device=x.device)
-        scale_shift = torch.empty((segments, 2 * c), dtype=torch.float32, device=x.device)
-        stream = _lib.stream_ptr(x.device)
-        ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_group_norm_segments_workspace_bytes(c, segments))
-        _gn_check(lib.ln_group_norm_forward_segments(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), m, c, num_groups, float(eps), int(relu),
-                                                     _lib.ptr(y), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), _lib.ptr(ws), ws.numel() * 8,
-                                                     _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev), _lib.ptr(row_starts), segments, stream),
-                  "ln_group_norm_forward_segments", x.device, stream)
+        x, y, mean_rstd, scale_shift = _gn_forward(x, weight, bias, num_groups, eps, relu, rows_dev, row_starts)
         ctx.rows_dev, ctx.row_starts = rows_dev, row_starts
         ctx.save_for_backward(x, weight, mean_rstd, scale_shift)
         ctx.args = (num_groups, bool(relu), bias is not None)
@@ -201,23 +211,7 @@ class GroupNormSegmentsFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_y):
-        lib = _lib.load()
-        x, weight, mean_rstd, scale_shift = ctx.saved_tensors
-        num_groups, relu, has_bias = ctx.args
-        grad_y = grad_y.contiguous()
-        m, c = x.shape
-        segments = int(ctx.row_starts.numel()) - 1
-        grad_x = torch.empty_like(x)
-        grad_w = torch.empty((c,), dtype=torch.float32, device=x.device) if weight is not None else None
-        grad_b = torch.empty((c,), dtype=torch.float32, device=x.device) if has_bias else None
-        stream = _lib.stream_ptr(x.device)
-        ws, ws_next, zero_bytes = _gn_workspace_pair(x.device, stream, lib.ln_group_norm_segments_workspace_bytes(c, segments))
-        _gn_check(lib.ln_group_norm_backward_segments(_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(weight), _lib.ptr(mean_rstd), _lib.ptr(scale_shift),
-                                                      m, c, num_groups, int(relu), _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b),
-                                                      _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(ctx.rows_dev),
-                                                      _lib.ptr(ctx.row_starts), segments, stream),
-                  "ln_group_norm_backward_segments", x.device, stream)
-        return grad_x, grad_w, grad_b, None, None, None, None, None
+        return (*_gn_backward(grad_y, *ctx.saved_tensors, *ctx.args, ctx.rows_dev, ctx.row_starts), None, None, None, None, None)
 
 
 class MaxCentreFunction(torch.autograd.Function):

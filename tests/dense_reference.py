@@ -13,6 +13,7 @@ EPS32 = 2.0 ** -24
 
 # csrc/ln_norm.hip
 LN_GN_PASSES = 16
+LN_GN_REPLICAS = 32
 # csrc/ln_mlp.hip
 LN_MLP_TILE = 64
 LN_MLP_W_GRID = 512
