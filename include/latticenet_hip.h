@@ -735,6 +735,47 @@ int ln_nll_forward_clouds(const float* log_probs, const long long* target, long 
 int ln_nll_backward_clouds(const long long* target, const float* grad_loss, const float* weight_sum, long long n, long long points_per_cloud,
                            int classes, long long ignore_index, const float* class_weight, float* grad_log_probs, void* stream);
 
+/* The three per-cloud losses above for a batch of clouds of UNEQUAL sizes (Lattice.set_cloud_batch([l_0, l_1, ...])): each _ranges
+ * entry point takes what its counterpart takes, with (point_starts, clouds, longest) in place of points_per_cloud.  point_starts is a device
+ * list of clouds + 1 ints, the list an LnTableClouds keeps as batch_point_starts; cloud b owns rows [point_starts[b], point_starts[b + 1]).
+ * CONTRACT ON THE LIST: ascending, point_starts[0] = 0, point_starts[clouds] = n, no cloud longer than `longest` (the host's copy of the
+ * longest length: grids and workspace strides are sized by it, nothing is read back).  WHATEVER THE LIST HOLDS, THE KERNELS STAY INSIDE THE
+ * n ROWS and inside the workspace: a cloud's range is clamped into [0, n] and its length to `longest`; a list that breaks the contract
+ * gives values without meaning, never an access out of bounds.
+ * Everything else is the equal-size form: the arithmetic and the order of every sum (a cloud is cut and summed by its own length alone, so
+ * per_cloud[b] and the per-cloud side outputs are what the one-cloud call gives on the cloud's rows, bit for bit, and lengths
+ * (n0, .., n0, rest) give the bits of the equal-size entry point), no float atomics, one launch backward, the launches forward, safe inside
+ * a stream capture (the list is read by the kernels only: the same pointer must hold the same lengths at every replay).
+ * An EMPTY cloud (point_starts[b] == point_starts[b + 1]) is a legal cloud and counts in the mean over the clouds: NLL per_cloud 0 (as -0)
+ * and weight_sum 1; Lovasz 0 (per_class row 0); Dice (classes other than ignore_index) / classes, stats 0, its coef row without meaning (no
+ * row reads it); no gradient row.  The backward kernels find a row's cloud by a binary search of the
+ * list that steps over empty clouds.  n == 0 (every cloud empty): the forward calls write those values and the mean, the backward calls
+ * launch nothing.
+ * Refused with nothing launched or written, the message of ln_last_error_string naming the entry point: point_starts == NULL, clouds < 1,
+ * longest < 0 or longest > n (LN_ERR_ARG); clouds > 65535 and the size limits of the counterpart (n * classes < 2^31, classes <= 1024), with
+ * the counterpart's code (LN_ERR_UNSUPPORTED for the NLL entries, LN_ERR_ARG otherwise); null buffers and a workspace below the
+ * *_ranges_workspace_bytes function — pure host functions of (n, clouds, longest[, classes]), total over any arguments.  The Lovasz
+ * workspace holds clouds x classes x tiles(longest) histograms: it grows with one long cloud among many short ones.
+ * ln_lovasz_forward_ranges has no backward of its own: ln_lovasz_backward is the backward.
+ * ln_iou_counts_clouds has no such form yet, and losses.py does not call these entry points yet: its points_per_cloud= takes equal sizes. */
+size_t ln_nll_ranges_workspace_bytes(long long n, int clouds, long long longest);
+int ln_nll_forward_ranges(const float* log_probs, const long long* target, long long n, const int* point_starts, int clouds, long long longest,
+                          int classes, long long ignore_index, const float* class_weight, void* workspace, size_t workspace_bytes, float* loss,
+                          float* per_cloud, float* weight_sum, void* stream);
+int ln_nll_backward_ranges(const long long* target, const float* grad_loss, const float* weight_sum, long long n, const int* point_starts,
+                           int clouds, long long longest, int classes, long long ignore_index, const float* class_weight,
+                           float* grad_log_probs, void* stream);
+size_t ln_dice_ranges_workspace_bytes(long long n, int clouds, long long longest, int classes);
+int ln_dice_forward_ranges(const float* log_probs, const long long* target, long long n, const int* point_starts, int clouds, long long longest,
+                           int classes, long long ignore_index, void* workspace, size_t workspace_bytes, float* loss, float* per_cloud,
+                           float* stats, float* coef, void* stream);
+int ln_dice_backward_ranges(const float* log_probs, const long long* target, const float* coef, const float* grad_loss, long long n,
+                            const int* point_starts, int clouds, long long longest, int classes, float* grad_log_probs, void* stream);
+size_t ln_lovasz_ranges_workspace_bytes(long long n, int clouds, long long longest, int classes);
+int ln_lovasz_forward_ranges(const float* log_probs, const long long* target, long long n, const int* point_starts, int clouds,
+                             long long longest, int classes, long long ignore_index, int reduction, void* workspace, size_t workspace_bytes,
+                             float* loss, float* per_cloud, float* per_class, float* dloss_dlogp, void* stream);
+
 /* Band check of a batch of clouds in one table (LnTable.batch_points / batch_key_step): a launch sequence of its own, queued on `stream`
  * behind the build of `t` from the same positions and sigmas; the build kernels are not involved.  B = ceil(n / batch_points) clouds, or,
  * for a table that heads an LnTableClouds, its batch_clouds clouds with the point ranges of its batch_point_starts (every cloud reduces

@@ -184,6 +184,14 @@ SIGNATURES = {
     "ln_dice_workspace_bytes": (_sz, [_ll, _ll, _i]),
     "ln_dice_forward": (_i, [_vp, _vp, _ll, _ll, _i, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ln_dice_backward": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _i, _vp, _vp]),
+    "ln_nll_ranges_workspace_bytes": (_sz, [_ll, _i, _ll]),
+    "ln_nll_forward_ranges": (_i, [_vp, _vp, _ll, _vp, _i, _ll, _i, _ll, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ln_nll_backward_ranges": (_i, [_vp, _vp, _vp, _ll, _vp, _i, _ll, _i, _ll, _vp, _vp, _vp]),
+    "ln_dice_ranges_workspace_bytes": (_sz, [_ll, _i, _ll, _i]),
+    "ln_dice_forward_ranges": (_i, [_vp, _vp, _ll, _vp, _i, _ll, _i, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ln_dice_backward_ranges": (_i, [_vp, _vp, _vp, _vp, _ll, _vp, _i, _ll, _i, _vp, _vp]),
+    "ln_lovasz_ranges_workspace_bytes": (_sz, [_ll, _i, _ll, _i]),
+    "ln_lovasz_forward_ranges": (_i, [_vp, _vp, _ll, _vp, _i, _ll, _i, _ll, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ln_max_centre_forward": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp]),
     "ln_max_centre_backward_workspace_bytes": (_sz, [_ll, _i, _i]),
     "ln_max_centre_backward": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -10,6 +10,10 @@
 // from the cloud contributes w_c / C.  A batch: cloud b owns rows [b n0, min((b + 1) n0, n)), the loss is the mean over the clouds of
 // each cloud's own loss, and a, b carry the 1 / clouds.
 //
+// Clouds of unequal sizes (ln_dice_forward_ranges / ln_dice_backward_ranges): cloud b owns the rows point_starts[b] .. point_starts[b + 1] of
+// a device list (LnCloudsListed, ln_loss_common.h); the same kernels instantiated on the list, the grid and the stride of a cloud's
+// partials by the longest cloud.  A cloud of no rows has no tile: its I, S, G are 0 and its loss sum_c w_c / C.
+//
 // Arithmetic, pinned so that tests/dice_reference.py can count its roundings: p = expf(lp) (OCML, 1 ulp); every sum in a fixed order,
 // no float atomics; G in 32-bit integers, converted once; IEEE division; no contraction (-ffp-contract=off).
 //
@@ -58,11 +62,13 @@ static inline int ln_dice_grid_tiles(long long n0, int C) {
     return int(t < LN_DICE_MAX_TILES ? t : LN_DICE_MAX_TILES);
 }
 
-template <bool WIDE>  // WIDE: C > 256
+// CUT, in the kernels that walk a cloud: how the batch is cut (ln_loss_common.h) — the rows of a full cloud (long long: the instances of
+// ln_dice_forward) or LnCloudsListed (ln_dice_forward_ranges).  The host picks the instance.
+template <bool WIDE, class CUT>  // WIDE: C > 256
 __global__ void __launch_bounds__(LN_DICE_THREADS)
-    k_dice_partials(const float* __restrict__ lp, const long long* __restrict__ target, long long n, long long n0, int C,
+    k_dice_partials(const float* __restrict__ lp, const long long* __restrict__ target, long long n, CUT cut, int C,
                     uint32_t* __restrict__ partial) {
-    const LnCloudRange cloud = ln_cloud_range(n, n0, blockIdx.y);
+    const LnCloudRange cloud = ln_cloud_range(n, cut, blockIdx.y);
     const long long first = cloud.first, len = cloud.len;
     const LnDiceTiling T = ln_dice_tiling(len, C);
     if ((int)blockIdx.x >= T.tiles) return;  // (the whole workgroup)
@@ -142,15 +148,16 @@ __global__ void __launch_bounds__(LN_DICE_THREADS)
 }
 
 // `terms` [B, C]: the class terms, written and read back by this workgroup alone (a barrier in between)
+template <class CUT>
 __global__ void __launch_bounds__(LN_DICE_THREADS)
-    k_dice_finish(const uint32_t* __restrict__ partial, long long n, long long n0, int C, int B, int grid_tiles, long long ignore_index,
+    k_dice_finish(const uint32_t* __restrict__ partial, long long n, CUT cut, int C, int B, int grid_tiles, long long ignore_index,
                   float* __restrict__ terms, float* __restrict__ loss, float* __restrict__ per_cloud, float* __restrict__ stats,
                   float* __restrict__ coef) {
     __shared__ float s_w[LN_DICE_WAVES];
     const float Cf = float(C), Bf = float(B);
     for (long long item = threadIdx.x; item < (long long)B * C; item += LN_DICE_THREADS) {
         const int b = int(item / C), c = int(item - (long long)b * C);
-        const int tiles = ln_dice_tiling(ln_cloud_range(n, n0, b).len, C).tiles;
+        const int tiles = ln_dice_tiling(ln_cloud_range(n, cut, b).len, C).tiles;
         const uint32_t* p = partial + (long long)b * grid_tiles * 3 * C + c;
         float I = 0.f, S = 0.f;
         uint32_t G = 0u;
@@ -200,14 +207,18 @@ __global__ void __launch_bounds__(LN_DICE_THREADS)
     if (threadIdx.x == 0) loss[0] = total / Bf;
 }
 
+// the cloud of a row: row / n0 for equal sizes, the search of the list otherwise (no division by n0 in that form)
+__device__ __forceinline__ int ln_cloud_of_row(int row, int n0) { return row / n0; }
+
+template <class CLOUD_OF>  // CLOUD_OF: int (n0) or LnCloudOfRowListed; the host picks
 __global__ void __launch_bounds__(256)
     k_dice_backward(const float* __restrict__ lp, const long long* __restrict__ target, const float* __restrict__ coef,
-                    const float* __restrict__ grad_loss, int total, int n0, int C, float* __restrict__ grad_lp) {
+                    const float* __restrict__ grad_loss, int total, CLOUD_OF cloud_of, int C, float* __restrict__ grad_lp) {
     const long long g64 = (long long)blockIdx.x * 256 + threadIdx.x;
     if (g64 >= total) return;
     const int g = int(g64);  // n * C < 2^31: 32-bit divisions
     const int i = g / C, c = g - i * C;
-    const float* ab = coef + (long long)(i / n0) * 2 * C;
+    const float* ab = coef + (long long)ln_cloud_of_row(i, cloud_of) * 2 * C;
     const float a = ab[c], b = ab[C + c];
     const float p = expf(lp[g]);
     const float t = target[i] == c ? a - b : -b;
@@ -234,6 +245,30 @@ LnDiceLayout ln_dice_layout(long long n, long long points_per_cloud, int classes
     L.terms = (B * size_t(L.grid_tiles) * 3 * size_t(Cc) * 4 + 255) & ~size_t(255);
     L.bytes = ((L.terms + B * size_t(Cc) * 4 + 255) & ~size_t(255)) + 256;
     return L;
+}
+// The layout of a listed batch (ln_loss_common.h, LnCloudsListed): the grid and the stride of a cloud's partials by the longest cloud, at
+// least one tile (a batch of empty clouds still runs the finish).  Total: clouds is brought into [1, LN_DICE_MAX_CLOUDS], longest into [0, n].
+LnDiceLayout ln_dice_layout_ranges(long long n, long long clouds, long long longest, int classes) {
+    LnDiceLayout L;
+    const long long N = n < 0 ? 0 : (n < (1ll << 31) ? n : 1ll << 31);
+    const int Cc = classes < 1 ? 1 : (classes > LN_DICE_MAX_CLASSES ? LN_DICE_MAX_CLASSES : classes);
+    L.n0 = longest < 0 ? 0 : (longest > N ? N : longest);
+    L.clouds = clouds < 1 ? 1 : (clouds > LN_DICE_MAX_CLOUDS ? LN_DICE_MAX_CLOUDS : clouds);
+    const size_t B = size_t(L.clouds);
+    L.grid_tiles = ln_dice_grid_tiles(L.n0, Cc);
+    if (L.grid_tiles < 1) L.grid_tiles = 1;
+    L.partial = 0;
+    L.terms = (B * size_t(L.grid_tiles) * 3 * size_t(Cc) * 4 + 255) & ~size_t(255);
+    L.bytes = ((L.terms + B * size_t(Cc) * 4 + 255) & ~size_t(255)) + 256;
+    return L;
+}
+int ln_dice_sizes_ranges(const char* who, long long n, const int* point_starts, int clouds, long long longest, int classes, LnDiceLayout& L) {
+    LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_DICE_MAX_CLASSES, LN_ERR_ARG, "%s: bad sizes (n >= 0, 1 <= classes <= %d)", who,
+               LN_DICE_MAX_CLASSES);
+    LN_REQUIRE(n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_ARG, "%s: n * classes must stay below 2^31", who);
+    LN_REQUIRE_CLOUD_LIST(who, n, point_starts, clouds, longest, LN_DICE_MAX_CLOUDS, LN_ERR_ARG);
+    L = ln_dice_layout_ranges(n, clouds, longest, classes);
+    return LN_OK;
 }
 int ln_dice_sizes(const char* who, long long n, long long points_per_cloud, int classes, LnDiceLayout& L) {
     LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_DICE_MAX_CLASSES, LN_ERR_ARG, "%s: bad sizes (n >= 0, 1 <= classes <= %d)", who,
@@ -267,10 +302,10 @@ extern "C" int ln_dice_forward(const float* log_probs, const long long* target, 
     float* terms = reinterpret_cast<float*>(ws + L.terms);
     const dim3 grid(L.grid_tiles, (unsigned)L.clouds), thr(LN_DICE_THREADS);
     if (classes <= LN_DICE_THREADS)
-        LN_LAUNCH("k_dice_partials", k_dice_partials<false>, grid, thr, 0, st, log_probs, target, n, L.n0, classes, partial);
+        LN_LAUNCH("k_dice_partials", (k_dice_partials<false, long long>), grid, thr, 0, st, log_probs, target, n, L.n0, classes, partial);
     else
-        LN_LAUNCH("k_dice_partials", k_dice_partials<true>, grid, thr, 0, st, log_probs, target, n, L.n0, classes, partial);
-    LN_LAUNCH("k_dice_finish", k_dice_finish, dim3(1), thr, 0, st, partial, n, L.n0, classes, int(L.clouds), L.grid_tiles, ignore_index, terms,
+        LN_LAUNCH("k_dice_partials", (k_dice_partials<true, long long>), grid, thr, 0, st, log_probs, target, n, L.n0, classes, partial);
+    LN_LAUNCH("k_dice_finish", k_dice_finish<long long>, dim3(1), thr, 0, st, partial, n, L.n0, classes, int(L.clouds), L.grid_tiles, ignore_index, terms,
               loss, per_cloud, stats, coef);
     return ln_check_launch("ln_dice_forward");
 }
@@ -282,7 +317,49 @@ extern "C" int ln_dice_backward(const float* log_probs, const long long* target,
     if (rc != LN_OK) return rc;
     if (n == 0) return LN_OK;
     LN_REQUIRE(log_probs && target && coef && grad_loss && grad_log_probs, LN_ERR_ARG, "ln_dice_backward: null buffer");
-    LN_LAUNCH("k_dice_backward", k_dice_backward, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, log_probs, target, coef,
+    LN_LAUNCH("k_dice_backward", k_dice_backward<int>, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, log_probs, target, coef,
               grad_loss, int(n * classes), int(L.n0), classes, grad_log_probs);
     return ln_check_launch("ln_dice_backward");
+}
+
+// Clouds of unequal sizes: the rows of cloud b from point_starts.
+extern "C" size_t ln_dice_ranges_workspace_bytes(long long n, int clouds, long long longest, int classes) {
+    return ln_dice_layout_ranges(n, clouds, longest, classes).bytes;
+}
+
+extern "C" int ln_dice_forward_ranges(const float* log_probs, const long long* target, long long n, const int* point_starts, int clouds,
+                                      long long longest, int classes, long long ignore_index, void* workspace, size_t workspace_bytes,
+                                      float* loss, float* per_cloud, float* stats, float* coef, void* stream) {
+    LnDiceLayout L;
+    const int rc = ln_dice_sizes_ranges("ln_dice_forward_ranges", n, point_starts, clouds, longest, classes, L);
+    if (rc != LN_OK) return rc;
+    LN_REQUIRE(loss && coef, LN_ERR_ARG, "ln_dice_forward_ranges: null buffer");
+    LN_REQUIRE(n == 0 || (log_probs && target), LN_ERR_ARG, "ln_dice_forward_ranges: null buffer");
+    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_dice_forward_ranges: null / small workspace (%zu bytes needed)", L.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* partial = reinterpret_cast<uint32_t*>(ws + L.partial);
+    float* terms = reinterpret_cast<float*>(ws + L.terms);
+    const LnCloudsListed cut{point_starts, L.n0};
+    const dim3 grid(L.grid_tiles, (unsigned)L.clouds), thr(LN_DICE_THREADS);
+    if (classes <= LN_DICE_THREADS)
+        LN_LAUNCH("k_dice_partials", (k_dice_partials<false, LnCloudsListed>), grid, thr, 0, st, log_probs, target, n, cut, classes, partial);
+    else
+        LN_LAUNCH("k_dice_partials", (k_dice_partials<true, LnCloudsListed>), grid, thr, 0, st, log_probs, target, n, cut, classes, partial);
+    LN_LAUNCH("k_dice_finish", k_dice_finish<LnCloudsListed>, dim3(1), thr, 0, st, partial, n, cut, classes, int(L.clouds), L.grid_tiles, ignore_index, terms, loss,
+              per_cloud, stats, coef);
+    return ln_check_launch("ln_dice_forward_ranges");
+}
+
+extern "C" int ln_dice_backward_ranges(const float* log_probs, const long long* target, const float* coef, const float* grad_loss, long long n,
+                                       const int* point_starts, int clouds, long long longest, int classes, float* grad_log_probs,
+                                       void* stream) {
+    LnDiceLayout L;
+    const int rc = ln_dice_sizes_ranges("ln_dice_backward_ranges", n, point_starts, clouds, longest, classes, L);
+    if (rc != LN_OK) return rc;
+    if (n == 0) return LN_OK;
+    LN_REQUIRE(log_probs && target && coef && grad_loss && grad_log_probs, LN_ERR_ARG, "ln_dice_backward_ranges: null buffer");
+    LN_LAUNCH("k_dice_backward", k_dice_backward<LnCloudOfRowListed>, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, log_probs, target,
+              coef, grad_loss, int(n * classes), LnCloudOfRowListed{point_starts, clouds}, classes, grad_log_probs);
+    return ln_check_launch("ln_dice_backward_ranges");
 }

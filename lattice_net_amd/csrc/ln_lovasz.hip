@@ -33,6 +33,10 @@
 // full: the buffers stay n C words), its tile histograms, tile counts and tile sums at  (b C + c) * tiles(n0);  the payload is the
 // point's index INSIDE its cloud.  The single-cloud call is the case n0 = n, B = 1 of the same launches.  k_lovasz_finish runs one
 // workgroup per cloud; k_lovasz_cloud_mean adds the clouds' losses in a fixed order and divides by B.  The gradient coefficient is divided by B.
+//
+// Clouds of unequal sizes (ln_lovasz_forward_ranges): cloud b owns the rows point_starts[b] .. point_starts[b + 1] of a device list
+// (LnCloudsListed, ln_loss_common.h).  The same kernels instantiated on the list: segment (b, c) at  starts[b] C + c len_b, tiles and
+// strides by the longest cloud, the tiles behind a cloud's last one find no item; a cloud of no rows has G = 0 everywhere and loss 0.
 #include "ln_loss_common.h"
 
 #define LN_LV_THREADS 256
@@ -62,9 +66,13 @@ __device__ __forceinline__ long long ln_lv_item(int b, int j) {
 struct LnLvSegment {
     long long first, len, base, id;
 };
-__device__ __forceinline__ LnLvSegment ln_lv_segment(long long n, long long n0, int C) {
+// CUT, here and in the kernels that walk a segment: how the batch is cut (ln_loss_common.h) — the rows of a full cloud (long long: the
+// instances of ln_lovasz_forward / ln_lovasz_forward_clouds) or LnCloudsListed (ln_lovasz_forward_ranges: `base` = starts[b] C + c len_b,
+// the rows in front of cloud b times C, so the buffers stay n C words whatever the lengths are).  The host picks the instance.
+template <class CUT>
+__device__ __forceinline__ LnLvSegment ln_lv_segment(long long n, CUT cut, int C) {
     LnLvSegment s;
-    const LnCloudRange cloud = ln_cloud_range(n, n0, blockIdx.z);
+    const LnCloudRange cloud = ln_cloud_range(n, cut, blockIdx.z);
     s.first = cloud.first;
     s.len = cloud.len;
     s.base = s.first * C + (long long)blockIdx.y * s.len;
@@ -72,12 +80,13 @@ __device__ __forceinline__ LnLvSegment ln_lv_segment(long long n, long long n0, 
     return s;
 }
 
+template <class CUT>
 __global__ void __launch_bounds__(LN_LV_THREADS)
-    k_lovasz_keys(const float* __restrict__ lp, const long long* __restrict__ target, long long n, long long n0, int C,
+    k_lovasz_keys(const float* __restrict__ lp, const long long* __restrict__ target, long long n, CUT cut, int C,
                   uint32_t* __restrict__ keys, uint32_t* __restrict__ pay) {
     const long long i = (long long)blockIdx.x * LN_LV_THREADS + threadIdx.x;  // inside the cloud
     const int c = blockIdx.y;
-    const LnLvSegment s = ln_lv_segment(n, n0, C);
+    const LnLvSegment s = ln_lv_segment(n, cut, C);
     if (i >= s.len) return;
     const long long t = target[s.first + i];
     const long long tc = t < 0 ? 0 : (t >= C ? C - 1 : t);
@@ -88,11 +97,12 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
 }
 
 // digit histogram of every tile: hist[(segment * 256 + digit) * nblk + b]
+template <class CUT>
 __global__ void __launch_bounds__(LN_LV_THREADS)
-    k_lovasz_hist(const uint32_t* __restrict__ keys, long long n, long long n0, int C, int nblk, int shift, uint32_t* __restrict__ hist) {
+    k_lovasz_hist(const uint32_t* __restrict__ keys, long long n, CUT cut, int C, int nblk, int shift, uint32_t* __restrict__ hist) {
     __shared__ uint32_t s_h[256];
     const int b = blockIdx.x;
-    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const LnLvSegment sg = ln_lv_segment(n, cut, C);
     const long long len = sg.len;
     s_h[threadIdx.x] = 0;
     __syncthreads();
@@ -131,14 +141,15 @@ __global__ void __launch_bounds__(LN_LV_SCAN_THREADS)
 
 // one stable pass: an item goes to  (items of smaller digits) + (items of its digit in earlier tiles)  [both: the scanned hist]
 //                                 + (items of its digit earlier in this tile: earlier waves, earlier rounds, lower lanes)
+template <class CUT>
 __global__ void __launch_bounds__(LN_LV_THREADS)
     k_lovasz_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ pay_in, uint32_t* __restrict__ keys_out,
-                     uint32_t* __restrict__ pay_out, const uint32_t* __restrict__ hist, long long n, long long n0, int C, int nblk,
+                     uint32_t* __restrict__ pay_out, const uint32_t* __restrict__ hist, long long n, CUT cut, int C, int nblk,
                      int shift) {
     __shared__ uint32_t s_cnt[LN_LV_WAVES][256];
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const LnLvSegment sg = ln_lv_segment(n, cut, C);
     const long long seg = sg.base, len = sg.len;
     uint32_t key[LN_LV_IPT], pl[LN_LV_IPT], rank[LN_LV_IPT];
 #pragma unroll
@@ -196,11 +207,12 @@ __global__ void __launch_bounds__(LN_LV_THREADS)
     }
 }
 
+template <class CUT>
 __global__ void __launch_bounds__(LN_LV_THREADS)
-    k_lovasz_fg_count(const uint32_t* __restrict__ pay, long long n, long long n0, int C, int nblk, uint32_t* __restrict__ fgcnt) {
+    k_lovasz_fg_count(const uint32_t* __restrict__ pay, long long n, CUT cut, int C, int nblk, uint32_t* __restrict__ fgcnt) {
     __shared__ int s_w[LN_LV_WAVES];
     const int b = blockIdx.x;
-    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const LnLvSegment sg = ln_lv_segment(n, cut, C);
     const long long len = sg.len;
     const uint32_t* p = pay + sg.base;
     int cnt = 0;
@@ -229,16 +241,17 @@ __device__ __forceinline__ int ln_lv_counting(const int* __restrict__ G, int C, 
     return total;
 }
 
+template <class CUT>
 __global__ void __launch_bounds__(LN_LV_THREADS)
     k_lovasz_dot(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pay, const uint32_t* __restrict__ fgbase,
-                 const int* __restrict__ Gall, const float* __restrict__ lp, long long n, long long n0, int C, int nblk,
+                 const int* __restrict__ Gall, const float* __restrict__ lp, long long n, CUT cut, int C, int nblk,
                  long long ignore_index, int reduction, float clouds, float* __restrict__ partial, float* __restrict__ dl) {
     __shared__ int s_tmp[8];
     __shared__ int s_fg[LN_LV_WAVES];
     __shared__ float s_w[LN_LV_WAVES];
     const int b = blockIdx.x, c = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const LnLvSegment sg = ln_lv_segment(n, n0, C);
+    const LnLvSegment sg = ln_lv_segment(n, cut, C);
     const long long seg = sg.base, len = sg.len;
     const int* G = Gall + (long long)blockIdx.z * C;  // of this cloud's classes
     const int counting = ln_lv_counting(G, C, ignore_index, s_tmp);
@@ -342,15 +355,13 @@ struct LnLovaszLayout {
     size_t keys[2], pay[2], hist, fgcnt, G, partial, cloud, bytes;
 };
 size_t ln_lv_align(size_t x) { return (x + 255) & ~size_t(255); }
-// total: any argument gives a layout (ln_cloud_split)
-LnLovaszLayout ln_lv_layout(long long n, long long points_per_cloud, int classes, bool per_cloud) {
+// N rows in B clouds of at most P rows (nblk tiles each) at C classes
+LnLovaszLayout ln_lv_layout_of(size_t N, size_t P, size_t B, int nblk, size_t C, bool per_cloud) {
     LnLovaszLayout L;
-    const LnCloudSplit split = ln_cloud_split(n, points_per_cloud);
-    const size_t N = n > 0 ? size_t(n) : 0, P = size_t(split.n0), B = size_t(split.clouds);
-    const size_t C = classes > 0 ? size_t(classes) : 0, S = C * B;  // classes, segments
+    const size_t S = C * B;  // segments
     L.n0 = (long long)P;
     L.clouds = (long long)B;
-    L.nblk = int(((N < P ? N : P) + LN_LV_TILE - 1) / LN_LV_TILE);
+    L.nblk = nblk;
     size_t at = 0;
     for (int k = 0; k < 2; ++k) {
         L.keys[k] = at;
@@ -371,9 +382,61 @@ LnLovaszLayout ln_lv_layout(long long n, long long points_per_cloud, int classes
     L.bytes = at + 256;
     return L;
 }
+// total: any argument gives a layout (ln_cloud_split)
+LnLovaszLayout ln_lv_layout(long long n, long long points_per_cloud, int classes, bool per_cloud) {
+    const LnCloudSplit split = ln_cloud_split(n, points_per_cloud);
+    const size_t N = n > 0 ? size_t(n) : 0, P = size_t(split.n0);
+    return ln_lv_layout_of(N, P, size_t(split.clouds), int(((N < P ? N : P) + LN_LV_TILE - 1) / LN_LV_TILE), classes > 0 ? size_t(classes) : 0,
+                           per_cloud);
+}
+// Listed clouds (ln_loss_common.h, LnCloudsListed): tiles and strides by the longest cloud, at least one tile.  Total: n is brought into
+// [0, 2^31], clouds into [1, LN_LV_MAX_CLOUDS], longest into [0, n].
+LnLovaszLayout ln_lv_layout_ranges(long long n, long long clouds, long long longest, int classes) {
+    const long long N = n < 0 ? 0 : (n < (1ll << 31) ? n : 1ll << 31);
+    const long long P = longest < 0 ? 0 : (longest > N ? N : longest);
+    const long long B = clouds < 1 ? 1 : (clouds > LN_LV_MAX_CLOUDS ? LN_LV_MAX_CLOUDS : clouds);
+    const long long nblk = (P + LN_LV_TILE - 1) / LN_LV_TILE;
+    return ln_lv_layout_of(size_t(N), size_t(P), size_t(B), int(nblk < 1 ? 1 : nblk), classes > 0 ? size_t(classes) : 0, true);
+}
 
-// Both entry points: `who` names the caller in messages; per_cloud_form: ln_lovasz_forward_clouds (the other passes
-// points_per_cloud = n, one cloud, and k_lovasz_finish writes the loss itself).
+// The launches of every entry point, its arguments checked and n > 0.  cut: L.n0 (long long), or the list.  mean_form: the per-cloud entries (k_lovasz_finish writes the clouds'
+// losses into the workspace and k_lovasz_cloud_mean the loss; the one-cloud entry lets k_lovasz_finish write the loss itself).
+template <class CUT>
+int ln_lv_launches(const char* who, bool mean_form, CUT cut, const LnLovaszLayout& L, const float* log_probs, const long long* target,
+                   long long n, int classes, long long ignore_index, int reduction, void* workspace, float* loss, float* per_cloud,
+                   float* per_class, float* dloss_dlogp, hipStream_t st) {
+    const int B = int(L.clouds);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(ws + L.keys[0]), reinterpret_cast<uint32_t*>(ws + L.keys[1])};
+    uint32_t* pay[2] = {reinterpret_cast<uint32_t*>(ws + L.pay[0]), reinterpret_cast<uint32_t*>(ws + L.pay[1])};
+    uint32_t* hist = reinterpret_cast<uint32_t*>(ws + L.hist);
+    uint32_t* fgcnt = reinterpret_cast<uint32_t*>(ws + L.fgcnt);
+    int* G = reinterpret_cast<int*>(ws + L.G);
+    float* partial = reinterpret_cast<float*>(ws + L.partial);
+    float* cloud = reinterpret_cast<float*>(ws + L.cloud);
+    const dim3 tiles(L.nblk, classes, B), segments(classes, B), thr(LN_LV_THREADS);
+    const int key_blocks = ln_div_up(L.n0, LN_LV_THREADS);
+    LN_LAUNCH("k_lovasz_keys", k_lovasz_keys<CUT>, dim3(key_blocks < 1 ? 1 : key_blocks, classes, B), thr, 0, st, log_probs, target, n, cut, classes,
+              keys[0], pay[0]);
+    for (int pass = 0; pass < LN_LV_PASSES; ++pass) {
+        const int in = pass & 1, out = in ^ 1, shift = 8 * pass;
+        LN_LAUNCH("k_lovasz_hist", k_lovasz_hist<CUT>, tiles, thr, 0, st, keys[in], n, cut, classes, L.nblk, shift, hist);
+        LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, segments, dim3(LN_LV_SCAN_THREADS), 0, st, hist, 256ll * L.nblk, (int*)nullptr);
+        LN_LAUNCH("k_lovasz_scatter", k_lovasz_scatter<CUT>, tiles, thr, 0, st, keys[in], pay[in], keys[out], pay[out], hist, n, cut, classes, L.nblk, shift);
+    }
+    static_assert(LN_LV_PASSES % 2 == 0, "the sorted order ends in buffer 0");
+    LN_LAUNCH("k_lovasz_fg_count", k_lovasz_fg_count<CUT>, tiles, thr, 0, st, pay[0], n, cut, classes, L.nblk, fgcnt);
+    LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, segments, dim3(LN_LV_SCAN_THREADS), 0, st, fgcnt, (long long)L.nblk, G);
+    LN_LAUNCH("k_lovasz_dot", k_lovasz_dot<CUT>, tiles, thr, 0, st, keys[0], pay[0], fgcnt, G, log_probs, n, cut, classes, L.nblk, ignore_index, reduction,
+              float(B), partial, dloss_dlogp);
+    LN_LAUNCH("k_lovasz_finish", k_lovasz_finish, dim3(B), thr, 0, st, partial, G, L.nblk, classes, ignore_index, reduction,
+              mean_form ? cloud : loss, per_class);
+    if (mean_form) LN_LAUNCH("k_lovasz_cloud_mean", k_lovasz_cloud_mean, dim3(1), thr, 0, st, cloud, (long long)B, loss, per_cloud);
+    return ln_check_launch(who);
+}
+
+// Both equal-size entry points: `who` names the caller in messages; per_cloud_form: ln_lovasz_forward_clouds (the other passes
+// points_per_cloud = n, one cloud).
 int ln_lv_forward(const char* who, bool per_cloud_form, const float* log_probs, const long long* target, long long n,
                   long long points_per_cloud, int classes, long long ignore_index, int reduction, void* workspace, size_t workspace_bytes,
                   float* loss, float* per_cloud, float* per_class, float* dloss_dlogp, hipStream_t st) {
@@ -393,36 +456,8 @@ int ln_lv_forward(const char* who, bool per_cloud_form, const float* log_probs, 
     }
     LN_REQUIRE(log_probs && target && dloss_dlogp, LN_ERR_ARG, "%s: null buffer", who);
     LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "%s: null / small workspace (%zu bytes needed)", who, L.bytes);
-    const long long n0 = L.n0;
-    const int B = int(L.clouds);
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(ws + L.keys[0]), reinterpret_cast<uint32_t*>(ws + L.keys[1])};
-    uint32_t* pay[2] = {reinterpret_cast<uint32_t*>(ws + L.pay[0]), reinterpret_cast<uint32_t*>(ws + L.pay[1])};
-    uint32_t* hist = reinterpret_cast<uint32_t*>(ws + L.hist);
-    uint32_t* fgcnt = reinterpret_cast<uint32_t*>(ws + L.fgcnt);
-    int* G = reinterpret_cast<int*>(ws + L.G);
-    float* partial = reinterpret_cast<float*>(ws + L.partial);
-    float* cloud = reinterpret_cast<float*>(ws + L.cloud);
-    const dim3 tiles(L.nblk, classes, B), segments(classes, B), thr(LN_LV_THREADS);
-    LN_LAUNCH("k_lovasz_keys", k_lovasz_keys, dim3(ln_div_up(n0, LN_LV_THREADS), classes, B), thr, 0, st, log_probs, target, n, n0, classes,
-              keys[0], pay[0]);
-    for (int pass = 0; pass < LN_LV_PASSES; ++pass) {
-        const int in = pass & 1, out = in ^ 1, shift = 8 * pass;
-        LN_LAUNCH("k_lovasz_hist", k_lovasz_hist, tiles, thr, 0, st, keys[in], n, n0, classes, L.nblk, shift, hist);
-        LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, segments, dim3(LN_LV_SCAN_THREADS), 0, st, hist, 256ll * L.nblk, (int*)nullptr);
-        LN_LAUNCH("k_lovasz_scatter", k_lovasz_scatter, tiles, thr, 0, st, keys[in], pay[in], keys[out], pay[out], hist, n, n0, classes, L.nblk,
-                  shift);
-    }
-    static_assert(LN_LV_PASSES % 2 == 0, "the sorted order ends in buffer 0");
-    LN_LAUNCH("k_lovasz_fg_count", k_lovasz_fg_count, tiles, thr, 0, st, pay[0], n, n0, classes, L.nblk, fgcnt);
-    LN_LAUNCH("k_lovasz_scan", k_lovasz_scan, segments, dim3(LN_LV_SCAN_THREADS), 0, st, fgcnt, (long long)L.nblk, G);
-    LN_LAUNCH("k_lovasz_dot", k_lovasz_dot, tiles, thr, 0, st, keys[0], pay[0], fgcnt, G, log_probs, n, n0, classes, L.nblk, ignore_index,
-              reduction, float(B), partial, dloss_dlogp);
-    LN_LAUNCH("k_lovasz_finish", k_lovasz_finish, dim3(B), thr, 0, st, partial, G, L.nblk, classes, ignore_index, reduction,
-              per_cloud_form ? cloud : loss, per_class);
-    if (per_cloud_form)
-        LN_LAUNCH("k_lovasz_cloud_mean", k_lovasz_cloud_mean, dim3(1), thr, 0, st, cloud, (long long)B, loss, per_cloud);
-    return ln_check_launch(who);
+    return ln_lv_launches(who, per_cloud_form, L.n0, L, log_probs, target, n, classes, ignore_index, reduction, workspace, loss,
+                          per_cloud, per_class, dloss_dlogp, st);
 }
 }  // namespace
 
@@ -454,4 +489,34 @@ extern "C" int ln_lovasz_backward(const float* dloss_dlogp, const float* grad_lo
     LN_LAUNCH("k_lovasz_backward", k_lovasz_backward, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, dloss_dlogp, grad_loss,
               n * classes, grad_log_probs);
     return ln_check_launch("ln_lovasz_backward");
+}
+
+// Clouds of unequal sizes: the rows of cloud b from point_starts.  ln_lovasz_backward is the backward.
+extern "C" size_t ln_lovasz_ranges_workspace_bytes(long long n, int clouds, long long longest, int classes) {
+    return ln_lv_layout_ranges(n, clouds, longest, classes).bytes;
+}
+
+extern "C" int ln_lovasz_forward_ranges(const float* log_probs, const long long* target, long long n, const int* point_starts, int clouds,
+                                        long long longest, int classes, long long ignore_index, int reduction, void* workspace,
+                                        size_t workspace_bytes, float* loss, float* per_cloud, float* per_class, float* dloss_dlogp,
+                                        void* stream) {
+    const char* who = "ln_lovasz_forward_ranges";
+    hipStream_t st = (hipStream_t)stream;
+    LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_LV_MAX_CLASSES, LN_ERR_ARG, "%s: bad sizes (n >= 0, 1 <= classes <= %d)", who,
+               LN_LV_MAX_CLASSES);
+    LN_REQUIRE(n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_ARG, "%s: n * classes must stay below 2^31", who);
+    LN_REQUIRE_CLOUD_LIST(who, n, point_starts, clouds, longest, LN_LV_MAX_CLOUDS, LN_ERR_ARG);
+    LN_REQUIRE(reduction == 0 || reduction == 1, LN_ERR_ARG, "%s: reduction is 0 (mean) or 1 (sum)", who);
+    LN_REQUIRE(loss, LN_ERR_ARG, "%s: null buffer", who);
+    if (n == 0) {  // every cloud is empty: each loss is 0, and so are their mean and every per-class row
+        int rc = ln_zero_async(loss, sizeof(float), st);
+        if (rc == LN_OK && per_cloud) rc = ln_zero_async(per_cloud, size_t(clouds) * sizeof(float), st);
+        if (rc == LN_OK && per_class) rc = ln_zero_async(per_class, size_t(clouds) * size_t(classes) * sizeof(float), st);
+        return rc;
+    }
+    const LnLovaszLayout L = ln_lv_layout_ranges(n, clouds, longest, classes);
+    LN_REQUIRE(log_probs && target && dloss_dlogp, LN_ERR_ARG, "%s: null buffer", who);
+    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "%s: null / small workspace (%zu bytes needed)", who, L.bytes);
+    return ln_lv_launches(who, true, LnCloudsListed{point_starts, L.n0}, L, log_probs, target, n, classes, ignore_index, reduction,
+                          workspace, loss, per_cloud, per_class, dloss_dlogp, st);
 }

@@ -5,6 +5,10 @@
 //   ln_nll_forward / ln_nll_backward                 the loss of the training loop: one cloud of all n rows, no weights, no mean over the
 //                                                    clouds — per_cloud and weight_sum are the two words of loss_count.
 //
+//   ln_nll_forward_ranges / ln_nll_backward_ranges   the first pair for clouds of unequal sizes: cloud b owns the rows point_starts[b] ..
+//                                                    point_starts[b + 1] of a device list (LnCloudsListed, ln_loss_common.h); the same
+//                                                    kernels, instantiated on the list, grids and strides by the longest cloud.
+//
 // Cloud b owns rows [b n0, min((b + 1) n0, n)), B = ceil(n / n0).  A label counts when it differs from ignore_index; labels outside
 // [0, C) are clamped and take the weight of the class they clamp to; w = 1 without class weights.  Per cloud
 //     N_b = sum_counted w[y_i] lp[i, y_i],   W_b = sum_counted w[y_i],   D_b = W_b != 0 ? W_b : 1
@@ -74,14 +78,16 @@ __device__ __forceinline__ void ln_nllc_publish(float a, float w, float* __restr
     weight_sum[b] = d;
 }
 
-template <bool WEIGHTED>
+// CUT, in every kernel that walks a cloud: how the batch is cut (ln_loss_common.h) — the rows of a full cloud (int here, long long below:
+// the instances of the equal-size entry points), or LnCloudsListed (the _ranges entry points).  The host picks the instance.
+template <bool WEIGHTED, class CUT>
 __global__ void __launch_bounds__(LN_NLLC_THREADS)
-    k_nll_clouds_wave(const float* __restrict__ lp, const long long* __restrict__ target, long long n, int n0, int C, int B,
+    k_nll_clouds_wave(const float* __restrict__ lp, const long long* __restrict__ target, long long n, CUT cut, int C, int B,
                       long long ignore_index, const float* __restrict__ cw, float* __restrict__ per_cloud, float* __restrict__ weight_sum) {
     const int b = blockIdx.x * (LN_NLLC_THREADS / 64) + (threadIdx.x >> 6);
     if (b >= B) return;  // (the whole wave; the kernel has no barrier)
     const int lane = threadIdx.x & 63;
-    const LnCloudRange cloud = ln_cloud_range(n, n0, b);
+    const LnCloudRange cloud = ln_cloud_range(n, cut, b);
     float acc = 0.f, wsum = 0.f;
     if (lane < cloud.len) ln_nllc_row<WEIGHTED>(lp, target, cloud.first + lane, C, ignore_index, cw, acc, wsum);
     for (int off = 32; off > 0; off >>= 1) {
@@ -91,14 +97,14 @@ __global__ void __launch_bounds__(LN_NLLC_THREADS)
     if (lane == 0) ln_nllc_publish(acc, wsum, per_cloud, weight_sum, b);
 }
 
-template <int MODE>  // bit 0: class weights; bit 1: one block per cloud, per_cloud / weight_sum written here
+template <int MODE, class CUT>  // bit 0: class weights; bit 1: one block per cloud, per_cloud / weight_sum written here
 __global__ void __launch_bounds__(LN_NLLC_THREADS)
-    k_nll_clouds_partials(const float* __restrict__ lp, const long long* __restrict__ target, long long n, long long n0, int C,
+    k_nll_clouds_partials(const float* __restrict__ lp, const long long* __restrict__ target, long long n, CUT cut, int C,
                           long long ignore_index, const float* __restrict__ cw, float* __restrict__ partial, float* __restrict__ per_cloud,
                           float* __restrict__ weight_sum) {
     constexpr bool WEIGHTED = (MODE & 1) != 0, DIRECT = (MODE & 2) != 0;
     __shared__ float s_sum[4], s_cnt[4];
-    const LnCloudRange cloud = ln_cloud_range(n, n0, blockIdx.y);
+    const LnCloudRange cloud = ln_cloud_range(n, cut, blockIdx.y);
     const int blocks = ln_nllc_blocks(cloud.len);
     if ((int)blockIdx.x >= blocks) return;  // (the whole workgroup)
     float acc = 0.f, wsum = 0.f;
@@ -126,14 +132,14 @@ __global__ void __launch_bounds__(LN_NLLC_THREADS)
     }
 }
 
-template <int MODE>  // bit 0: phase 1 (per cloud, from the partials); bit 1: phase 2 (the mean over the clouds)
+template <int MODE, class CUT>  // bit 0: phase 1 (per cloud, from the partials); bit 1: phase 2 (the mean over the clouds)
 __global__ void __launch_bounds__(LN_NLLC_FINISH_THREADS)
-    k_nll_clouds_finish(const float* __restrict__ partial, long long n, long long n0, int B, int grid_blocks, float* __restrict__ per_cloud,
+    k_nll_clouds_finish(const float* __restrict__ partial, long long n, CUT cut, int B, int grid_blocks, float* __restrict__ per_cloud,
                         float* __restrict__ weight_sum, float* __restrict__ loss) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (MODE & 1) {
         for (int b = blockIdx.x * LN_NLLC_FINISH_WAVES + wave; b < B; b += gridDim.x * LN_NLLC_FINISH_WAVES) {
-            const int blocks = ln_nllc_blocks(ln_cloud_range(n, n0, b).len);
+            const int blocks = ln_nllc_blocks(ln_cloud_range(n, cut, b).len);
             const float* p = partial + (long long)b * grid_blocks * 2;
             float x[LN_NLLC_BLOCKS / 64], y[LN_NLLC_BLOCKS / 64];
 #pragma unroll
@@ -189,17 +195,20 @@ static LnDivU31 ln_div_u31(long long d) {
 }
 __device__ __forceinline__ int ln_div(int x, LnDivU31 k) { return int(((unsigned long long)(unsigned)x * k.m) >> k.shift); }
 
-template <bool WEIGHTED>
+// the cloud of a row: row / n0 for equal sizes, the search of the list otherwise (no division by n0 in that form)
+__device__ __forceinline__ int ln_cloud_of_row(int row, LnDivU31 by_n0) { return ln_div(row, by_n0); }
+
+template <bool WEIGHTED, class CLOUD_OF>  // CLOUD_OF: LnDivU31 (by n0) or LnCloudOfRowListed; the host picks
 __global__ void __launch_bounds__(256)
     k_nll_clouds_backward(const long long* __restrict__ target, const float* __restrict__ grad_loss, const float* __restrict__ weight_sum,
-                          int total, LnDivU31 by_n0, LnDivU31 by_C, int C, int B, long long ignore_index, const float* __restrict__ cw,
+                          int total, CLOUD_OF cloud_of, LnDivU31 by_C, int C, int B, long long ignore_index, const float* __restrict__ cw,
                           float* __restrict__ grad_lp) {
     const long long g64 = (long long)blockIdx.x * 256 + threadIdx.x;
     if (g64 >= total) return;
     const int g = int(g64);  // n * C < 2^31
     const int i = ln_div(g, by_C), c = g - i * C;
     const long long t = target[i];
-    const float d = float(B) * weight_sum[ln_div(i, by_n0)];  // (read for every row, beside the label: not a second trip behind it)
+    const float d = float(B) * weight_sum[ln_cloud_of_row(i, cloud_of)];  // (read for every row, beside the label: not a second trip behind it)
     const float gl = -grad_loss[0];
     const long long tc = t < 0 ? 0 : (t >= C ? C - 1 : t);
     float v = 0.f;
@@ -226,6 +235,17 @@ LnNllcLayout ln_nllc_layout(long long n, long long points_per_cloud) {
     L.bytes = 256 + (L.grid_blocks > 1 ? ((size_t(L.clouds) * size_t(L.grid_blocks) * 2 * sizeof(float) + 255) & ~size_t(255)) : 0);
     return L;
 }
+// The layout of a listed batch: grids and the stride of a cloud's partials by the longest cloud.  Total: clouds is brought into
+// [1, LN_NLLC_MAX_CLOUDS], longest into [0, n].
+LnNllcLayout ln_nllc_layout_ranges(long long n, long long clouds, long long longest) {
+    LnNllcLayout L;
+    const long long N = n < 0 ? 0 : (n < (1ll << 31) ? n : 1ll << 31);
+    L.n0 = longest < 0 ? 0 : (longest > N ? N : longest);
+    L.clouds = clouds < 1 ? 1 : (clouds > LN_NLLC_MAX_CLOUDS ? LN_NLLC_MAX_CLOUDS : clouds);
+    L.grid_blocks = ln_nllc_blocks(L.n0);
+    L.bytes = 256 + (L.grid_blocks > 1 ? ((size_t(L.clouds) * size_t(L.grid_blocks) * 2 * sizeof(float) + 255) & ~size_t(255)) : 0);
+    return L;
+}
 int ln_nllc_sizes(const char* who, long long n, long long points_per_cloud, int classes, LnNllcLayout& L) {
     LN_REQUIRE(n >= 0 && classes >= 1, LN_ERR_ARG, "%s: bad sizes (n >= 0, classes >= 1)", who);
     LN_REQUIRE(points_per_cloud >= 1, LN_ERR_ARG, "%s: bad sizes (points_per_cloud >= 1)", who);
@@ -236,24 +256,39 @@ int ln_nllc_sizes(const char* who, long long n, long long points_per_cloud, int 
     return LN_OK;
 }
 
-// Both forward entry points, their arguments checked.  loss == nullptr: the one-cloud entry, which takes no mean over the clouds (phase 2).
+int ln_nllc_sizes_ranges(const char* who, long long n, const int* point_starts, int clouds, long long longest, int classes, LnNllcLayout& L) {
+    LN_REQUIRE(n >= 0 && classes >= 1, LN_ERR_ARG, "%s: bad sizes (n >= 0, classes >= 1)", who);
+    LN_REQUIRE(n < (1ll << 31) && n * classes < (1ll << 31), LN_ERR_UNSUPPORTED, "%s: n * classes must stay below 2^31", who);
+    LN_REQUIRE_CLOUD_LIST(who, n, point_starts, clouds, longest, LN_NLLC_MAX_CLOUDS, LN_ERR_UNSUPPORTED);
+    L = ln_nllc_layout_ranges(n, clouds, longest);
+    return LN_OK;
+}
+
+// what k_nll_clouds_wave takes of a cut: its clouds have at most 64 rows
+int ln_nllc_wave_cut(long long n0) { return int(n0); }
+LnCloudsListed ln_nllc_wave_cut(LnCloudsListed cut) { return cut; }
+
+// Every forward entry point, its arguments checked.  loss == nullptr: the one-cloud entry, which takes no mean over the clouds (phase 2).
+// cut: L.n0 (long long) for the equal-size entries, the list for the _ranges entries (L by ln_nllc_layout_ranges: L.n0 the longest cloud).
+template <class CUT>
 int ln_nllc_forward(const char* who, const float* log_probs, const long long* target, long long n, const LnNllcLayout& L, int classes,
                     long long ignore_index, const float* class_weight, float* partial, float* loss, float* per_cloud, float* weight_sum,
-                    hipStream_t st) {
+                    hipStream_t st, CUT cut) {
+    using WAVE_CUT = decltype(ln_nllc_wave_cut(cut));
     const int B = int(L.clouds);
     const bool direct = L.grid_blocks == 1, mean = loss != nullptr;
     if (L.n0 <= LN_NLLC_WAVE_ROWS) {
         const dim3 grid(ln_div_up(B, LN_NLLC_THREADS / 64)), thr(LN_NLLC_THREADS);
         if (class_weight)
-            LN_LAUNCH("k_nll_clouds_wave", k_nll_clouds_wave<true>, grid, thr, 0, st, log_probs, target, n, int(L.n0), classes, B, ignore_index,
+            LN_LAUNCH("k_nll_clouds_wave", (k_nll_clouds_wave<true, WAVE_CUT>), grid, thr, 0, st, log_probs, target, n, ln_nllc_wave_cut(cut), classes, B, ignore_index,
                       class_weight, per_cloud, weight_sum);
         else
-            LN_LAUNCH("k_nll_clouds_wave", k_nll_clouds_wave<false>, grid, thr, 0, st, log_probs, target, n, int(L.n0), classes, B, ignore_index,
+            LN_LAUNCH("k_nll_clouds_wave", (k_nll_clouds_wave<false, WAVE_CUT>), grid, thr, 0, st, log_probs, target, n, ln_nllc_wave_cut(cut), classes, B, ignore_index,
                       class_weight, per_cloud, weight_sum);
     } else {
         const dim3 grid(L.grid_blocks, (unsigned)B), thr(LN_NLLC_THREADS);
-#define LN_NLLC_PARTIALS(MODE)                                                                                                          \
-    LN_LAUNCH("k_nll_clouds_partials", k_nll_clouds_partials<MODE>, grid, thr, 0, st, log_probs, target, n, L.n0, classes, ignore_index, \
+#define LN_NLLC_PARTIALS(MODE)                                                                                                                 \
+    LN_LAUNCH("k_nll_clouds_partials", (k_nll_clouds_partials<MODE, CUT>), grid, thr, 0, st, log_probs, target, n, cut, classes, ignore_index, \
               class_weight, partial, per_cloud, weight_sum)
         if (direct) {
             if (class_weight) LN_NLLC_PARTIALS(3);
@@ -266,7 +301,7 @@ int ln_nllc_forward(const char* who, const float* log_probs, const long long* ta
     }
     const dim3 fthr(LN_NLLC_FINISH_THREADS);
 #define LN_NLLC_FINISH(MODE, GRID) \
-    LN_LAUNCH("k_nll_clouds_finish", k_nll_clouds_finish<MODE>, dim3(GRID), fthr, 0, st, partial, n, L.n0, B, L.grid_blocks, per_cloud, weight_sum, loss)
+    LN_LAUNCH("k_nll_clouds_finish", (k_nll_clouds_finish<MODE, CUT>), dim3(GRID), fthr, 0, st, partial, n, cut, B, L.grid_blocks, per_cloud, weight_sum, loss)
     if (direct) {
         if (mean) LN_NLLC_FINISH(2, 1);
     } else if (B <= LN_NLLC_FUSED_CLOUDS) {
@@ -280,17 +315,18 @@ int ln_nllc_forward(const char* who, const float* log_probs, const long long* ta
     return ln_check_launch(who);
 }
 
-// Both backward entry points, their arguments checked and n > 0.
+// Every backward entry point, its arguments checked and n > 0.  cloud_of: ln_div_u31(L.n0), or the list.
+template <class CLOUD_OF>
 int ln_nllc_backward(const char* who, const long long* target, const float* grad_loss, const float* weight_sum, long long n,
                      const LnNllcLayout& L, int classes, long long ignore_index, const float* class_weight, float* grad_log_probs,
-                     hipStream_t st) {
+                     hipStream_t st, CLOUD_OF cloud_of) {
     const dim3 grid(ln_div_up(n * classes, 256)), thr(256);
-    const LnDivU31 by_n0 = ln_div_u31(L.n0), by_C = ln_div_u31(classes);  // (1 <= n0 <= n < 2^31, 1 <= classes <= n * classes < 2^31)
+    const LnDivU31 by_C = ln_div_u31(classes);  // (1 <= classes <= n * classes < 2^31)
     if (class_weight)
-        LN_LAUNCH("k_nll_clouds_backward", k_nll_clouds_backward<true>, grid, thr, 0, st, target, grad_loss, weight_sum, int(n * classes), by_n0,
+        LN_LAUNCH("k_nll_clouds_backward", (k_nll_clouds_backward<true, CLOUD_OF>), grid, thr, 0, st, target, grad_loss, weight_sum, int(n * classes), cloud_of,
                   by_C, classes, int(L.clouds), ignore_index, class_weight, grad_log_probs);
     else
-        LN_LAUNCH("k_nll_clouds_backward", k_nll_clouds_backward<false>, grid, thr, 0, st, target, grad_loss, weight_sum, int(n * classes), by_n0,
+        LN_LAUNCH("k_nll_clouds_backward", (k_nll_clouds_backward<false, CLOUD_OF>), grid, thr, 0, st, target, grad_loss, weight_sum, int(n * classes), cloud_of,
                   by_C, classes, int(L.clouds), ignore_index, class_weight, grad_log_probs);
     return ln_check_launch(who);
 }
@@ -310,7 +346,7 @@ extern "C" int ln_nll_forward_clouds(const float* log_probs, const long long* ta
     LN_REQUIRE(log_probs && target && per_cloud && weight_sum, LN_ERR_ARG, "ln_nll_forward_clouds: null buffer");
     LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_nll_forward_clouds: null / small workspace (%zu bytes needed)", L.bytes);
     return ln_nllc_forward("ln_nll_forward_clouds", log_probs, target, n, L, classes, ignore_index, class_weight, static_cast<float*>(workspace),
-                           loss, per_cloud, weight_sum, st);
+                           loss, per_cloud, weight_sum, st, L.n0);
 }
 
 extern "C" int ln_nll_backward_clouds(const long long* target, const float* grad_loss, const float* weight_sum, long long n,
@@ -322,7 +358,37 @@ extern "C" int ln_nll_backward_clouds(const long long* target, const float* grad
     if (n == 0) return LN_OK;
     LN_REQUIRE(target && grad_loss && weight_sum && grad_log_probs, LN_ERR_ARG, "ln_nll_backward_clouds: null buffer");
     return ln_nllc_backward("ln_nll_backward_clouds", target, grad_loss, weight_sum, n, L, classes, ignore_index, class_weight, grad_log_probs,
-                            (hipStream_t)stream);
+                            (hipStream_t)stream, ln_div_u31(L.n0));  // (1 <= n0 <= n < 2^31)
+}
+
+// Clouds of unequal sizes: the rows of cloud b from point_starts (ln_loss_common.h, LnCloudsListed).
+extern "C" size_t ln_nll_ranges_workspace_bytes(long long n, int clouds, long long longest) { return ln_nllc_layout_ranges(n, clouds, longest).bytes; }
+
+extern "C" int ln_nll_forward_ranges(const float* log_probs, const long long* target, long long n, const int* point_starts, int clouds,
+                                     long long longest, int classes, long long ignore_index, const float* class_weight, void* workspace,
+                                     size_t workspace_bytes, float* loss, float* per_cloud, float* weight_sum, void* stream) {
+    LnNllcLayout L;
+    const int rc = ln_nllc_sizes_ranges("ln_nll_forward_ranges", n, point_starts, clouds, longest, classes, L);
+    if (rc != LN_OK) return rc;
+    LN_REQUIRE(loss && per_cloud && weight_sum, LN_ERR_ARG, "ln_nll_forward_ranges: null buffer");
+    LN_REQUIRE(n == 0 || (log_probs && target), LN_ERR_ARG, "ln_nll_forward_ranges: null buffer");
+    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_nll_forward_ranges: null / small workspace (%zu bytes needed)", L.bytes);
+    // (n = 0: every cloud is empty; a wave over a cloud of no rows reads nothing and writes -0 and 1)
+    const LnCloudsListed cut{point_starts, L.n0};
+    return ln_nllc_forward("ln_nll_forward_ranges", log_probs, target, n, L, classes, ignore_index, class_weight, static_cast<float*>(workspace),
+                           loss, per_cloud, weight_sum, (hipStream_t)stream, cut);
+}
+
+extern "C" int ln_nll_backward_ranges(const long long* target, const float* grad_loss, const float* weight_sum, long long n,
+                                      const int* point_starts, int clouds, long long longest, int classes, long long ignore_index,
+                                      const float* class_weight, float* grad_log_probs, void* stream) {
+    LnNllcLayout L;
+    const int rc = ln_nllc_sizes_ranges("ln_nll_backward_ranges", n, point_starts, clouds, longest, classes, L);
+    if (rc != LN_OK) return rc;
+    if (n == 0) return LN_OK;
+    LN_REQUIRE(target && grad_loss && weight_sum && grad_log_probs, LN_ERR_ARG, "ln_nll_backward_ranges: null buffer");
+    return ln_nllc_backward("ln_nll_backward_ranges", target, grad_loss, weight_sum, n, L, classes, ignore_index, class_weight, grad_log_probs,
+                            (hipStream_t)stream, LnCloudOfRowListed{point_starts, clouds});
 }
 
 // The one-cloud, unweighted entry: points_per_cloud = n.  One size serves every n: the partials of one cloud.
@@ -337,7 +403,7 @@ extern "C" int ln_nll_forward(const float* log_probs, const long long* target, l
     LN_REQUIRE(n == 0 || (log_probs && target), LN_ERR_ARG, "ln_nll_forward: null buffer");
     // (n = 0: a wave over a cloud of no rows writes -0 and 1)
     return ln_nllc_forward("ln_nll_forward", log_probs, target, n, L, classes, ignore_index, nullptr, static_cast<float*>(workspace), nullptr,
-                           loss_count, loss_count + 1, (hipStream_t)stream);
+                           loss_count, loss_count + 1, (hipStream_t)stream, L.n0);
 }
 
 extern "C" int ln_nll_backward(const long long* target, const float* grad_loss, const float* loss_count, long long n, int classes,
@@ -348,5 +414,5 @@ extern "C" int ln_nll_backward(const long long* target, const float* grad_loss, 
     if (n == 0) return LN_OK;
     LN_REQUIRE(target && grad_loss && loss_count && grad_log_probs, LN_ERR_ARG, "ln_nll_backward: null buffer");
     return ln_nllc_backward("ln_nll_backward", target, grad_loss, loss_count + 1, n, L, classes, ignore_index, nullptr, grad_log_probs,
-                            (hipStream_t)stream);
+                            (hipStream_t)stream, ln_div_u31(L.n0));  // (1 <= n0 <= n < 2^31)
 }

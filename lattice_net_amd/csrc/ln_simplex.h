@@ -112,24 +112,7 @@ LN_HD void ln_simplex_of_cloud(LnSimplex<D>& s, long long point, int batch_point
     if (batch_points > 0) s.rem0[0] += int(point / batch_points) * batch_key_step;
 }
 
-// Clouds of unequal sizes (LnTableClouds.batch_point_starts): the cloud of point p is upper_bound(starts, p) - 1 over the clouds + 1 ascending
-// ints, i.e. the last c with starts[c] <= p (empty clouds, starts[c] == starts[c + 1], are stepped over).  A binary search that keeps
-// starts[lo] <= p < starts[hi]: ceil(log2(clouds)) dependent loads (6 for 64 clouds, at most 16) of a list of a few cache lines that every
-// wave of the launch reads; points are cloud-major, so all lanes of a wave but those around a boundary walk the same path and a load is
-// one line for the wave.  It only ever reads starts[1 .. clouds - 1] and returns a cloud in [0, clouds): whatever the list holds, nothing
-// is read out of bounds and no key leaves the clouds' bands.
-LN_HD int ln_cloud_of_point(const int* starts, int clouds, int point) {
-    int lo = 0, hi = clouds;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (starts[mid] <= point)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
+// (ln_cloud_of_point, the cloud of a point under LnTableClouds.batch_point_starts, is in ln_common.h: the loss kernels search the same list.)
 // What the kernels get of an LnTableClouds: the list and its length, by value beside the LnTable (whose layout does not change).
 struct LnCloudStarts {
     const int* starts;  // nullptr: no list (no batch, or equal sizes from LnTable.batch_points)

@@ -3,7 +3,9 @@
 ln_nll_forward, torch's nll_loss(weight=) and the torch gather form; `--nll` stops after these lines), Lovasz-Softmax (HIP kernels, and the torch form with
 losses.FUSED_LOVASZ off), soft Dice (HIP kernels, and the torch form with losses.FUSED_DICE off; then per cloud); forward + backward.  Then the same matrix as a batch of 16 clouds x 7 500 points: the per-cloud
 loss (ln_lovasz_forward_clouds against 16 calls of ln_lovasz_forward and against the batched torch form) and the per-cloud IoU
-counts (ln_iou_counts_clouds against Scores.accumulate_scores cloud by cloud)."""
+counts (ln_iou_counts_clouds against Scores.accumulate_scores cloud by cloud).  `--ragged` runs only the C-ABI lines of clouds of unequal
+sizes (the _ranges entry points, which losses.py does not call yet): forward + backward calls alone, no log-softmax, 16 clouds of 5 068 to
+9 825 points against the equal-size entry points at 16 x 7 500 and at one cloud of 120 000."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -74,6 +76,81 @@ def nll_section():
     for (name, _), t in zip(variants, times):
         t.sort()
         print(f"{name} median {t[len(t) // 2]:6.4f} ms, fastest {t[0]:6.4f} ms, slowest {t[-1]:6.4f} ms")
+
+# ---- clouds of unequal sizes through the C ABI: 21 windows of 200 forward + backward calls per variant, taken in turn (a round dropped) ----
+def ragged_section():
+    import random
+    from lattice_net_amd import _lib
+    lib, P = _lib.load(), _lib.ptr
+    lengths = None
+    for seed in range(1000):  # (bounded: a seed whose 16th length fits the range)
+        rng = random.Random(seed)
+        ls = [rng.randint(5068, 9825) for _ in range(15)]
+        if 5068 <= n - sum(ls) <= 9825:
+            lengths = ls + [n - sum(ls)]
+            break
+    if lengths is None:
+        sys.exit("no seed below 1000 gives 16 lengths in 5068 .. 9825 that sum to %d" % n)
+    B, longest = len(lengths), max(lengths)
+    starts = torch.tensor([sum(lengths[:k]) for k in range(B + 1)], dtype=torch.int32, device=dev)
+    print(f"ragged batch: {B} clouds of {min(lengths)} .. {max(lengths)} points, {n} in all")
+    lp = torch.log_softmax(logits.detach(), 1).contiguous()
+    g = torch.ones((1,), device=dev)
+    ws = torch.empty((max(lib.ln_lovasz_ranges_workspace_bytes(n, B, longest, c), lib.ln_lovasz_clouds_workspace_bytes(n, 7500, c),
+                          lib.ln_lovasz_workspace_bytes(n, c)),), dtype=torch.uint8, device=dev)
+    loss, pc, side, coef = (torch.empty((k,), device=dev) for k in (1, B, B * 3 * c, B * 2 * c))
+    dl, grad = torch.empty((n, c), device=dev), torch.empty((n, c), device=dev)
+    sp = _lib.stream_ptr(dev)
+    W, nb = P(ws), ws.numel()
+    def nll(n0):
+        def f():
+            if n0 is None:
+                lib.ln_nll_forward_ranges(P(lp), P(target), n, P(starts), B, longest, c, 0, None, W, nb, P(loss), P(pc), P(side), sp)
+                lib.ln_nll_backward_ranges(P(target), P(g), P(side), n, P(starts), B, longest, c, 0, None, P(grad), sp)
+            else:
+                lib.ln_nll_forward_clouds(P(lp), P(target), n, n0, c, 0, None, W, nb, P(loss), P(pc), P(side), sp)
+                lib.ln_nll_backward_clouds(P(target), P(g), P(side), n, n0, c, 0, None, P(grad), sp)
+        return f
+    def dice(n0):
+        def f():
+            if n0 is None:
+                lib.ln_dice_forward_ranges(P(lp), P(target), n, P(starts), B, longest, c, 0, W, nb, P(loss), None, None, P(coef), sp)
+                lib.ln_dice_backward_ranges(P(lp), P(target), P(coef), P(g), n, P(starts), B, longest, c, P(grad), sp)
+            else:
+                lib.ln_dice_forward(P(lp), P(target), n, n0, c, 0, W, nb, P(loss), None, None, P(coef), sp)
+                lib.ln_dice_backward(P(lp), P(target), P(coef), P(g), n, n0, c, P(grad), sp)
+        return f
+    def lovasz(n0):
+        def f():
+            if n0 is None:
+                lib.ln_lovasz_forward_ranges(P(lp), P(target), n, P(starts), B, longest, c, 0, 0, W, nb, P(loss), None, None, P(dl), sp)
+            else:
+                lib.ln_lovasz_forward_clouds(P(lp), P(target), n, n0, c, 0, 0, W, nb, P(loss), None, None, P(dl), sp)
+            lib.ln_lovasz_backward(P(dl), P(g), n, c, P(grad), sp)
+        return f
+    def window(fn, steps=200):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+    variants = [(f"{name}, {shape}", make(n0)) for name, make in (("nll   ", nll), ("dice  ", dice), ("lovasz", lovasz))
+                for shape, n0 in (("16 x 7500 ", 7500), ("1 x 120000", n), ("16 ragged ", None))]
+    times = [[] for _ in variants]
+    for r in range(22):
+        for k, (_, fn) in enumerate(variants):
+            t = window(fn)
+            if r:
+                times[k].append(t)
+    for (name, _), t in zip(variants, times):
+        t.sort()
+        print(f"{name} median {t[len(t) // 2]:6.4f} ms, fastest {t[0]:6.4f} ms, slowest {t[-1]:6.4f} ms")
+if "--ragged" in sys.argv:  # (only these lines)
+    ragged_section()
+    sys.exit(0)
 nll_section()
 if "--nll" in sys.argv:  # (only the lines above)
     sys.exit(0)
