@@ -475,7 +475,7 @@ int ln_group_norm_backward_rows(const float* x, const float* grad_y, const float
  * ln_cloud_row_starts writes row_starts[clouds + 1] (int32; row_starts[clouds] = min(*t->nr_filled, rows_upper, t->row_limit if
  * set), a cloud without a vertex starts where the next one does) from the first key coordinate of every row, with no host readback,
  * and *order_flag = 1 when some row's cloud is smaller than its predecessor's (the rows are not cloud-major: row_starts is not
- * usable), 0 otherwise.  1 <= clouds <= 64 (LN_ERR_UNSUPPORTED); the clouds must keep within half of t->batch_key_step of the origin.
+ * usable), 0 otherwise.  1 <= clouds <= 64 (LN_ERR_UNSUPPORTED; ln_cloud_row_starts_many: the same call, 1 <= clouds <= 1024); the clouds must keep within half of t->batch_key_step of the origin.
  * ln_group_norm_forward_segments / _backward_segments: ln_group_norm_forward_rows / _backward_rows over `segments` row ranges of one
  * matrix, each normalised with the statistics of its own rows: the same blocking of the rows, counted from the start of the range,
  * the same summation, accumulator slab s for range s.  mean_rstd [segments, 2 * groups], scale_shift [segments, 2 * channels];
@@ -484,8 +484,14 @@ int ln_group_norm_backward_rows(const float* x, const float* grad_y, const float
  * nothing (its mean_rstd / scale_shift rows keep their contents) and adds nothing.  Limits and the next_workspace alternation as for
  * ln_group_norm_forward; 1 <= segments <= 64; workspace = ln_group_norm_segments_workspace_bytes(channels, segments): `segments`
  * accumulator slabs of ln_group_norm_workspace_bytes(channels), then segments x 2 channels doubles the backward call keeps its
- * per-range parameter-gradient terms in. */
+ * per-range parameter-gradient terms in.
+ * ln_group_norm_forward_many_segments / _backward_many_segments: the same calls for 1 <= segments <= 1024.  Up to 64 segments they are
+ * the calls above, launch for launch.  Beyond, a form made for many short ranges: one workgroup owns one range, takes its sums in LDS in
+ * a fixed order (no accumulator slab, no atomic: two runs give the same bits) and writes its rows in the same launch; a long range is
+ * correct and slow, one workgroup walks it.  There ln_group_norm_segments_workspace_bytes(channels, segments) is segments x 2 channels
+ * doubles, the parameter-gradient terms of the backward call, none of which has to be zero on entry. */
 int ln_cloud_row_starts(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream);
+int ln_cloud_row_starts_many(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream);
 size_t ln_group_norm_segments_workspace_bytes(int channels, int segments);
 int ln_group_norm_forward_segments(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps, int relu,
                                    float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes, void* next_workspace,
@@ -494,6 +500,14 @@ int ln_group_norm_backward_segments(const float* x, const float* grad_y, const f
                                     int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma, float* grad_beta, void* workspace,
                                     size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, const int* rows_device,
                                     const int* row_starts, int segments, void* stream);
+int ln_group_norm_forward_many_segments(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
+                                        int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
+                                        void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
+                                        int segments, void* stream);
+int ln_group_norm_backward_many_segments(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
+                                         const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
+                                         float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
+                                         size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream);
 
 /* BatchNorm (+ optional fused ReLU) of BatchNormLatticeModule / BnReluConv (lattice_modules.py:570-583, 988-1009: torch.nn.BatchNorm1d
  * on the [m, channels] values), with the device-side row count of the _rows calls above: n = min(m, *rows_device) rows count (n = m
@@ -564,7 +578,7 @@ int ln_distribute_centre(const float* distributed, const int* splat_idx, const f
                          int width, int pos_dim, float* out, void* stream);
 /* The same for a batch of clouds in one table (LnTable.batch_points), where the reference's "invalid" vertex is the first vertex of
  * EVERY cloud, not row 0 of the table.  row_starts: device int32 [clouds + 1], what ln_cloud_row_starts writes; 1 <= clouds <= 64
- * (LN_ERR_UNSUPPORTED, nothing launched).  Token t belongs to cloud min(t / tokens_per_cloud, clouds - 1), tokens_per_cloud =
+ * (LN_ERR_UNSUPPORTED, nothing launched; ln_distribute_centre_many_clouds / _many_cloud_starts: the same calls, 1 <= clouds <= 1024).  Token t belongs to cloud min(t / tokens_per_cloud, clouds - 1), tokens_per_cloud =
  * LnTable.batch_points x (lattice pos_dim + 1) >= 1; its row is zero when idx[t] < 0 or idx[t] == row_starts[cloud of t], and gets the
  * arithmetic of ln_distribute_centre otherwise.  One cloud with row_starts[0] = 0 is ln_distribute_centre.  No host readback, no
  * allocation: safe inside a stream capture. */
@@ -577,6 +591,12 @@ int ln_distribute_centre_clouds(const float* distributed, const int* splat_idx, 
 int ln_distribute_centre_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
                                       long long tokens, int width, int pos_dim, int tokens_per_point, const int* point_starts,
                                       const int* row_starts, int clouds, float* out, void* stream);
+int ln_distribute_centre_many_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                     long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts, int clouds,
+                                     float* out, void* stream);
+int ln_distribute_centre_many_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                           long long tokens, int width, int pos_dim, int tokens_per_point, const int* point_starts,
+                                           const int* row_starts, int clouds, float* out, void* stream);
 
 /* The vertex-side reduction of PointNetModule (lattice_modules.py:688-712: scatter_max, scatter_add of ones, index_select of the
  * winning tokens' barycentric weights, cat, masked_fill(nr_points < 4), keep mask of vertex 0) over the token adjacency `csr`:
@@ -590,7 +610,9 @@ int ln_pointnet_reduce_forward(const LnCsr* csr, const int* grp_row, long long m
                                float* out, int* out_arg, void* stream);
 /* ln_pointnet_reduce_forward for a batch of clouds in one table: the same segment max, counts, min_points rule and workspace, but the
  * decode step drops the invalid vertex of every cloud instead of row 0.  row_starts: device int32 [clouds + 1] (ln_cloud_row_starts),
- * 1 <= clouds <= 64 (LN_ERR_UNSUPPORTED, nothing launched).  Row r is the invalid vertex of cloud c exactly when r == row_starts[c] and
+ * 1 <= clouds <= 64 (LN_ERR_UNSUPPORTED, nothing launched).  ln_pointnet_reduce_forward_many_clouds: the same call for 1 <= clouds <=
+ * 1024; beyond 64 clouds a second instance of the decode kernel holds up to 1025 starts in LDS and finds the cloud of a row by binary
+ * search.  Row r is the invalid vertex of cloud c exactly when r == row_starts[c] and
  * row_starts[c] < row_starts[c + 1]: a cloud without a vertex has none, row_starts[clouds] is none; a dropped row gets out = 0 and
  * out_arg = -1.  No host readback, no allocation: safe inside a stream capture.
  * ln_pointnet_reduce_backward serves both: it selects by out_arg[idx[t], c] == t, and out_arg is -1 on every dropped row, so the tokens
@@ -599,6 +621,9 @@ int ln_pointnet_reduce_forward(const LnCsr* csr, const int* grp_row, long long m
 int ln_pointnet_reduce_forward_clouds(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
                                       const float* bary, int bary_stride, int rows, int min_points, void* workspace, size_t workspace_bytes,
                                       float* out, int* out_arg, const int* row_starts, int clouds, void* stream);
+int ln_pointnet_reduce_forward_many_clouds(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
+                                           const float* bary, int bary_stride, int rows, int min_points, void* workspace,
+                                           size_t workspace_bytes, float* out, int* out_arg, const int* row_starts, int clouds, void* stream);
 int ln_pointnet_reduce_backward(const float* grad_out, int grad_stride, const int* out_arg, const int* splat_idx, long long tokens,
                                 int channels, float* grad_src, void* stream);
 

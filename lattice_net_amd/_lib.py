@@ -161,10 +161,13 @@ SIGNATURES = {
     "ln_weight_norm_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ln_distribute_centre": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp]),
     "ln_distribute_centre_clouds": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _ll, _vp, _i, _vp, _vp]),
+    "ln_distribute_centre_many_clouds": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _ll, _vp, _i, _vp, _vp]),
     "ln_distribute_centre_cloud_starts": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "ln_distribute_centre_many_cloud_starts": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "ln_pointnet_reduce_workspace_bytes": (_sz, [_i, _i]),
     "ln_pointnet_reduce_forward": (_i, [_CSR, _vp, _ll, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "ln_pointnet_reduce_forward_clouds": (_i, [_CSR, _vp, _ll, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp]),
+    "ln_pointnet_reduce_forward_many_clouds": (_i, [_CSR, _vp, _ll, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp]),
     "ln_pointnet_reduce_backward": (_i, [_vp, _i, _vp, _vp, _ll, _i, _vp, _vp]),
     "ln_linear_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "ln_linear_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -201,9 +204,12 @@ SIGNATURES = {
     "ln_group_norm_forward_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_group_norm_backward_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_cloud_row_starts": (_i, [_T, _i, _i, _vp, _vp, _vp]),
+    "ln_cloud_row_starts_many": (_i, [_T, _i, _i, _vp, _vp, _vp]),
     "ln_group_norm_segments_workspace_bytes": (_sz, [_i, _i]),
     "ln_group_norm_forward_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
+    "ln_group_norm_forward_many_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
     "ln_group_norm_backward_segments": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
+    "ln_group_norm_backward_many_segments": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
     "ln_batch_norm_workspace_bytes": (_sz, [_i]),
     "ln_batch_norm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),

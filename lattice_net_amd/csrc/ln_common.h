@@ -8,7 +8,8 @@
 #define LN_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
 #define LN_EMPTY_TOK 0xFFFFFFFFu
 #define LN_MAX_RETRIEVE_CONFLICTS 300  // HashTableGPU.cuh:494
-#define LN_CLOUDS_MAX 64  // clouds of a batch in one table whose row ranges ln_cloud_row_starts writes (LN_GN_MAX_SEGMENTS of ln_norm.hip)
+#define LN_CLOUDS_MANY_MAX 1024  // clouds of a batch in one table that the *_many per-cloud entry points take (ln_cloud_row_starts_many, ...)
+#define LN_CLOUDS_MAX 64  // ... and the entry points without that suffix; up to here the kernel forms made for a few long clouds; beyond, those for many short ones (LN_GN_MAX_SEGMENTS of ln_norm.hip)
 
 #if defined(__HIPCC__)
 #define LN_HD __host__ __device__ __forceinline__

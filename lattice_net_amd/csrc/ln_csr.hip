@@ -1043,6 +1043,49 @@ __global__ void __launch_bounds__(256)
     out_arg[g] = arg;
 }
 
+// The same step for LN_CLOUDS_MAX < clouds <= LN_CLOUDS_MANY_MAX: the LDS copy holds up to 1025 starts, filled by a strided loop, and
+// every one of the workgroup's <= 256 rows finds its cloud by a binary search in that copy (10 steps in LDS) instead of every cloud
+// marking its row: row r is an invalid vertex when the LAST cloud that starts at or before r starts at r and is not empty (the clouds
+// in front of it that start at r are empty: row_starts ascends).  A list that does not ascend marks other rows, never one outside the
+// workgroup's 256.
+__global__ void __launch_bounds__(256)
+    k_pointnet_reduce_decode_many_clouds(const unsigned long long* __restrict__ packed, const int* __restrict__ counts,
+                                         const float* __restrict__ bary, int bary_stride, long long work, int channels, int min_points,
+                                         const int* __restrict__ row_starts, int clouds, float* __restrict__ out, int* __restrict__ out_arg) {
+    __shared__ int s_start[LN_CLOUDS_MANY_MAX + 1];
+    __shared__ unsigned char s_invalid[256];
+    const long long g0 = (long long)blockIdx.x * 256;
+    const long long row0 = g0 / channels;  // first row of this workgroup; its last one is at most row0 + 255
+    for (int i = threadIdx.x; i <= clouds; i += 256) s_start[i] = row_starts[i];
+    __syncthreads();
+    {
+        const long long r = row0 + threadIdx.x;  // thread i marks row row0 + i
+        int lo = -1, hi = clouds;                // the last cloud c in [0, clouds) with s_start[c] <= r: lo, -1 when there is none
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_start[mid] <= r) lo = mid;
+            else hi = mid;
+        }
+        s_invalid[threadIdx.x] = lo >= 0 && s_start[lo] == r && r < s_start[lo + 1];
+    }
+    __syncthreads();
+    const long long g = g0 + threadIdx.x;
+    if (g >= work) return;
+    const long long row = g / channels;
+    const int c = int(g - row * channels);
+    const unsigned long long p = packed[g];
+    float mx = 0.f, bw = 0.f;
+    int arg = -1;
+    if (p != 0ull && !s_invalid[row - row0] && counts[row] >= min_points) {
+        mx = ln_ordered_to_float((unsigned int)(p >> 32));
+        arg = int(0xFFFFFFFFu - (unsigned int)(p & 0xFFFFFFFFull));
+        bw = bary[(size_t)arg * bary_stride];
+    }
+    out[row * 2 * channels + c] = mx;
+    out[row * 2 * channels + channels + c] = bw;
+    out_arg[g] = arg;
+}
+
 // gradient of the maxima wrt the per-token rows, token-major (every element written: no zero fill, no scatter):
 //   grad_src[t, c] = grad_out[row, c] if arg[row, c] == t else 0,   row = idx[t]
 // A thread owns VEC consecutive channels of one token (VEC = 4: 16-byte loads of the winners' ids and a 16-byte store).
@@ -1101,7 +1144,10 @@ static int ln_pointnet_reduce_run(const char* who, const LnCsr* csr, const int* 
         return ln_check_launch(who);
     if (max_segments > 0)
         ln_launch_segment_max(csr, grp_row, max_segments, src, channels, packed, counts, st);
-    if (row_starts)
+    if (row_starts && clouds > LN_CLOUDS_MAX)
+        LN_LAUNCH("k_pointnet_reduce_decode_many_clouds", k_pointnet_reduce_decode_many_clouds, dim3(ln_div_up(work, 256)), dim3(256), 0, st, packed,
+                  counts, bary, bary_stride, work, channels, min_points, row_starts, clouds, out, out_arg);
+    else if (row_starts)
         LN_LAUNCH("k_pointnet_reduce_decode_clouds", k_pointnet_reduce_decode_clouds, dim3(ln_div_up(work, 256)), dim3(256), 0, st, packed, counts,
                   bary, bary_stride, work, channels, min_points, row_starts, clouds, out, out_arg);
     else
@@ -1125,6 +1171,18 @@ extern "C" int ln_pointnet_reduce_forward_clouds(const LnCsr* csr, const int* gr
                LN_CLOUDS_MAX, clouds);
     LN_REQUIRE(row_starts, LN_ERR_ARG, "ln_pointnet_reduce_forward_clouds: null row_starts");
     return ln_pointnet_reduce_run("ln_pointnet_reduce_forward_clouds", csr, grp_row, max_segments, src, channels, bary, bary_stride, rows,
+                                  min_points, workspace, workspace_bytes, row_starts, clouds, out, out_arg, (hipStream_t)stream);
+}
+
+// up to LN_CLOUDS_MANY_MAX clouds; beyond LN_CLOUDS_MAX the decode step is k_pointnet_reduce_decode_many_clouds, up to there the call above
+extern "C" int ln_pointnet_reduce_forward_many_clouds(const LnCsr* csr, const int* grp_row, long long max_segments, const float* src, int channels,
+                                                      const float* bary, int bary_stride, int rows, int min_points, void* workspace,
+                                                      size_t workspace_bytes, float* out, int* out_arg, const int* row_starts, int clouds,
+                                                      void* stream) {
+    LN_REQUIRE(clouds >= 1 && clouds <= LN_CLOUDS_MANY_MAX, LN_ERR_UNSUPPORTED, "ln_pointnet_reduce_forward_many_clouds: 1 <= clouds <= %d (got %d)",
+               LN_CLOUDS_MANY_MAX, clouds);
+    LN_REQUIRE(row_starts, LN_ERR_ARG, "ln_pointnet_reduce_forward_many_clouds: null row_starts");
+    return ln_pointnet_reduce_run("ln_pointnet_reduce_forward_many_clouds", csr, grp_row, max_segments, src, channels, bary, bary_stride, rows,
                                   min_points, workspace, workspace_bytes, row_starts, clouds, out, out_arg, (hipStream_t)stream);
 }
 

@@ -157,7 +157,7 @@ extern "C" int ln_distribute_centre(const float* distributed, const int* splat_i
 // The same pass for a batch of clouds in one table (LnTable.batch_points): the "invalid" vertex of the reference is the first vertex of
 // EVERY cloud, row_starts[cloud] (ln_cloud_row_starts), not row 0 of the table.  Token t belongs to cloud min(t / tokens_per_cloud,
 // clouds - 1).  row_starts[cloud] is addressed from t alone, so its load is in flight beside idx[t] (a wave reads one or two of the at
-// most 64 ints: one cache line).  IDX: int when every element index fits 31 bits (32-bit divisions), else long long.
+// most 1025 ints: one cache line).  IDX: int when every element index fits 31 bits (32-bit divisions), else long long.
 // (Measured and dropped: row_starts in LDS behind a barrier, and cloud / boundary / first rows computed once per workgroup — both slower.)
 template <typename IDX>
 __global__ void __launch_bounds__(256)
@@ -180,15 +180,15 @@ __global__ void __launch_bounds__(256)
     out[i64] = x;
 }
 
-extern "C" int ln_distribute_centre_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
-                                           long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts,
-                                           int clouds, float* out, void* stream) {
+static int ln_distribute_centre_clouds_run(const char* who, int max_clouds, const float* distributed, const int* splat_idx, const float* position_sums,
+                                           const int* counts, long long tokens, int width, int pos_dim, long long tokens_per_cloud,
+                                           const int* row_starts, int clouds, float* out, void* stream) {
     LN_REQUIRE(tokens >= 0 && width >= 1 && pos_dim >= 0 && pos_dim <= width && tokens_per_cloud >= 1, LN_ERR_ARG,
-               "ln_distribute_centre_clouds: bad sizes");
-    LN_REQUIRE(clouds >= 1 && clouds <= LN_CLOUDS_MAX, LN_ERR_UNSUPPORTED, "ln_distribute_centre_clouds: 1 <= clouds <= %d (got %d)",
-               LN_CLOUDS_MAX, clouds);
+               "%s: bad sizes", who);
+    LN_REQUIRE(clouds >= 1 && clouds <= max_clouds, LN_ERR_UNSUPPORTED, "%s: 1 <= clouds <= %d (got %d)", who, max_clouds,
+               clouds);
     if (tokens == 0) return LN_OK;
-    LN_REQUIRE(distributed && splat_idx && position_sums && counts && row_starts && out, LN_ERR_ARG, "ln_distribute_centre_clouds: null buffer");
+    LN_REQUIRE(distributed && splat_idx && position_sums && counts && row_starts && out, LN_ERR_ARG, "%s: null buffer", who);
     const dim3 grid(ln_div_up(tokens * width, 256));
     if (tokens * width <= 0x7fffffffll && tokens_per_cloud <= 0x7fffffffll)
         LN_LAUNCH("k_distribute_centre_clouds", k_distribute_centre_clouds<int>, grid, dim3(256), 0, (hipStream_t)stream, distributed, splat_idx,
@@ -196,7 +196,22 @@ extern "C" int ln_distribute_centre_clouds(const float* distributed, const int* 
     else
         LN_LAUNCH("k_distribute_centre_clouds", k_distribute_centre_clouds<long long>, grid, dim3(256), 0, (hipStream_t)stream, distributed,
                   splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_cloud, row_starts, clouds, out);
-    return ln_check_launch("ln_distribute_centre_clouds");
+    return ln_check_launch(who);
+}
+
+// (the kernel reads the starts from global memory, any number of them: the two entry points differ in the limit they check)
+extern "C" int ln_distribute_centre_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                           long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts,
+                                           int clouds, float* out, void* stream) {
+    return ln_distribute_centre_clouds_run("ln_distribute_centre_clouds", LN_CLOUDS_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_cloud,
+                                           row_starts, clouds, out, stream);
+}
+
+extern "C" int ln_distribute_centre_many_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                                long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts,
+                                                int clouds, float* out, void* stream) {
+    return ln_distribute_centre_clouds_run("ln_distribute_centre_many_clouds", LN_CLOUDS_MANY_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim,
+                                           tokens_per_cloud, row_starts, clouds, out, stream);
 }
 
 // Clouds of unequal sizes (LnTableClouds.batch_point_starts): the cloud of token t is that of its point t / tokens_per_point, found by the
@@ -222,18 +237,18 @@ __global__ void __launch_bounds__(256)
     out[i64] = x;
 }
 
-extern "C" int ln_distribute_centre_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
-                                                 long long tokens, int width, int pos_dim, int tokens_per_point, const int* point_starts,
-                                                 const int* row_starts, int clouds, float* out, void* stream) {
+static int ln_distribute_centre_cloud_starts_run(const char* who, int max_clouds, const float* distributed, const int* splat_idx, const float* position_sums,
+                                                 const int* counts, long long tokens, int width, int pos_dim, int tokens_per_point,
+                                                 const int* point_starts, const int* row_starts, int clouds, float* out, void* stream) {
     LN_REQUIRE(tokens >= 0 && width >= 1 && pos_dim >= 0 && pos_dim <= width && tokens_per_point >= 1, LN_ERR_ARG,
-               "ln_distribute_centre_cloud_starts: bad sizes");
-    LN_REQUIRE(tokens / tokens_per_point <= 0x7fffffffll, LN_ERR_ARG, "ln_distribute_centre_cloud_starts: more than 2^31 points");
-    LN_REQUIRE(clouds >= 1 && clouds <= LN_CLOUDS_MAX, LN_ERR_UNSUPPORTED, "ln_distribute_centre_cloud_starts: 1 <= clouds <= %d (got %d)",
-               LN_CLOUDS_MAX, clouds);
-    LN_REQUIRE(point_starts != nullptr, LN_ERR_ARG, "ln_distribute_centre_cloud_starts: null point_starts");
+               "%s: bad sizes", who);
+    LN_REQUIRE(tokens / tokens_per_point <= 0x7fffffffll, LN_ERR_ARG, "%s: more than 2^31 points", who);
+    LN_REQUIRE(clouds >= 1 && clouds <= max_clouds, LN_ERR_UNSUPPORTED, "%s: 1 <= clouds <= %d (got %d)", who,
+               max_clouds, clouds);
+    LN_REQUIRE(point_starts != nullptr, LN_ERR_ARG, "%s: null point_starts", who);
     if (tokens == 0) return LN_OK;
     LN_REQUIRE(distributed && splat_idx && position_sums && counts && row_starts && out, LN_ERR_ARG,
-               "ln_distribute_centre_cloud_starts: null buffer");
+               "%s: null buffer", who);
     const dim3 grid(ln_div_up(tokens * width, 256));
     if (tokens * width <= 0x7fffffffll)
         LN_LAUNCH("k_distribute_centre_cloud_starts", k_distribute_centre_cloud_starts<int>, grid, dim3(256), 0, (hipStream_t)stream, distributed,
@@ -241,5 +256,19 @@ extern "C" int ln_distribute_centre_cloud_starts(const float* distributed, const
     else
         LN_LAUNCH("k_distribute_centre_cloud_starts", k_distribute_centre_cloud_starts<long long>, grid, dim3(256), 0, (hipStream_t)stream,
                   distributed, splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_point, point_starts, row_starts, clouds, out);
-    return ln_check_launch("ln_distribute_centre_cloud_starts");
+    return ln_check_launch(who);
+}
+
+extern "C" int ln_distribute_centre_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
+                                                 long long tokens, int width, int pos_dim, int tokens_per_point, const int* point_starts,
+                                                 const int* row_starts, int clouds, float* out, void* stream) {
+    return ln_distribute_centre_cloud_starts_run("ln_distribute_centre_cloud_starts", LN_CLOUDS_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim,
+                                                 tokens_per_point, point_starts, row_starts, clouds, out, stream);
+}
+
+extern "C" int ln_distribute_centre_many_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums,
+                                                      const int* counts, long long tokens, int width, int pos_dim, int tokens_per_point,
+                                                      const int* point_starts, const int* row_starts, int clouds, float* out, void* stream) {
+    return ln_distribute_centre_cloud_starts_run("ln_distribute_centre_many_cloud_starts", LN_CLOUDS_MANY_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim,
+                                                 tokens_per_point, point_starts, row_starts, clouds, out, stream);
 }

@@ -1,14 +1,15 @@
 // GroupNorm and BatchNorm (+ fused ReLU) on the native [M, C] lattice-value layout, forward and backward, in three forms: GroupNorm over
 // the whole matrix, BatchNorm (GroupNorm with one channel per group, plus running statistics) and GroupNorm per row range (the clouds of
-// a batch).  The reference runs torch.nn.GroupNorm on a transposed [1, C, M] view (lattice_modules.py:585-616), two transposed copies in
+// a batch; beyond 64 ranges one workgroup owns one range: k_gn_forward_range_owner, below).  The reference runs torch.nn.GroupNorm on a transposed [1, C, M] view (lattice_modules.py:585-616), two transposed copies in
 // each direction; the LNN blocks apply it before every operator, so it sits between any two lattice kernels of the U-Net.
 //   statistics : per-channel partial sums over a slab of rows per workgroup (lanes run along the channels of a row: coalesced),
 //                combined across workgroups with one fp64 atomic per (workgroup, channel) into LN_GN_REPLICAS accumulator copies
 //   apply      : every workgroup rebuilds the per-channel scale/shift from the C channel sums in LDS, then one float4 pass over its rows
 // Backward uses the same two shapes: per-channel sums of gy*x and gy, then dx = gy*gamma*rstd + x*c2[g] + c3[g].
 // Every step has ONE device body, and a kernel is a shell that resolves its rows and its slabs and calls them: ln_gn_stats_rows (the
-// sums), ln_gn_replica_sums, ln_gn_channel_affine, ln_gn_affine_rows (y), ln_gn_masked (the ReLU mask), ln_gn_backward_rows (c2 / c3 and
-// dx), ln_gn_live_rows / ln_gn_zero_next / ln_gn_zero_tail (the prologue).  A change to a formula is made in one place for every form.
+// sums; ln_gn_thread_sums is the part of one thread, ln_gn_range_sums the sums of a range by one workgroup), ln_gn_replica_sums,
+// ln_gn_channel_affine (ln_gn_affine_of_sums behind the replica loads), ln_gn_affine_rows (y), ln_gn_masked (the ReLU mask), ln_gn_backward_rows (c2 / c3 and
+// dx; ln_gn_backward_of_sums behind the replica loads), ln_gn_live_rows / ln_gn_zero_next / ln_gn_zero_tail (the prologue).  A change to a formula is made in one place for every form.
 // Every fp32 sum that involves x is a sum of x - p over the LN_GN_PASSES rows of ONE thread, with the pivot p the first of these
 // rows: sum (x-p)^2 and sum gy*(x-p) have the size of the spread of those rows, not of their offset from zero, and a pivot that is an
 // outlier spoils 16 rows' worth of a sum it is itself a term of, never the whole statistic.  Each thread then puts its pivot back in
@@ -20,7 +21,9 @@
 #define LN_GN_PASSES 16
 #define LN_GN_REPLICAS 32  // accumulator copies: memory-side atomics serialise per cache line, so spread the workgroups
 #define LN_BN_SUM_BATCH 8  // replica loads in flight in the BatchNorm kernels (ln_gn_replica_sums)
-#define LN_GN_MAX_SEGMENTS 64  // row ranges of one call (the clouds of a batch: Lattice.set_cloud_batch)
+#define LN_GN_MAX_SEGMENTS LN_CLOUDS_MAX  // row ranges of one call in the slab form: a 2-D grid and an accumulator slab per range
+#define LN_GN_MANY_MAX_SEGMENTS LN_CLOUDS_MANY_MAX  // row ranges of one call (the clouds of a batch: Lattice.set_cloud_batch); beyond
+                                                    // LN_GN_MAX_SEGMENTS the range-owner form, one workgroup per range
 
 // The rows that count, 0 <= live <= m (static-rows mode: the tensors are taller than the lattice, *rows_dev rows of them are its rows;
 // the rows behind them are excluded from the statistics and written as zeros).  With no live row the forms differ, on purpose: the
@@ -53,24 +56,23 @@ __device__ __forceinline__ void ln_gn_masked_grad(float4& g, const float4& xv, c
     g.w = ln_gn_masked(g.w, xv.w, s_a[col + 3], s_b[col + 3]);
 }
 
-// acc[c*2 + 0] += sum_rows p(row, c), acc[c*2 + 1] += sum_rows q(row, c)
+// The two sums of ONE thread over its LN_GN_PASSES rows of the slab of rows_per_pass * LN_GN_PASSES rows that starts at row r0, pivot put
+// back: pd[j] = sum_rows p(row, 4 qi + j), qd[j] = sum_rows q(row, 4 qi + j)
 //   forward  (gy == nullptr): p = x,  q = x*x
 //   backward               : p = gy' * x, q = gy'   with gy' = gy masked by (x*a[c] + b[c] > 0) when relu
 // A thread owns one float4 (4 channels) of a row; 256 / (c/4) rows are read per pass and LN_GN_PASSES independent
-// passes are in flight per thread.  The rows are [row_begin, m); workgroup `block` takes the slab of rows_per_pass * LN_GN_PASSES rows
-// that starts that many * block rows behind row_begin (k_gn_stats: the whole matrix; k_gn_stats_segments: one row range of it).
-__device__ __forceinline__ void ln_gn_stats_rows(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift,
-                                                 int relu, int row_begin, int m, int c, double* __restrict__ acc, int block) {
-    __shared__ double s_p[256][4], s_q[256][4];
+// passes are in flight per thread.  Rows from m on count nowhere; a thread with rp >= rows_per_pass has no row (zeros).
+__device__ __forceinline__ void ln_gn_thread_sums(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift,
+                                                  int relu, long long r0, int m, int c, double (&pd)[4], double (&qd)[4]) {
     const int tid = threadIdx.x;
     const int quads = c >> 2;                 // c % 4 == 0, c <= 1024  ->  quads <= 256
     const int rows_per_pass = 256 / quads;
     const int rp = tid / quads;
     const int qi = tid - rp * quads;
     const bool live = rp < rows_per_pass;
-    const long long r0 = row_begin + (long long)block * rows_per_pass * LN_GN_PASSES;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), q = p;
-    double pd[4] = {0.0, 0.0, 0.0, 0.0}, qd[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pd[j] = qd[j] = 0.0;
     if (live) {
         float4 a = p, b = p;
         // pivots: this thread's first row (with no row of its own all its terms are zero)
@@ -116,6 +118,22 @@ __device__ __forceinline__ void ln_gn_stats_rows(const float* __restrict__ x, co
             qd[j] = gy ? s2 : s2 + 2.0 * pj * s1 + n * pj * pj;
         }
     }
+}
+
+// acc[c*2 + 0] += sum_rows p(row, c), acc[c*2 + 1] += sum_rows q(row, c), p and q those of ln_gn_thread_sums.  The rows are
+// [row_begin, m); workgroup `block` takes the slab of rows_per_pass * LN_GN_PASSES rows that starts that many * block rows behind
+// row_begin (k_gn_stats: the whole matrix; k_gn_stats_segments: one row range of it).
+__device__ __forceinline__ void ln_gn_stats_rows(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift,
+                                                 int relu, int row_begin, int m, int c, double* __restrict__ acc, int block) {
+    __shared__ double s_p[256][4], s_q[256][4];
+    const int tid = threadIdx.x;
+    const int quads = c >> 2;
+    const int rows_per_pass = 256 / quads;
+    const int rp = tid / quads;
+    const int qi = tid - rp * quads;
+    const bool live = rp < rows_per_pass;
+    double pd[4], qd[4];
+    ln_gn_thread_sums(x, gy, scale_shift, relu, row_begin + (long long)block * rows_per_pass * LN_GN_PASSES, m, c, pd, qd);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         s_p[tid][j] = pd[j];
@@ -136,6 +154,54 @@ __device__ __forceinline__ void ln_gn_stats_rows(const float* __restrict__ x, co
             atomicAdd(dst + 2 * j + 1, qd[j]);
         }
     }
+}
+
+// The same sums over the rows [lo, hi) taken by ONE workgroup, left in LDS: s_sum[col] = sum p, s_sq[col] = sum q (the range-owner
+// kernels: many short ranges, no accumulator slab and no atomic).  The slabs are those of ln_gn_stats_rows, blocked from lo, so every
+// fp32 rounding is the one of the other forms; a thread adds its slabs in fp64 in row order, then the threads of a channel quad are
+// folded in thread order: one fixed order, the same bits on every run.  All 256 threads call it; it ends with a barrier.
+__device__ __forceinline__ void ln_gn_range_sums(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift,
+                                                 int relu, int lo, int hi, int c, double* s_sum, double* s_sq) {
+    __shared__ double s_p[256][4], s_q[256][4];
+    const int tid = threadIdx.x;
+    const int quads = c >> 2;
+    const int rows_per_pass = 256 / quads;
+    const int rp = tid / quads;
+    const int qi = tid - rp * quads;
+    double pd[4] = {0.0, 0.0, 0.0, 0.0}, qd[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (long long r0 = lo; r0 < hi; r0 += rows_per_pass * LN_GN_PASSES) {  // (one trip for a range of up to 16 passes; a long range loops)
+        long long slab = r0;
+        asm volatile("" : "+s"(slab));  // (opaque: the 32 row addresses are formed per trip as in k_gn_stats, not carried round the loop in 64 VGPRs:
+                                        // 276 -> 184 VGPRs in the backward kernel with AMD clang 22.0.0git of ROCm 7.2.0; drop it if a later compiler no longer needs it)
+        double p1[4], q1[4];
+        ln_gn_thread_sums(x, gy, scale_shift, relu, slab, hi, c, p1, q1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            pd[j] += p1[j];
+            qd[j] += q1[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s_p[tid][j] = pd[j];
+        s_q[tid][j] = qd[j];
+    }
+    __syncthreads();
+    if (rp == 0) {
+        for (int r = 1; r < rows_per_pass; ++r)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                pd[j] += s_p[r * quads + qi][j];
+                qd[j] += s_q[r * quads + qi][j];
+            }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            s_sum[4 * qi + j] = pd[j];
+            s_sq[4 * qi + j] = qd[j];
+        }
+    }
+    __syncthreads();
 }
 
 // The two fp64 sums of channel `col` over the accumulator replicas, added in replica order, BATCH loads of each in flight at a time.  The
@@ -161,21 +227,13 @@ __device__ __forceinline__ void ln_gn_replica_sums(const double* __restrict__ ac
     }
 }
 
-// per-channel scale a[c] = gamma*rstd[g], shift b[c] = beta - mean[g]*a[c] from the channel sums over m rows; block 0 also
-// publishes mean/rstd per group and scale/shift per channel for the backward pass
-__device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ acc, const float* __restrict__ gamma,
+// per-channel scale a[c] = gamma*rstd[g], shift b[c] = beta - mean[g]*a[c] from the channel sums over m rows in LDS (s_sum, s_sq: complete
+// behind a barrier); block 0 also publishes mean/rstd per group and scale/shift per channel for the backward pass
+__device__ __forceinline__ void ln_gn_affine_of_sums(const double* s_sum, const double* s_sq, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, int m, int c, int groups, float eps, float* s_a,
                                                      float* s_b, float* __restrict__ mean_rstd, float* __restrict__ scale_shift) {
     if (m < 1) m = 1;  // (an empty lattice under a static row bound: all sums are zero)
     const int cg = c / groups;
-    __shared__ double s_sum[LN_GN_MAX_C], s_sq[LN_GN_MAX_C];
-    for (int col = threadIdx.x; col < c; col += 256) {
-        double a0, a1;
-        ln_gn_replica_sums<LN_GN_REPLICAS>(acc, c, col, a0, a1);
-        s_sum[col] = a0;
-        s_sq[col] = a1;
-    }
-    __syncthreads();
     for (int col = threadIdx.x; col < c; col += 256) {
         const int g = col / cg;
         double s = 0.0, ss = 0.0;
@@ -203,6 +261,21 @@ __device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ 
     }
 }
 
+// ln_gn_affine_of_sums on the channel sums of the accumulator replicas
+__device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ acc, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, int m, int c, int groups, float eps, float* s_a,
+                                                     float* s_b, float* __restrict__ mean_rstd, float* __restrict__ scale_shift) {
+    __shared__ double s_sum[LN_GN_MAX_C], s_sq[LN_GN_MAX_C];
+    for (int col = threadIdx.x; col < c; col += 256) {
+        double a0, a1;
+        ln_gn_replica_sums<LN_GN_REPLICAS>(acc, c, col, a0, a1);
+        s_sum[col] = a0;
+        s_sq[col] = a1;
+    }
+    __syncthreads();
+    ln_gn_affine_of_sums(s_sum, s_sq, gamma, beta, m, c, groups, eps, s_a, s_b, mean_rstd, scale_shift);
+}
+
 // y = act(x * a[c] + b[c]) over the float4 [first4, last4) of the matrix, the workgroups of blockIdx.y side by side
 __device__ __forceinline__ void ln_gn_affine_rows(const float* __restrict__ x, const float* s_a, const float* s_b, long long first4, long long last4,
                                                   int c, int relu, float* __restrict__ y) {
@@ -224,24 +297,16 @@ __device__ __forceinline__ void ln_gn_affine_rows(const float* __restrict__ x, c
     }
 }
 
-// dx = gy' * gamma * rstd + x * c2[g] + c3[g] over the float4 [first4, last4) of the matrix, from the channel sums of ln_gn_stats_rows
-// over `count` rows (acc, mean_rstd, scale_shift: those of the rows in question).  The first workgroup of the rows also leaves the terms
+// dx = gy' * gamma * rstd + x * c2[g] + c3[g] over the float4 [first4, last4) of the matrix, from the channel sums of ln_gn_stats_rows /
+// ln_gn_range_sums over `count` rows in LDS (s_ds, s_db: complete behind a barrier; mean_rstd, scale_shift: those of the rows in question).  The first workgroup of the rows also leaves the terms
 // of the parameter gradients in LDS, in fp64: term_gamma[col] = (ds - db*mean)*rstd, term_beta[col] = db, each written by the thread that
 // owns `col` in a loop `col = threadIdx.x; col < c; col += 256` (which may read them back without a barrier).
-__device__ __forceinline__ void ln_gn_backward_rows(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
-                                                    const float* __restrict__ gamma, const float* __restrict__ mean_rstd,
-                                                    const float* __restrict__ scale_shift, int count, long long first4, long long last4, int c,
-                                                    int groups, int relu, float* __restrict__ dx, double*& term_gamma, double*& term_beta) {
+__device__ __forceinline__ void ln_gn_backward_of_sums(const float* __restrict__ x, const float* __restrict__ gy, double* s_ds, double* s_db,
+                                                       const float* __restrict__ gamma, const float* __restrict__ mean_rstd,
+                                                       const float* __restrict__ scale_shift, int count, long long first4, long long last4, int c,
+                                                       int groups, int relu, float* __restrict__ dx, double*& term_gamma, double*& term_beta) {
     __shared__ float s_gr[LN_GN_MAX_C], s_c2[LN_GN_MAX_C], s_c3[LN_GN_MAX_C], s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
-    __shared__ double s_ds[LN_GN_MAX_C], s_db[LN_GN_MAX_C];
     const int cg = c / groups;
-    for (int col = threadIdx.x; col < c; col += 256) {
-        double ds, db;
-        ln_gn_replica_sums<LN_GN_REPLICAS>(acc, c, col, ds, db);
-        s_ds[col] = ds;
-        s_db[col] = db;
-    }
-    __syncthreads();
     for (int col = threadIdx.x; col < c; col += 256) {
         const int g = col / cg;
         const float mean = mean_rstd[g], rstd = mean_rstd[groups + g];
@@ -282,6 +347,22 @@ __device__ __forceinline__ void ln_gn_backward_rows(const float* __restrict__ x,
         o.w = g.w * s_gr[col + 3] + xv.w * s_c2[col + 3] + s_c3[col + 3];
         reinterpret_cast<float4*>(dx)[i] = o;
     }
+}
+
+// ln_gn_backward_of_sums on the channel sums of the accumulator replicas
+__device__ __forceinline__ void ln_gn_backward_rows(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
+                                                    const float* __restrict__ gamma, const float* __restrict__ mean_rstd,
+                                                    const float* __restrict__ scale_shift, int count, long long first4, long long last4, int c,
+                                                    int groups, int relu, float* __restrict__ dx, double*& term_gamma, double*& term_beta) {
+    __shared__ double s_ds[LN_GN_MAX_C], s_db[LN_GN_MAX_C];
+    for (int col = threadIdx.x; col < c; col += 256) {
+        double ds, db;
+        ln_gn_replica_sums<LN_GN_REPLICAS>(acc, c, col, ds, db);
+        s_ds[col] = ds;
+        s_db[col] = db;
+    }
+    __syncthreads();
+    ln_gn_backward_of_sums(x, gy, s_ds, s_db, gamma, mean_rstd, scale_shift, count, first4, last4, c, groups, relu, dx, term_gamma, term_beta);
 }
 
 __global__ void __launch_bounds__(256)
@@ -548,6 +629,63 @@ __global__ void __launch_bounds__(256)
     if (out) out[i < c ? i : i - c] = (float)sum;
 }
 
+// ---- GroupNorm per row range, many short ranges (LN_GN_MAX_SEGMENTS < B <= LN_GN_MANY_MAX_SEGMENTS): one workgroup owns one range ----
+// A grid sized for the whole matrix once per range, and an accumulator slab per range that has to be zero, are what the kernels above
+// cost per range; at 1024 ranges of a few dozen rows that is a thousand times the useful workgroups and 32 MB of zero fill per call.
+// Here the grid is (1, B): workgroup blockIdx.y takes the sums of its range alone (ln_gn_range_sums: LDS, fixed order, no slab, no
+// atomic), and behind a barrier walks the range a second time (from L2: a range of 40 rows x 64 channels is 10 KB) to write y, or dx.
+// The grid is (1, B) and not (B, 1) because the shared bodies stride their rows by gridDim.x and publish from blockIdx.x == 0: with one
+// workgroup in x they are the owner's loop as they stand, and ln_gn_zero_next gives every owner a share of the next call's accumulators.
+// A range of any length is correct, the owner loops over it, but it is walked by ONE workgroup of the chip's 256 CUs: a 100 000-row
+// range among 200 short ones takes as long as that range alone on one CU.  The host takes this form only beyond LN_GN_MAX_SEGMENTS
+// ranges, where the ranges of a batch that fits one table are short.
+__global__ void __launch_bounds__(256)
+    k_gn_forward_range_owner(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, int m, int c, int groups,
+                             float eps, int relu, float* __restrict__ y, float* __restrict__ mean_rstd, float* __restrict__ scale_shift,
+                             double* __restrict__ zero_next, int zero_count, const int* __restrict__ rows_dev,
+                             const int* __restrict__ row_starts, int segments) {
+    __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
+    __shared__ double s_sum[LN_GN_MAX_C], s_sq[LN_GN_MAX_C];
+    const int s = blockIdx.y;
+    int live, lo, hi;
+    ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
+    ln_gn_segments_housekeeping(zero_next, zero_count, live, m, c, y);
+    if (hi == lo) return;  // an empty range: no statistics, no rows
+    ln_gn_range_sums(x, nullptr, nullptr, 0, lo, hi, c, s_sum, s_sq);
+    ln_gn_affine_of_sums(s_sum, s_sq, gamma, beta, hi - lo, c, groups, eps, s_a, s_b, mean_rstd + (size_t)s * 2 * groups,
+                         scale_shift + (size_t)s * 2 * c);
+    __syncthreads();
+    ln_gn_affine_rows(x, s_a, s_b, (long long)lo * c / 4, (long long)hi * c / 4, c, relu, y);
+}
+
+// The owner of range s takes the sums of gy' x and gy' over its range, writes dx and leaves its terms of the parameter gradients in
+// parts[s * 2 C ...] (zeros for an empty range) for k_gn_param_grads_segments.
+__global__ void __launch_bounds__(256)
+    k_gn_backward_range_owner(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ gamma,
+                              const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m, int c, int groups, int relu,
+                              float* __restrict__ dx, double* __restrict__ parts, double* __restrict__ zero_next, int zero_count,
+                              const int* __restrict__ rows_dev, const int* __restrict__ row_starts, int segments) {
+    __shared__ double s_ds[LN_GN_MAX_C], s_db[LN_GN_MAX_C];
+    const int s = blockIdx.y;
+    int live, lo, hi;
+    ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
+    ln_gn_segments_housekeeping(zero_next, zero_count, live, m, c, dx);
+    parts += (size_t)s * 2 * c;
+    if (hi == lo) {
+        for (int i = threadIdx.x; i < 2 * c; i += 256) parts[i] = 0.0;
+        return;
+    }
+    scale_shift += (size_t)s * 2 * c;
+    ln_gn_range_sums(x, gy, scale_shift, relu, lo, hi, c, s_ds, s_db);
+    double *term_gamma, *term_beta;
+    ln_gn_backward_of_sums(x, gy, s_ds, s_db, gamma, mean_rstd + (size_t)s * 2 * groups, scale_shift, hi - lo, (long long)lo * c / 4,
+                           (long long)hi * c / 4, c, groups, relu, dx, term_gamma, term_beta);
+    for (int col = threadIdx.x; col < c; col += 256) {
+        parts[col] = term_gamma[col];
+        parts[c + col] = term_beta[col];
+    }
+}
+
 static int ln_gn_check(const char* who, int m, int c, int groups) {
     LN_REQUIRE(m >= 1 && c >= 4 && c <= LN_GN_MAX_C && c % 4 == 0, LN_ERR_UNSUPPORTED, "%s: need 1 <= rows, channels %% 4 == 0 and <= %d (got %d x %d)",
                who, LN_GN_MAX_C, m, c);
@@ -697,30 +835,40 @@ extern "C" int ln_batch_norm_backward(const float* x, const float* grad_y, const
     return ln_check_launch("ln_batch_norm_backward");
 }
 
-extern "C" int ln_cloud_row_starts(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream) {
-    LN_REQUIRE(t && t->keys && t->nr_filled && t->pos_dim >= 1 && t->pos_dim <= LN_MAX_POS_DIM, LN_ERR_ARG, "ln_cloud_row_starts: null table");
+static int ln_cloud_row_starts_run(const char* who, const LnTable* t, int rows_upper, int clouds, int max_clouds, int* row_starts, int* order_flag, void* stream) {
+    LN_REQUIRE(t && t->keys && t->nr_filled && t->pos_dim >= 1 && t->pos_dim <= LN_MAX_POS_DIM, LN_ERR_ARG, "%s: null table", who);
     LN_REQUIRE((t->batch_points > 0 || t->batch_points == LN_BATCH_POINT_STARTS) && t->batch_key_step >= 2, LN_ERR_ARG,
-               "ln_cloud_row_starts: the table holds no batch of clouds");
-    LN_REQUIRE(clouds >= 1 && clouds <= LN_GN_MAX_SEGMENTS, LN_ERR_UNSUPPORTED, "ln_cloud_row_starts: 1 <= clouds <= %d (got %d)",
-               LN_GN_MAX_SEGMENTS, clouds);
-    LN_REQUIRE(rows_upper >= 0 && row_starts && order_flag, LN_ERR_ARG, "ln_cloud_row_starts: null output or negative rows_upper");
+               "%s: the table holds no batch of clouds", who);
+    LN_REQUIRE(clouds >= 1 && clouds <= max_clouds, LN_ERR_UNSUPPORTED, "%s: 1 <= clouds <= %d (got %d)", who, max_clouds, clouds);
+    LN_REQUIRE(rows_upper >= 0 && row_starts && order_flag, LN_ERR_ARG, "%s: null output or negative rows_upper", who);
     hipStream_t st = (hipStream_t)stream;
-    if (ln_zero_async(order_flag, sizeof(int), st) != LN_OK) return ln_check_launch("ln_cloud_row_starts(memset)");
+    if (ln_zero_async(order_flag, sizeof(int), st) != LN_OK) return ln_check_launch(who);
     LN_LAUNCH("k_cloud_row_starts", k_cloud_row_starts, dim3(ln_div_up((long long)rows_upper + 1, 256)), dim3(256), 0, st, *t, rows_upper, clouds,
               row_starts, order_flag);
-    return ln_check_launch("ln_cloud_row_starts");
+    return ln_check_launch(who);
 }
 
-// B accumulator slabs, then the B x 2 C parameter-gradient terms of the backward call
+// (k_cloud_row_starts writes any number of starts: the two entry points differ in the limit they check)
+extern "C" int ln_cloud_row_starts(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream) {
+    return ln_cloud_row_starts_run("ln_cloud_row_starts", t, rows_upper, clouds, LN_CLOUDS_MAX, row_starts, order_flag, stream);
+}
+
+extern "C" int ln_cloud_row_starts_many(const LnTable* t, int rows_upper, int clouds, int* row_starts, int* order_flag, void* stream) {
+    return ln_cloud_row_starts_run("ln_cloud_row_starts_many", t, rows_upper, clouds, LN_CLOUDS_MANY_MAX, row_starts, order_flag, stream);
+}
+
+// Up to LN_GN_MAX_SEGMENTS ranges: B accumulator slabs, then the B x 2 C parameter-gradient terms of the backward call.  Beyond (the
+// range-owner form): the B x 2 C terms alone, written before they are read, so that nothing in this workspace has to be zero.
 extern "C" size_t ln_group_norm_segments_workspace_bytes(int channels, int segments) {
-    return (size_t)segments * (ln_group_norm_workspace_bytes(channels) + 2 * (size_t)channels * sizeof(double));
+    const size_t parts = 2 * (size_t)channels * sizeof(double);
+    if (segments > LN_GN_MAX_SEGMENTS) return (size_t)segments * parts;
+    return (size_t)segments * (ln_group_norm_workspace_bytes(channels) + parts);
 }
 
-static int ln_gn_segments_check(const char* who, int m, int c, int groups, int segments, const int* row_starts) {
+static int ln_gn_segments_check(const char* who, int m, int c, int groups, int segments, int max_segments, const int* row_starts) {
     int rc = ln_gn_check(who, m, c, groups);
     if (rc) return rc;
-    LN_REQUIRE(segments >= 1 && segments <= LN_GN_MAX_SEGMENTS, LN_ERR_UNSUPPORTED, "%s: 1 <= row ranges <= %d (got %d)", who, LN_GN_MAX_SEGMENTS,
-               segments);
+    LN_REQUIRE(segments >= 1 && segments <= max_segments, LN_ERR_UNSUPPORTED, "%s: 1 <= row ranges <= %d (got %d)", who, max_segments, segments);
     LN_REQUIRE(row_starts, LN_ERR_ARG, "%s: null row_starts", who);
     return LN_OK;
 }
@@ -728,41 +876,75 @@ static int ln_gn_segments_check(const char* who, int m, int c, int groups, int s
 // apply grid of one range: sized for twice the mean range (the loops are grid-stride: any range is covered)
 static int ln_gn_segments_apply_grid(int m, int c, int segments) { return ln_gn_apply_grid(2 * ln_div_up(m, segments), c); }
 
-extern "C" int ln_group_norm_forward_segments(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
-                                              int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
-                                              void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
-                                              int segments, void* stream) {
-    int rc = ln_gn_segments_check("ln_group_norm_forward_segments", m, channels, groups, segments, row_starts);
+static int ln_gn_forward_segments_run(const char* who, int max_segments, const float* x, const float* gamma, const float* beta, int m, int channels, int groups,
+                                      float eps, int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
+                                      void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
+                                      int segments, void* stream) {
+    int rc = ln_gn_segments_check(who, m, channels, groups, segments, max_segments, row_starts);
     if (rc) return rc;
-    rc = ln_norm_check_buffers("ln_group_norm_forward_segments", x, nullptr, y, mean_rstd, scale_shift, workspace, workspace_bytes,
+    rc = ln_norm_check_buffers(who, x, nullptr, y, mean_rstd, scale_shift, workspace, workspace_bytes,
                                ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, false);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
+    if (segments > LN_GN_MAX_SEGMENTS) {  // many short ranges: one owner per range, `workspace` is not touched
+        LN_LAUNCH("k_gn_forward_range_owner", k_gn_forward_range_owner, dim3(1, segments), dim3(256), 0, st, x, gamma, beta, m, channels, groups, eps,
+                  relu, y, mean_rstd, scale_shift, static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device,
+                  row_starts, segments);
+        return ln_check_launch(who);
+    }
     double* acc = static_cast<double*>(workspace);
     if (!next_workspace && ln_zero_async(acc, (size_t)segments * ln_group_norm_workspace_bytes(channels), st) != LN_OK)
-        return ln_check_launch("ln_group_norm_forward_segments(memset)");
+        return ln_check_launch(who);
     LN_LAUNCH("k_gn_stats_segments", k_gn_stats_segments, dim3(ln_gn_stats_grid(m, channels), segments), dim3(256), 0, st, x, (const float*)nullptr,
               (const float*)nullptr, 0, m, channels, acc, rows_device, row_starts, segments);
     LN_LAUNCH("k_gn_apply_segments", k_gn_apply_segments, dim3(ln_gn_segments_apply_grid(m, channels, segments), segments), dim3(256), 0, st, x,
               (const double*)acc, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, static_cast<double*>(next_workspace),
               int(next_workspace_bytes / sizeof(double)), rows_device, row_starts, segments);
-    return ln_check_launch("ln_group_norm_forward_segments");
+    return ln_check_launch(who);
 }
 
-extern "C" int ln_group_norm_backward_segments(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
-                                               const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
-                                               float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
-                                               size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream) {
-    int rc = ln_gn_segments_check("ln_group_norm_backward_segments", m, channels, groups, segments, row_starts);
+// The entry points over row ranges.  ln_group_norm_forward_segments / _backward_segments take up to LN_GN_MAX_SEGMENTS ranges, as they always
+// did; ln_group_norm_forward_many_segments / _backward_many_segments take up to LN_GN_MANY_MAX_SEGMENTS and, beyond LN_GN_MAX_SEGMENTS, the
+// range-owner kernels (up to there they are the first pair, launch for launch).
+extern "C" int ln_group_norm_forward_segments(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
+                                              int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
+                                              void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
+                                              int segments, void* stream) {
+    return ln_gn_forward_segments_run("ln_group_norm_forward_segments", LN_GN_MAX_SEGMENTS, x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace,
+                                      workspace_bytes, next_workspace, next_workspace_bytes, rows_device, row_starts, segments, stream);
+}
+
+extern "C" int ln_group_norm_forward_many_segments(const float* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
+                                                   int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace,
+                                                   size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes,
+                                                   const int* rows_device, const int* row_starts, int segments, void* stream) {
+    return ln_gn_forward_segments_run("ln_group_norm_forward_many_segments", LN_GN_MANY_MAX_SEGMENTS, x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace,
+                                      workspace_bytes, next_workspace, next_workspace_bytes, rows_device, row_starts, segments, stream);
+}
+
+static int ln_gn_backward_segments_run(const char* who, int max_segments, const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
+                                       const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
+                                       float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
+                                       size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream) {
+    int rc = ln_gn_segments_check(who, m, channels, groups, segments, max_segments, row_starts);
     if (rc) return rc;
-    rc = ln_norm_check_buffers("ln_group_norm_backward_segments", x, grad_y, grad_x, mean_rstd, scale_shift, workspace, workspace_bytes,
+    rc = ln_norm_check_buffers(who, x, grad_y, grad_x, mean_rstd, scale_shift, workspace, workspace_bytes,
                                ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, true);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     double* acc = static_cast<double*>(workspace);
+    if (segments > LN_GN_MAX_SEGMENTS) {  // many short ranges: one owner per range, the workspace is the B x 2 C terms
+        LN_LAUNCH("k_gn_backward_range_owner", k_gn_backward_range_owner, dim3(1, segments), dim3(256), 0, st, x, grad_y, gamma, mean_rstd,
+                  scale_shift, m, channels, groups, relu, grad_x, acc, static_cast<double*>(next_workspace),
+                  int(next_workspace_bytes / sizeof(double)), rows_device, row_starts, segments);
+        if (grad_gamma || grad_beta)
+            LN_LAUNCH("k_gn_param_grads_segments", k_gn_param_grads_segments, dim3(ln_div_up(2 * channels, 256)), dim3(256), 0, st,
+                      (const double*)acc, segments, channels, grad_gamma, grad_beta);
+        return ln_check_launch(who);
+    }
     const size_t slabs = (size_t)segments * ln_group_norm_workspace_bytes(channels);
     double* parts = acc + slabs / sizeof(double);
-    if (!next_workspace && ln_zero_async(acc, slabs, st) != LN_OK) return ln_check_launch("ln_group_norm_backward_segments(memset)");
+    if (!next_workspace && ln_zero_async(acc, slabs, st) != LN_OK) return ln_check_launch(who);
     LN_LAUNCH("k_gn_stats_segments", k_gn_stats_segments, dim3(ln_gn_stats_grid(m, channels), segments), dim3(256), 0, st, x, grad_y, scale_shift, relu,
               m, channels, acc, rows_device, row_starts, segments);
     LN_LAUNCH("k_gn_backward_apply_segments", k_gn_backward_apply_segments, dim3(ln_gn_segments_apply_grid(m, channels, segments), segments), dim3(256),
@@ -771,5 +953,24 @@ extern "C" int ln_group_norm_backward_segments(const float* x, const float* grad
     if (grad_gamma || grad_beta)
         LN_LAUNCH("k_gn_param_grads_segments", k_gn_param_grads_segments, dim3(ln_div_up(2 * channels, 256)), dim3(256), 0, st, (const double*)parts,
                   segments, channels, grad_gamma, grad_beta);
-    return ln_check_launch("ln_group_norm_backward_segments");
+    return ln_check_launch(who);
+}
+
+extern "C" int ln_group_norm_backward_segments(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
+                                               const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
+                                               float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
+                                               size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream) {
+    return ln_gn_backward_segments_run("ln_group_norm_backward_segments", LN_GN_MAX_SEGMENTS, x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x, grad_gamma,
+                                       grad_beta, workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device, row_starts, segments,
+                                       stream);
+}
+
+extern "C" int ln_group_norm_backward_many_segments(const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
+                                                    const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x,
+                                                    float* grad_gamma, float* grad_beta, void* workspace, size_t workspace_bytes,
+                                                    void* next_workspace, size_t next_workspace_bytes, const int* rows_device,
+                                                    const int* row_starts, int segments, void* stream) {
+    return ln_gn_backward_segments_run("ln_group_norm_backward_many_segments", LN_GN_MANY_MAX_SEGMENTS, x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x,
+                                       grad_gamma, grad_beta, workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device,
+                                       row_starts, segments, stream);
 }

@@ -441,6 +441,7 @@ class HashTable:
         self._cloud_lengths = None  # clouds of unequal sizes (set_cloud_batch([...])): the lengths, and the device int32 [B + 1] of their
         self._cloud_starts = None   # first points (LnTableClouds.batch_point_starts), one tensor shared with clones and coarser levels
         self._per_cloud_norm = False  # GroupNorm blocks take their statistics per cloud of the batch (set_cloud_batch(per_cloud_norm=True))
+        self._many_clouds = False  # the per-cloud switches take up to 1024 clouds, not 64 (set_cloud_batch(many_clouds=True))
         self._per_cloud_invalid_vertex = False  # Distribute / PointNet drop the first vertex of every cloud (set_cloud_batch(per_cloud_invalid_vertex=True))
         self._band = None  # band check of the batch (set_cloud_batch(check_band=True)): a _BandCheck shared with clones and coarser levels
         self._band_launch = False  # this table's builds queue the check (the finest level: its verdict with the guard covers the coarser ones)
@@ -707,6 +708,7 @@ class Lattice:
         ht._cloud_lengths, ht._cloud_starts = oh._cloud_lengths, oh._cloud_starts
         ht._per_cloud_norm = oh._per_cloud_norm
         ht._per_cloud_invalid_vertex = oh._per_cloud_invalid_vertex
+        ht._many_clouds = oh._many_clouds
         ht._band, ht._band_launch = oh._band, oh._band_launch
         ht._static_levels = getattr(oh, "_static_levels", None)
         ht.m_nr_filled_is_dirty = oh.m_nr_filled_is_dirty
@@ -1444,6 +1446,7 @@ class Lattice:
         ht._cloud_lengths, ht._cloud_starts = self.m_hash_table._cloud_lengths, self.m_hash_table._cloud_starts
         ht._per_cloud_norm = self.m_hash_table._per_cloud_norm
         ht._per_cloud_invalid_vertex = self.m_hash_table._per_cloud_invalid_vertex
+        ht._many_clouds = self.m_hash_table._many_clouds
         ht._band = self.m_hash_table._band  # (inherited, but no launch: the finest level's verdict with the guard covers this level)
         ht._storage = _TableStorage(capacity, d, dev, spare_row_width=self.val_dim())
         # [1, val_dim] zeros: a placeholder until the coarse values exist
@@ -1759,7 +1762,8 @@ class Lattice:
         ht._static_levels = None if coarse_bounds is None else {self.m_lvl + 1 + k: int(b) for k, b in enumerate(coarse_bounds)}
 
     def set_cloud_batch(self, points_per_cloud, quotient_step: int = 1 << 13, per_cloud_norm: bool = False,
-                        per_cloud_invalid_vertex: bool = False, check_band: bool = False, guard: Optional[int] = None):
+                        per_cloud_invalid_vertex: bool = False, check_band: bool = False, guard: Optional[int] = None,
+                        many_clouds: bool = False):
         """The multi-cloud launch form for small clouds.  From now on the positions handed to this lattice are a BATCH of independent
         clouds of `points_per_cloud` points each (cloud c = rows c * points_per_cloud ... of the positions tensor; None / 0 switches it
         off).  The lattice of cloud c is translated by c * quotient_step lattice cells along the first coordinate (a translation of the
@@ -1795,12 +1799,14 @@ class Lattice:
         set_row_order("canonical"); coarser levels inherit it) makes the GroupNorm of the `Gn*` blocks and of GroupNormLatticeModule
         take its statistics per cloud: in first-occurrence row order the vertices of cloud c are one contiguous row range
         (cloud_row_starts()), and the kernels run the same GroupNorm over each range (ln_group_norm_forward_segments), in eager
-        mode and under set_static_rows.  At most 64 clouds.  A network of such blocks then computes, for every cloud, what a run on
+        mode and under set_static_rows.  At most 64 clouds, or at most 1024 with `many_clouds=True` (beyond 64
+        the kernels take a form made for many short ranges, one workgroup per cloud: a long cloud among them is correct and slow; the
+        switch is inherited by clones and coarser levels and changes nothing up to 64 clouds).  A network of such blocks then computes, for every cloud, what a run on
         that cloud alone computes, and parameter gradients that are the sum over the clouds.
 
         DistributeLatticeModule and PointNetModule treat row 0 of the table as the reference's "invalid" vertex: in canonical row order
         the first vertex of point 0, whose tokens are zeroed and whose PointNet feature is dropped.  In a batch, row 0 is the first
-        vertex of cloud 0 only.  `per_cloud_invalid_vertex=True` (same conditions as per_cloud_norm: canonical rows, at most 64 clouds,
+        vertex of cloud 0 only.  `per_cloud_invalid_vertex=True` (same conditions as per_cloud_norm: canonical rows, at most 64 clouds or 1024 with many_clouds=True,
         inherited by clones and coarser levels) makes both modules drop the first vertex of EVERY cloud, row cloud_row_starts()[c]
         (ln_distribute_centre_clouds, ln_pointnet_reduce_forward_clouds), in eager mode, under set_static_rows and inside a capture.
         With both switches on, models.LNN on a batch computes for every cloud what a run on that cloud alone computes.  Only the fused
@@ -1808,15 +1814,17 @@ class Lattice:
         `distributed`) it raises a ValueError.
 
         Not covered: coarse levels built from keys (create_coarse_verts: cloud_row_starts() has no ranges for them), slot and space row
-        orders, more than 64 clouds; BatchNorm blocks (statistics over the batch by definition) are unchanged.  With the defaults
+        orders, more than 1024 clouds; BatchNorm blocks (statistics over the batch by definition) are unchanged.  With the defaults
         False nothing changes."""
         d = self.pos_dim() if self.m_hash_table.is_initialized() else len(self.m_sigmas)
         band = None
         lengths = None
         if points_per_cloud is not None and not isinstance(points_per_cloud, int) and hasattr(points_per_cloud, "__len__"):
             lengths = _checked_cloud_lengths(points_per_cloud)
-            if (per_cloud_norm or per_cloud_invalid_vertex) and len(lengths) > Lattice.MAX_BATCH_CLOUDS:
-                raise ValueError(f"{len(lengths)} clouds: per_cloud_norm and per_cloud_invalid_vertex take at most {Lattice.MAX_BATCH_CLOUDS}")
+            limit = Lattice.MAX_BATCH_CLOUDS if many_clouds else Lattice.DEFAULT_MAX_BATCH_CLOUDS
+            if (per_cloud_norm or per_cloud_invalid_vertex) and len(lengths) > limit:
+                raise ValueError(f"{len(lengths)} clouds: per_cloud_norm and per_cloud_invalid_vertex take at most {limit}" +
+                                 ("" if many_clouds else f" ({Lattice.MAX_BATCH_CLOUDS} with many_clouds=True)"))
             points_per_cloud = max(max(lengths), 1)  # (LnTable.batch_points > 0 marks the batch; the kernels take the ranges from the list)
         if not points_per_cloud:
             self.m_hash_table._batch = (0, 0)
@@ -1838,16 +1846,18 @@ class Lattice:
         self.m_hash_table._band_launch = band is not None
         self.m_hash_table._per_cloud_norm = bool(per_cloud_norm) and bool(points_per_cloud)
         self.m_hash_table._per_cloud_invalid_vertex = bool(per_cloud_invalid_vertex) and bool(points_per_cloud)
+        self.m_hash_table._many_clouds = bool(many_clouds) and bool(points_per_cloud)
         if self.m_hash_table.is_initialized():
             self.m_hash_table._storage.touch()
 
-    MAX_BATCH_CLOUDS = 64  # LN_GN_MAX_SEGMENTS of csrc/ln_norm.hip
+    MAX_BATCH_CLOUDS = 1024  # with set_cloud_batch(many_clouds=True): LN_CLOUDS_MANY_MAX of csrc/ln_common.h
+    DEFAULT_MAX_BATCH_CLOUDS = 64  # without: LN_CLOUDS_MAX
     CLOUD_STARTS_MESSAGE = ("the per-cloud point starts of the batch (LnTableClouds.batch_point_starts, Lattice.set_cloud_batch([...])) are not an "
                             "ascending list from 0 to the number of points: the clouds of this build are wrong")
 
     def _cloud_batch_size(self) -> int:
         """Clouds in the batch the last build of this table inserted.  Raises, without device work, where cloud_row_starts() has no
-        meaning: no batch, more than 64 clouds, a level not built from positions, rows not numbered by first occurrence."""
+        meaning: no batch, more than 64 clouds (1024 with many_clouds), a level not built from positions, rows not numbered by first occurrence."""
         ht = self.m_hash_table
         st = ht._storage
         if not ht._batch[0]:
@@ -1858,8 +1868,10 @@ class Lattice:
         if not st.rows_first_occurrence:
             raise _lib.LatticeNetHipError('cloud_row_starts: the rows of a cloud are one contiguous range only in first-occurrence row '
                                           'order: call set_row_order("canonical") before the lattice is built')
-        if st.batch_clouds > Lattice.MAX_BATCH_CLOUDS:
-            raise _lib.LatticeNetHipError(f"cloud_row_starts: {st.batch_clouds} clouds in the batch, at most {Lattice.MAX_BATCH_CLOUDS}")
+        limit = Lattice.MAX_BATCH_CLOUDS if ht._many_clouds else Lattice.DEFAULT_MAX_BATCH_CLOUDS
+        if st.batch_clouds > limit:
+            raise _lib.LatticeNetHipError(f"cloud_row_starts: {st.batch_clouds} clouds in the batch, at most {limit}" +
+                                          ("" if ht._many_clouds else f" ({Lattice.MAX_BATCH_CLOUDS} with set_cloud_batch(many_clouds=True))"))
         return st.batch_clouds
 
     def _cloud_rows(self) -> torch.Tensor:
@@ -1874,7 +1886,8 @@ class Lattice:
             return hit[0]
         out = torch.empty((clouds + 2,), dtype=torch.int32, device=self._dev())
         t = ht.c_table()
-        _lib.check(_lib.load().ln_cloud_row_starts(C.byref(t), rows_upper, clouds, _lib.ptr(out), out.data_ptr() + 4 * (clouds + 1),
+        fn = _lib.load().ln_cloud_row_starts_many if clouds > Lattice.DEFAULT_MAX_BATCH_CLOUDS else _lib.load().ln_cloud_row_starts
+        _lib.check(fn(C.byref(t), rows_upper, clouds, _lib.ptr(out), out.data_ptr() + 4 * (clouds + 1),
                                                    self._stream()), "ln_cloud_row_starts")
         st.nbr_cache[key] = (out,)
         return out

@@ -57,6 +57,8 @@ class BatchNormLatticeModule(torch.nn.Module):  # mods:570-583
         return lattice_values, lattice_py
 
 
+MAX_ROW_RANGES = 1024  # row ranges of one GroupNorm call asked for with many_ranges=True (LN_CLOUDS_MANY_MAX of csrc/ln_common.h)
+DEFAULT_MAX_ROW_RANGES = 64  # ... and without (LN_CLOUDS_MAX): up to here the accumulator-slab kernels, beyond one workgroup per range
 _GN_WORKSPACES = {}
 _GN_PRIVATE = [None]  # accumulator pair of the captured step being warmed up / captured (use_gn_workspace)
 
@@ -66,7 +68,8 @@ def new_gn_workspace(device, nbytes: int = 0, segments: int = 1):
     `segments` row ranges (the clouds of a batch with per-cloud statistics: Lattice.cloud_segments())."""
     if nbytes <= 0:
         lib = _lib.load()
-        nbytes = int(lib.ln_group_norm_workspace_bytes(1024) if segments <= 1 else lib.ln_group_norm_segments_workspace_bytes(1024, segments))
+        # (whole-matrix launches share the pair: never smaller than theirs, whatever the form the ranges take)
+        nbytes = int(max(lib.ln_group_norm_workspace_bytes(1024), lib.ln_group_norm_segments_workspace_bytes(1024, segments) if segments > 1 else 0))
     n = max(nbytes // 8, 1)
     return {"bufs": [torch.zeros((n,), dtype=torch.float64, device=device), torch.zeros((n,), dtype=torch.float64, device=device)],
             "dirty": [0, 0], "cur": 0}
@@ -149,7 +152,8 @@ def _gn_forward(x, weight, bias, num_groups, eps, relu, rows_dev, row_starts=Non
     args = (_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), m, c, num_groups, float(eps), int(relu), _lib.ptr(y), _lib.ptr(mean_rstd),
             _lib.ptr(scale_shift), _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev))
     if ranged:
-        _gn_check(lib.ln_group_norm_forward_segments(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_forward_segments", x.device, stream)
+        fn = lib.ln_group_norm_forward_many_segments if segments > DEFAULT_MAX_ROW_RANGES else lib.ln_group_norm_forward_segments
+        _gn_check(fn(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_forward_segments", x.device, stream)
     else:
         _gn_check(lib.ln_group_norm_forward_rows(*args, stream), "ln_group_norm_forward", x.device, stream)
     return x, y, mean_rstd, scale_shift
@@ -171,8 +175,8 @@ def _gn_backward(grad_y, x, weight, mean_rstd, scale_shift, num_groups, relu, ha
     args = (_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(weight), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), m, c, num_groups, int(relu),
             _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b), _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev))
     if ranged:
-        _gn_check(lib.ln_group_norm_backward_segments(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_backward_segments", x.device,
-                  stream)
+        fn = lib.ln_group_norm_backward_many_segments if segments > DEFAULT_MAX_ROW_RANGES else lib.ln_group_norm_backward_segments
+        _gn_check(fn(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_backward_segments", x.device, stream)
     else:
         _gn_check(lib.ln_group_norm_backward_rows(*args, stream), "ln_group_norm_backward", x.device, stream)
     return grad_x, grad_w, grad_b
@@ -198,7 +202,7 @@ class GroupNormReluFunction(torch.autograd.Function):
 class GroupNormSegmentsFunction(torch.autograd.Function):
     """GroupNormReluFunction over row ranges: the rows [row_starts[s], row_starts[s + 1]) of x are normalised with the statistics of
     that range alone (ln_group_norm_forward_segments / _backward_segments) — the clouds of a batch in one lattice
-    (Lattice.cloud_row_starts()).  `row_starts`: device int32 [B + 1], B <= 64; the rows from row_starts[B] on come out as zeros.  The
+    (Lattice.cloud_row_starts()).  `row_starts`: device int32 [B + 1], B <= 1024 (beyond 64 the _many_segments entry points); the rows from row_starts[B] on come out as zeros.  The
     gradients of weight and bias are the sums over the ranges."""
 
     @staticmethod
@@ -323,17 +327,20 @@ def batch_norm_rows(x: torch.Tensor, bn: torch.nn.BatchNorm1d, relu: bool = Fals
     return torch.relu(y) if relu else y
 
 
-def group_norm_rows(x: torch.Tensor, gn: torch.nn.GroupNorm, relu: bool = False, rows_dev=None, row_starts=None) -> torch.Tensor:
+def group_norm_rows(x: torch.Tensor, gn: torch.nn.GroupNorm, relu: bool = False, rows_dev=None, row_starts=None,
+                    many_ranges: bool = False) -> torch.Tensor:
     """GroupNorm of an [M, C] matrix with the parameters of `gn` (statistics over rows x group channels).  `rows_dev`: device int
     holding the number of rows that count (Lattice.rows_device(): static-rows mode, where x is taller than its lattice).
-    `row_starts`: device int32 [B + 1], B <= 64 — the statistics are taken per row range [row_starts[s], row_starts[s + 1]) (the
+    `row_starts`: device int32 [B + 1], B <= 64, or B <= 1024 with many_ranges=True (beyond 64 ranges a kernel form made for many
+    short ranges: one workgroup per range, a long range is correct and slow) — the statistics are taken per row range [row_starts[s], row_starts[s + 1]) (the
     clouds of a batch: Lattice.cloud_row_starts(), or cloud_point_starts() for per-point rows); only the HIP kernels do that."""
     native = x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.shape[1] <= 1024 and x.shape[0] > 0
     if row_starts is not None:
+        limit = MAX_ROW_RANGES if many_ranges else DEFAULT_MAX_ROW_RANGES
         if not native or row_starts.dtype != torch.int32 or row_starts.device != x.device or not row_starts.is_contiguous() or \
-                not 2 <= row_starts.numel() <= 65:
+                not 2 <= row_starts.numel() <= limit + 1:
             raise ValueError("GroupNorm per row range needs the HIP GroupNorm (float32 CUDA rows, channels % 4 == 0, <= 1024 channels) and "
-                             "a contiguous int32 row_starts [B + 1], B <= 64, on the device of the rows")
+                             f"a contiguous int32 row_starts [B + 1], B <= {limit}, on the device of the rows")
         return GroupNormSegmentsFunction.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, relu, rows_dev, row_starts)
     if native:
         return GroupNormReluFunction.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, relu, rows_dev)
@@ -354,8 +361,9 @@ class GroupNormLatticeModule(torch.nn.Module):  # mods:585-616: 32 groups, or C/
         # a batch of clouds with per_cloud_norm: the statistics of every cloud over its own row range (asked of a Lattice only: any
         # object with the lattice interface of the blocks may stand in for one)
         starts = getattr(lattice_py, "per_cloud_norm_row_starts", None)
+        # (many_ranges: a Lattice hands out more than 64 ranges only where set_cloud_batch(many_clouds=True) asked for them)
         lattice_values = group_norm_rows(lattice_values, self.gn, fuse_relu, lattice_py.rows_device() if lattice_py is not None else None,
-                                         starts() if starts is not None else None)
+                                         starts() if starts is not None else None, many_ranges=True)
         if do_set_values:
             lattice_py.set_values(lattice_values)
         return lattice_values, lattice_py

@@ -247,6 +247,11 @@ def _invalid_row_starts(lattice):
     return starts() if starts is not None else None
 
 
+def _many_clouds(starts) -> bool:
+    """More clouds than the *_clouds entry points take: the *_many_clouds ones (Lattice.set_cloud_batch(many_clouds=True))."""
+    return starts.numel() - 1 > Lattice.DEFAULT_MAX_BATCH_CLOUDS
+
+
 class PointNetReduceFunction(torch.autograd.Function):
     """The vertex side of PointNetModule (lattice_modules.py:688-712): per-vertex max of the token features with the barycentric
     weight of each winning token appended, vertices with fewer than four tokens and vertex 0 zeroed — on a batch of clouds with
@@ -273,8 +278,9 @@ class PointNetReduceFunction(torch.autograd.Function):
         args = (C.byref(csr), _lib.ptr(grp_row), max_seg, _lib.ptr(x), c, distributed.data_ptr() + 4 * (width - 1), width, m, 4, _lib.ptr(ws),
                 ws.numel(), _lib.ptr(out), _lib.ptr(arg))
         if starts is not None:
-            _lib.check(lib.ln_pointnet_reduce_forward_clouds(*args, _lib.ptr(starts), starts.numel() - 1, _lib.stream_ptr(dev)),
-                       "ln_pointnet_reduce_forward_clouds")
+            clouds = starts.numel() - 1
+            fn = lib.ln_pointnet_reduce_forward_many_clouds if _many_clouds(starts) else lib.ln_pointnet_reduce_forward_clouds
+            _lib.check(fn(*args, _lib.ptr(starts), clouds, _lib.stream_ptr(dev)), "ln_pointnet_reduce_forward_clouds")
         else:
             _lib.check(lib.ln_pointnet_reduce_forward(*args, _lib.stream_ptr(dev)), "ln_pointnet_reduce_forward")
         ctx.save_for_backward(arg, splatting_indices)
@@ -319,7 +325,8 @@ class DistributeLatticeModule(torch.nn.Module):  # lattice_modules.py:52-96
             centred = torch.empty_like(distributed)
             point_starts = getattr(getattr(distributed_lattice, "m_hash_table", None), "_cloud_starts", None) if starts is not None else None
             if point_starts is not None:  # clouds of unequal sizes: the cloud of a token comes from the batch's point starts
-                _lib.check(_lib.load().ln_distribute_centre_cloud_starts(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums),
+                fn = _lib.load().ln_distribute_centre_many_cloud_starts if _many_clouds(starts) else _lib.load().ln_distribute_centre_cloud_starts
+                _lib.check(fn(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums),
                                                                          _lib.ptr(counts), tokens, width, pos_dim,
                                                                          distributed_lattice.pos_dim() + 1, _lib.ptr(point_starts),
                                                                          _lib.ptr(starts), starts.numel() - 1, _lib.ptr(centred),
@@ -328,7 +335,8 @@ class DistributeLatticeModule(torch.nn.Module):  # lattice_modules.py:52-96
                 return distributed_lattice, centred, splatting_indices, splatting_weights
             if starts is not None:  # a batch of clouds: the first vertex of every cloud is its "invalid" vertex
                 tokens_per_cloud = distributed_lattice.points_per_cloud() * (distributed_lattice.pos_dim() + 1)
-                _lib.check(_lib.load().ln_distribute_centre_clouds(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums),
+                fn = _lib.load().ln_distribute_centre_many_clouds if _many_clouds(starts) else _lib.load().ln_distribute_centre_clouds
+                _lib.check(fn(_lib.ptr(distributed), _lib.ptr(splatting_indices), _lib.ptr(sums),
                                                                    _lib.ptr(counts), tokens, width, pos_dim, tokens_per_cloud, _lib.ptr(starts),
                                                                    starts.numel() - 1, _lib.ptr(centred), _lib.stream_ptr(distributed.device)),
                            "ln_distribute_centre_clouds")

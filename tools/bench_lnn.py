@@ -42,7 +42,8 @@ lattice_gpu: { hash_table_capacity: 5000000  nr_sigmas: 1  sigma_0: "0.08 3" }
 def set_clouds(lattice, args):
     """--clouds B: the scan is a batch of B clouds of n / B points in one lattice, GroupNorm statistics and the "invalid" vertex per cloud."""
     if args.clouds > 1:
-        lattice.set_cloud_batch(args.n // args.clouds, per_cloud_norm=True, per_cloud_invalid_vertex=True)
+        lattice.set_cloud_batch(args.n // args.clouds, per_cloud_norm=True, per_cloud_invalid_vertex=True,
+                                many_clouds=args.clouds > Lattice.DEFAULT_MAX_BATCH_CLOUDS)
 
 
 def make_graph_step(args, preset, cfg_text, net, opt, gen, dev, nll_loss_gather, first=None):
@@ -162,7 +163,7 @@ def main():
     ap.add_argument("--in-flight", type=int, default=1, help="with --graph: scans per optimizer step, each with its own lattice, graph and "
                                                              "stream, replayed concurrently; their gradients are summed (batch of K scans)")
     ap.add_argument("--clouds", type=int, default=1, help="run the network on a batch of B clouds of n / B points in one lattice "
-                                                          "(Lattice.set_cloud_batch with both per-cloud switches; canonical row order; B <= 64)")
+                                                          "(Lattice.set_cloud_batch with both per-cloud switches; canonical row order; B <= 1024)")
     ap.add_argument("--host-profile", action="store_true", help="cProfile of the host side of the timed steps")
     ap.add_argument("--gc", type=int, default=0, help="1 = leave Python's cyclic garbage collector on during the timed steps; 2 = on, after gc.freeze()")
     args = ap.parse_args()

@@ -6,7 +6,13 @@ What is measured is the wall-clock time of 200 eager forward + backward calls be
 kernels plus the Python and autograd overhead of either path, which is what a training loop in eager mode pays.  Five runs of each,
 alternating.  The rule for switching FUSED_BATCH_NORM on: the median of the five native runs below the fastest torch
 run.  (Both paths are in training mode: every call also moves the module's running statistics and num_batches_tracked, part of
-either path's work and of no consequence here.)"""
+either path's work and of no consequence here.)
+
+--ranges B [B ...]: instead, GroupNorm + ReLU forward + backward per row range at [46 080, 64] and [11 520, 128], B equal ranges
+(ln_group_norm_forward_many_segments / _backward_many_segments: up to 64 ranges the accumulator-slab kernels, beyond one workgroup per
+range) against the whole-matrix GroupNorm on the same tensor, through the C ABI on buffers allocated once, the alternating accumulator
+pair as the modules use it.  A window is 200 forward + backward pairs queued between two device synchronisations, divided by 200: the
+kernels of a pair when they take longer than their launches.  Five windows of each form, alternating; median, fastest and slowest."""
 import os
 import statistics
 import sys
@@ -39,8 +45,59 @@ def run(x, gy, bn):
     return (time.perf_counter() - t0) / ITERS * 1e6
 
 
+RANGE_SHAPES = ((46080, 64), (11520, 128))
+
+
+def range_windows(m, c, ranges_list, dev):
+    from lattice_net_amd import _lib
+    lib, p = _lib.load(), _lib.ptr
+    groups = 32
+    x, gy = torch.randn((m, c), device=dev), torch.randn((m, c), device=dev)
+    w, b = torch.rand((c,), device=dev) + 0.5, torch.randn((c,), device=dev)
+    y, dx, dw, db = torch.empty_like(x), torch.empty_like(x), torch.empty_like(w), torch.empty_like(w)
+    stream = _lib.stream_ptr(dev)
+    forms = {}
+    for segs in ranges_list:  # 0: the whole matrix
+        n = max(segs, 1)
+        nbytes = int(lib.ln_group_norm_segments_workspace_bytes(c, segs) if segs else lib.ln_group_norm_workspace_bytes(c))
+        ws = [torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev) for _ in range(2)]
+        mr, ss = torch.empty((n, 2 * groups), device=dev), torch.empty((n, 2 * c), device=dev)
+        starts = torch.tensor([m * i // n for i in range(n + 1)], dtype=torch.int32, device=dev)
+        tail = (p(starts), segs, stream) if segs else (stream,)
+        fwd = lib.ln_group_norm_forward_many_segments if segs else lib.ln_group_norm_forward_rows
+        bwd = lib.ln_group_norm_backward_many_segments if segs else lib.ln_group_norm_backward_rows
+
+        def pair(ws=ws, mr=mr, ss=ss, tail=tail, fwd=fwd, bwd=bwd, nbytes=nbytes, keep=starts):
+            _lib.check(fwd(p(x), p(w), p(b), m, c, groups, 1e-5, 1, p(y), p(mr), p(ss), p(ws[0]), nbytes, p(ws[1]), nbytes, None, *tail), "forward")
+            _lib.check(bwd(p(x), p(gy), p(w), p(mr), p(ss), m, c, groups, 1, p(dx), p(dw), p(db), p(ws[1]), nbytes, p(ws[0]), nbytes, None, *tail),
+                       "backward")
+        forms[segs] = pair
+    times = {segs: [] for segs in forms}
+    for _ in range(RUNS):
+        for segs, pair in forms.items():
+            for _ in range(WARMUP):
+                pair()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(ITERS):
+                pair()
+            torch.cuda.synchronize()
+            times[segs].append((time.perf_counter() - t0) / ITERS * 1e6)
+    whole = statistics.median(times[0])
+    for segs, t in times.items():
+        t = sorted(t)
+        name = "whole matrix" if not segs else f"{segs:4d} ranges ({'slab form' if segs <= 64 else 'range owners'})"
+        print(f"GnRelu fwd+bwd [{m}, {c}] {name:28s} median {statistics.median(t):7.1f} us  fastest {t[0]:7.1f}  slowest {t[-1]:7.1f}  "
+              f"median / whole matrix {statistics.median(t) / whole:.2f}")
+
+
 def main():
     dev = torch.device("cuda", 0)
+    if "--ranges" in sys.argv:
+        ranges = [int(a) for a in sys.argv[sys.argv.index("--ranges") + 1:]]
+        for m, c in RANGE_SHAPES:
+            range_windows(m, c, [0] + ranges, dev)
+        return
     default = lattice_blocks.FUSED_BATCH_NORM
     try:
         for m, c in SHAPES:
