@@ -509,6 +509,25 @@ int ln_group_norm_backward_many_segments(const float* x, const float* grad_y, co
                                          float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
                                          size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream);
 
+/* GroupNorm per row range on fp16 matrices: ln_group_norm_forward_segments / _backward_segments argument for argument, with x, y,
+ * grad_y and grad_x pointing at IEEE half-precision elements ([m, channels], row-major).  An element is converted to fp32 as it is read
+ * (exact) and rounded to nearest-even once as it is written; everything in between — the assignment of rows to threads, the fp32 / fp64
+ * sums and their order, the statistics, the grids — is that of the fp32 call on the same numbers, so mean_rstd, scale_shift, grad_gamma
+ * and grad_beta are those of the fp32 call on the converted inputs bit for bit, and y / grad_x are its outputs rounded to fp16.  The
+ * ReLU mask of the backward call is x * a + b > 0 in fp32, not y > 0 of the rounded output.  gamma, beta, mean_rstd, scale_shift,
+ * grad_gamma, grad_beta and the workspace (ln_group_norm_segments_workspace_bytes) are what they are in the fp32 calls.  The matrices
+ * must be 8-byte aligned (LN_ERR_ARG); 1 <= segments <= 64 (there is no fp16 form of the _many_segments calls, nor of the calls over
+ * the whole matrix: one range is the whole matrix); every other limit and error code is that of the fp32 call.  A refused call launches
+ * and writes nothing. */
+int ln_group_norm_forward_segments_f16(const void* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps, int relu,
+                                       void* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
+                                       void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
+                                       int segments, void* stream);
+int ln_group_norm_backward_segments_f16(const void* x, const void* grad_y, const float* gamma, const float* mean_rstd, const float* scale_shift,
+                                        int m, int channels, int groups, int relu, void* grad_x, float* grad_gamma, float* grad_beta,
+                                        void* workspace, size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes,
+                                        const int* rows_device, const int* row_starts, int segments, void* stream);
+
 /* BatchNorm (+ optional fused ReLU) of BatchNormLatticeModule / BnReluConv (lattice_modules.py:570-583, 988-1009: torch.nn.BatchNorm1d
  * on the [m, channels] values), with the device-side row count of the _rows calls above: n = min(m, *rows_device) rows count (n = m
  * when rows_device is NULL), rows beyond n are written as zeros (y, grad_x) and contribute to nothing.

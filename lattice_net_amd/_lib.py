@@ -210,6 +210,8 @@ SIGNATURES = {
     "ln_group_norm_forward_many_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
     "ln_group_norm_backward_segments": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
     "ln_group_norm_backward_many_segments": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
+    "ln_group_norm_forward_segments_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
+    "ln_group_norm_backward_segments_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp]),
     "ln_batch_norm_workspace_bytes": (_sz, [_i]),
     "ln_batch_norm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ln_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),

@@ -39,14 +39,41 @@ __device__ __forceinline__ void ln_gn_zero_next(double* __restrict__ zero_next, 
     for (int i = (int)blockIdx.y * share + threadIdx.x; i < end; i += 256) zero_next[i] = 0.0;
 }
 
-// zeros in the rows of `out` from `live` to m_tensor, spread over the linear_blocks workgroups of the grid
-__device__ __forceinline__ void ln_gn_zero_tail(float* __restrict__ out, int live, int m_tensor, int c, long long linear_block, long long linear_blocks) {
-    const long long tensor4 = (long long)m_tensor * c / 4;  // c % 4 == 0 checked by the host
-    for (long long i = (long long)live * c / 4 + linear_block * 256 + threadIdx.x; i < tensor4; i += linear_blocks * 256)
-        reinterpret_cast<float4*>(out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+// The storage type T of the [M, C] matrices (x, y, grad_y, grad_x): float or _Float16.  Every body below reaches a matrix through these two
+// and nowhere else: the 4 channels of one thread are one 16-byte (fp32) or one 8-byte (fp16) access, `i` counting such quads from `base`.
+// An fp16 element is converted to fp32 as it is loaded (exact) and rounded to nearest-even once as it is stored; every operation in
+// between is the fp32 / fp64 one of the fp32 instance on the same numbers, in the same order (same rows per thread, same slabs, same
+// grids).  The parameters, the statistics and the workspace are fp32 / fp64 for either T.
+typedef _Float16 ln_gn_half4 __attribute__((ext_vector_type(4)));
+
+template <typename I>
+__device__ __forceinline__ const float4& ln_gn_load4(const float* base, I i) { return reinterpret_cast<const float4*>(base)[i]; }
+template <typename I>
+__device__ __forceinline__ float4 ln_gn_load4(const _Float16* base, I i) {
+    const ln_gn_half4 h = reinterpret_cast<const ln_gn_half4*>(base)[i];
+    return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
+}
+__device__ __forceinline__ void ln_gn_store4(float* base, long long i, float4 v) { reinterpret_cast<float4*>(base)[i] = v; }
+__device__ __forceinline__ void ln_gn_store4(_Float16* base, long long i, float4 v) {
+    ln_gn_half4 h;
+    h.x = (_Float16)v.x;
+    h.y = (_Float16)v.y;
+    h.z = (_Float16)v.z;
+    h.w = (_Float16)v.w;
+    reinterpret_cast<ln_gn_half4*>(base)[i] = h;
 }
 
-// gy' of the fused ReLU: the incoming gradient where the forward output x * a + b is positive, zero elsewhere (a NaN output included)
+// zeros in the rows of `out` from `live` to m_tensor, spread over the linear_blocks workgroups of the grid
+template <typename T>
+__device__ __forceinline__ void ln_gn_zero_tail(T* __restrict__ out, int live, int m_tensor, int c, long long linear_block, long long linear_blocks) {
+    const long long tensor4 = (long long)m_tensor * c / 4;  // c % 4 == 0 checked by the host
+    for (long long i = (long long)live * c / 4 + linear_block * 256 + threadIdx.x; i < tensor4; i += linear_blocks * 256)
+        ln_gn_store4(out, i, make_float4(0.f, 0.f, 0.f, 0.f));
+}
+
+// gy' of the fused ReLU: the incoming gradient where the forward output x * a + b is positive, zero elsewhere (a NaN output included).
+// The mask is decided on this fp32 value for either storage type, never on the rounded fp16 y: a positive x * a + b below half the
+// smallest fp16 subnormal is stored as y = 0 and still passes its gradient, as the fp32 instance does on the same x.
 __device__ __forceinline__ float ln_gn_masked(float g, float x, float a, float b) { return x * a + b > 0.f ? g : 0.f; }
 
 __device__ __forceinline__ void ln_gn_masked_grad(float4& g, const float4& xv, const float* s_a, const float* s_b, int col) {
@@ -62,7 +89,8 @@ __device__ __forceinline__ void ln_gn_masked_grad(float4& g, const float4& xv, c
 //   backward               : p = gy' * x, q = gy'   with gy' = gy masked by (x*a[c] + b[c] > 0) when relu
 // A thread owns one float4 (4 channels) of a row; 256 / (c/4) rows are read per pass and LN_GN_PASSES independent
 // passes are in flight per thread.  Rows from m on count nowhere; a thread with rp >= rows_per_pass has no row (zeros).
-__device__ __forceinline__ void ln_gn_thread_sums(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift,
+template <typename T>
+__device__ __forceinline__ void ln_gn_thread_sums(const T* __restrict__ x, const T* __restrict__ gy, const float* __restrict__ scale_shift,
                                                   int relu, long long r0, int m, int c, double (&pd)[4], double (&qd)[4]) {
     const int tid = threadIdx.x;
     const int quads = c >> 2;                 // c % 4 == 0, c <= 1024  ->  quads <= 256
@@ -76,7 +104,7 @@ __device__ __forceinline__ void ln_gn_thread_sums(const float* __restrict__ x, c
     if (live) {
         float4 a = p, b = p;
         // pivots: this thread's first row (with no row of its own all its terms are zero)
-        const float4 pv = r0 + rp < m ? reinterpret_cast<const float4*>(x + (r0 + rp) * c)[qi] : p;
+        const float4 pv = r0 + rp < m ? ln_gn_load4(x + (r0 + rp) * c, qi) : p;
         int n = 0;
         if (gy && relu) {
             a = reinterpret_cast<const float4*>(scale_shift)[qi];
@@ -88,8 +116,8 @@ __device__ __forceinline__ void ln_gn_thread_sums(const float* __restrict__ x, c
             const long long row = r0 + (long long)k * rows_per_pass + rp;
             const bool ok = row < m;
             n += ok;
-            xv[k] = ok ? reinterpret_cast<const float4*>(x + row * c)[qi] : pv;  // (x - p = 0 beyond the last row)
-            if (gy) gv[k] = ok ? reinterpret_cast<const float4*>(gy + row * c)[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
+            xv[k] = ok ? ln_gn_load4(x + row * c, qi) : pv;  // (x - p = 0 beyond the last row)
+            if (gy) gv[k] = ok ? ln_gn_load4(gy + row * c, qi) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int k = 0; k < LN_GN_PASSES; ++k) {
@@ -123,7 +151,8 @@ __device__ __forceinline__ void ln_gn_thread_sums(const float* __restrict__ x, c
 // acc[c*2 + 0] += sum_rows p(row, c), acc[c*2 + 1] += sum_rows q(row, c), p and q those of ln_gn_thread_sums.  The rows are
 // [row_begin, m); workgroup `block` takes the slab of rows_per_pass * LN_GN_PASSES rows that starts that many * block rows behind
 // row_begin (k_gn_stats: the whole matrix; k_gn_stats_segments: one row range of it).
-__device__ __forceinline__ void ln_gn_stats_rows(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ scale_shift,
+template <typename T>
+__device__ __forceinline__ void ln_gn_stats_rows(const T* __restrict__ x, const T* __restrict__ gy, const float* __restrict__ scale_shift,
                                                  int relu, int row_begin, int m, int c, double* __restrict__ acc, int block) {
     __shared__ double s_p[256][4], s_q[256][4];
     const int tid = threadIdx.x;
@@ -277,12 +306,13 @@ __device__ __forceinline__ void ln_gn_channel_affine(const double* __restrict__ 
 }
 
 // y = act(x * a[c] + b[c]) over the float4 [first4, last4) of the matrix, the workgroups of blockIdx.y side by side
-__device__ __forceinline__ void ln_gn_affine_rows(const float* __restrict__ x, const float* s_a, const float* s_b, long long first4, long long last4,
-                                                  int c, int relu, float* __restrict__ y) {
+template <typename T>
+__device__ __forceinline__ void ln_gn_affine_rows(const T* __restrict__ x, const float* s_a, const float* s_b, long long first4, long long last4,
+                                                  int c, int relu, T* __restrict__ y) {
     const long long stride = (long long)gridDim.x * 256;
     for (long long i = first4 + (long long)blockIdx.x * 256 + threadIdx.x; i < last4; i += stride) {
         const int col = int((i * 4) % c);
-        float4 v = reinterpret_cast<const float4*>(x)[i];
+        float4 v = ln_gn_load4(x, i);
         v.x = v.x * s_a[col] + s_b[col];
         v.y = v.y * s_a[col + 1] + s_b[col + 1];
         v.z = v.z * s_a[col + 2] + s_b[col + 2];
@@ -293,7 +323,7 @@ __device__ __forceinline__ void ln_gn_affine_rows(const float* __restrict__ x, c
             v.z = fmaxf(v.z, 0.f);
             v.w = fmaxf(v.w, 0.f);
         }
-        reinterpret_cast<float4*>(y)[i] = v;
+        ln_gn_store4(y, i, v);
     }
 }
 
@@ -301,10 +331,11 @@ __device__ __forceinline__ void ln_gn_affine_rows(const float* __restrict__ x, c
 // ln_gn_range_sums over `count` rows in LDS (s_ds, s_db: complete behind a barrier; mean_rstd, scale_shift: those of the rows in question).  The first workgroup of the rows also leaves the terms
 // of the parameter gradients in LDS, in fp64: term_gamma[col] = (ds - db*mean)*rstd, term_beta[col] = db, each written by the thread that
 // owns `col` in a loop `col = threadIdx.x; col < c; col += 256` (which may read them back without a barrier).
-__device__ __forceinline__ void ln_gn_backward_of_sums(const float* __restrict__ x, const float* __restrict__ gy, double* s_ds, double* s_db,
+template <typename T>
+__device__ __forceinline__ void ln_gn_backward_of_sums(const T* __restrict__ x, const T* __restrict__ gy, double* s_ds, double* s_db,
                                                        const float* __restrict__ gamma, const float* __restrict__ mean_rstd,
                                                        const float* __restrict__ scale_shift, int count, long long first4, long long last4, int c,
-                                                       int groups, int relu, float* __restrict__ dx, double*& term_gamma, double*& term_beta) {
+                                                       int groups, int relu, T* __restrict__ dx, double*& term_gamma, double*& term_beta) {
     __shared__ float s_gr[LN_GN_MAX_C], s_c2[LN_GN_MAX_C], s_c3[LN_GN_MAX_C], s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
     const int cg = c / groups;
     for (int col = threadIdx.x; col < c; col += 256) {
@@ -337,23 +368,24 @@ __device__ __forceinline__ void ln_gn_backward_of_sums(const float* __restrict__
     const long long stride = (long long)gridDim.x * 256;
     for (long long i = first4 + (long long)blockIdx.x * 256 + threadIdx.x; i < last4; i += stride) {
         const int col = int((i * 4) % c);
-        const float4 xv = reinterpret_cast<const float4*>(x)[i];
-        float4 g = reinterpret_cast<const float4*>(gy)[i];
+        const float4 xv = ln_gn_load4(x, i);
+        float4 g = ln_gn_load4(gy, i);
         if (relu) ln_gn_masked_grad(g, xv, s_a, s_b, col);
         float4 o;
         o.x = g.x * s_gr[col] + xv.x * s_c2[col] + s_c3[col];
         o.y = g.y * s_gr[col + 1] + xv.y * s_c2[col + 1] + s_c3[col + 1];
         o.z = g.z * s_gr[col + 2] + xv.z * s_c2[col + 2] + s_c3[col + 2];
         o.w = g.w * s_gr[col + 3] + xv.w * s_c2[col + 3] + s_c3[col + 3];
-        reinterpret_cast<float4*>(dx)[i] = o;
+        ln_gn_store4(dx, i, o);
     }
 }
 
 // ln_gn_backward_of_sums on the channel sums of the accumulator replicas
-__device__ __forceinline__ void ln_gn_backward_rows(const float* __restrict__ x, const float* __restrict__ gy, const double* __restrict__ acc,
+template <typename T>
+__device__ __forceinline__ void ln_gn_backward_rows(const T* __restrict__ x, const T* __restrict__ gy, const double* __restrict__ acc,
                                                     const float* __restrict__ gamma, const float* __restrict__ mean_rstd,
                                                     const float* __restrict__ scale_shift, int count, long long first4, long long last4, int c,
-                                                    int groups, int relu, float* __restrict__ dx, double*& term_gamma, double*& term_beta) {
+                                                    int groups, int relu, T* __restrict__ dx, double*& term_gamma, double*& term_beta) {
     __shared__ double s_ds[LN_GN_MAX_C], s_db[LN_GN_MAX_C];
     for (int col = threadIdx.x; col < c; col += 256) {
         double ds, db;
@@ -561,9 +593,22 @@ __global__ void __launch_bounds__(256)
                      blockIdx.x);
 }
 
+__global__ void __launch_bounds__(256)
+    k_gn_stats_segments_f16(const _Float16* __restrict__ x, const _Float16* __restrict__ gy, const float* __restrict__ scale_shift, int relu, int m,
+                            int c, double* __restrict__ acc, const int* __restrict__ rows_dev, const int* __restrict__ row_starts, int segments) {
+    const int s = blockIdx.y;
+    int live, lo, hi;
+    ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
+    // (the grid covers a range of m rows: the workgroups behind the end of this range, all of them for an empty one, have nothing to add)
+    if ((long long)blockIdx.x * (256 / (c >> 2)) * LN_GN_PASSES >= hi - lo) return;
+    ln_gn_stats_rows(x, gy, scale_shift ? scale_shift + (size_t)s * 2 * c : nullptr, relu, lo, hi, c, acc + (size_t)s * LN_GN_REPLICAS * 2 * c,
+                     blockIdx.x);
+}
+
 // the prologue of the two apply kernels: the next call's accumulators, and zeros in the rows behind the last range (all workgroups of the 2-D grid)
+template <typename T>
 __device__ __forceinline__ void ln_gn_segments_housekeeping(double* __restrict__ zero_next, int zero_count, int live, int m, int c,
-                                                            float* __restrict__ out) {
+                                                            T* __restrict__ out) {
     ln_gn_zero_next(zero_next, zero_count);
     ln_gn_zero_tail(out, live, m, c, (long long)blockIdx.y * gridDim.x + blockIdx.x, (long long)gridDim.x * gridDim.y);
 }
@@ -585,6 +630,23 @@ __global__ void __launch_bounds__(256)
     ln_gn_affine_rows(x, s_a, s_b, (long long)lo * c / 4, (long long)hi * c / 4, c, relu, y);
 }
 
+__global__ void __launch_bounds__(256)
+    k_gn_apply_segments_f16(const _Float16* __restrict__ x, const double* __restrict__ acc, const float* __restrict__ gamma,
+                            const float* __restrict__ beta, int m, int c, int groups, float eps, int relu, _Float16* __restrict__ y,
+                            float* __restrict__ mean_rstd, float* __restrict__ scale_shift, double* __restrict__ zero_next, int zero_count,
+                            const int* __restrict__ rows_dev, const int* __restrict__ row_starts, int segments) {
+    __shared__ float s_a[LN_GN_MAX_C], s_b[LN_GN_MAX_C];
+    const int s = blockIdx.y;
+    int live, lo, hi;
+    ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
+    ln_gn_segments_housekeeping(zero_next, zero_count, live, m, c, y);
+    if (hi == lo) return;  // an empty range: no statistics, no rows
+    ln_gn_channel_affine(acc + (size_t)s * LN_GN_REPLICAS * 2 * c, gamma, beta, hi - lo, c, groups, eps, s_a, s_b, mean_rstd + (size_t)s * 2 * groups,
+                         scale_shift + (size_t)s * 2 * c);
+    __syncthreads();
+    ln_gn_affine_rows(x, s_a, s_b, (long long)lo * c / 4, (long long)hi * c / 4, c, relu, y);
+}
+
 // ln_gn_backward_rows over range blockIdx.y.  The parameter gradients are sums over the ranges: the first workgroup of range s leaves its
 // terms in parts[s * 2 C ...], in fp64 (zeros for an empty range); k_gn_param_grads_segments adds them.
 __global__ void __launch_bounds__(256)
@@ -592,6 +654,32 @@ __global__ void __launch_bounds__(256)
                                  const float* __restrict__ gamma, const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift, int m,
                                  int c, int groups, int relu, float* __restrict__ dx, double* __restrict__ parts, double* __restrict__ zero_next,
                                  int zero_count, const int* __restrict__ rows_dev, const int* __restrict__ row_starts, int segments) {
+    const int s = blockIdx.y;
+    int live, lo, hi;
+    ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
+    ln_gn_segments_housekeeping(zero_next, zero_count, live, m, c, dx);
+    parts += (size_t)s * 2 * c;
+    if (hi == lo) {
+        if (blockIdx.x == 0)
+            for (int i = threadIdx.x; i < 2 * c; i += 256) parts[i] = 0.0;
+        return;
+    }
+    double *term_gamma, *term_beta;
+    ln_gn_backward_rows(x, gy, acc + (size_t)s * LN_GN_REPLICAS * 2 * c, gamma, mean_rstd + (size_t)s * 2 * groups, scale_shift + (size_t)s * 2 * c,
+                        hi - lo, (long long)lo * c / 4, (long long)hi * c / 4, c, groups, relu, dx, term_gamma, term_beta);
+    if (blockIdx.x == 0)
+        for (int col = threadIdx.x; col < c; col += 256) {
+            parts[col] = term_gamma[col];
+            parts[c + col] = term_beta[col];
+        }
+}
+
+__global__ void __launch_bounds__(256)
+    k_gn_backward_apply_segments_f16(const _Float16* __restrict__ x, const _Float16* __restrict__ gy, const double* __restrict__ acc,
+                                     const float* __restrict__ gamma, const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift,
+                                     int m, int c, int groups, int relu, _Float16* __restrict__ dx, double* __restrict__ parts,
+                                     double* __restrict__ zero_next, int zero_count, const int* __restrict__ rows_dev,
+                                     const int* __restrict__ row_starts, int segments) {
     const int s = blockIdx.y;
     int live, lo, hi;
     ln_gn_segment(row_starts, segments, s, m, rows_dev, live, lo, hi);
@@ -693,15 +781,21 @@ static int ln_gn_check(const char* who, int m, int c, int groups) {
     return LN_OK;
 }
 
-// The buffers of a call: its [M, C] matrices (x, y forward; x, grad_y, grad_x backward) non-null and 16-byte aligned for the float4 passes,
-// mean_rstd / scale_shift non-null, `workspace` non-null with at least `need` bytes (need == 0: a call that takes no sums and leaves
-// `workspace` alone), both workspaces 8-byte aligned.
+// The storage type of the [M, C] matrices of a call, by its element size: what the host function behind an fp32 / fp16 pair of entry
+// points is told, and what it picks the kernel instances by.
+enum LnGnStorage { LN_GN_F16 = 2, LN_GN_F32 = 4 };
+
+// The buffers of a call: its [M, C] matrices (x, y forward; x, grad_y, grad_x backward) non-null and aligned to the 4 elements a thread
+// accesses at once (16 bytes in fp32, 8 in fp16), mean_rstd / scale_shift non-null, `workspace` non-null with at least `need` bytes
+// (need == 0: a call that takes no sums and leaves `workspace` alone), both workspaces 8-byte aligned.
 static int ln_norm_check_buffers(const char* who, const void* x, const void* grad_y, const void* out, const void* mean_rstd, const void* scale_shift,
-                                 const void* workspace, size_t workspace_bytes, size_t need, const void* next_workspace, bool backward) {
+                                 const void* workspace, size_t workspace_bytes, size_t need, const void* next_workspace, bool backward,
+                                 LnGnStorage storage = LN_GN_F32) {
     LN_REQUIRE(x && out && mean_rstd && scale_shift && (grad_y || !backward), LN_ERR_ARG, "%s: null buffer", who);
     LN_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), LN_ERR_ARG, "%s: null workspace, or smaller than %zu bytes", who, need);
-    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0, LN_ERR_ARG,
-               "%s: the [rows, channels] matrices must be 16-byte aligned", who);
+    const uintptr_t align = 4 * (uintptr_t)storage;
+    LN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(out)) & (align - 1)) == 0, LN_ERR_ARG,
+               "%s: the [rows, channels] matrices must be %d-byte aligned", who, (int)align);
     LN_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(next_workspace)) & 7) == 0, LN_ERR_ARG,
                "%s: the workspaces must be 8-byte aligned", who);
     return LN_OK;
@@ -876,30 +970,43 @@ static int ln_gn_segments_check(const char* who, int m, int c, int groups, int s
 // apply grid of one range: sized for twice the mean range (the loops are grid-stride: any range is covered)
 static int ln_gn_segments_apply_grid(int m, int c, int segments) { return ln_gn_apply_grid(2 * ln_div_up(m, segments), c); }
 
-static int ln_gn_forward_segments_run(const char* who, int max_segments, const float* x, const float* gamma, const float* beta, int m, int channels, int groups,
-                                      float eps, int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
-                                      void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
-                                      int segments, void* stream) {
+// The fp32 and fp16 entry points over row ranges share one host function: `storage` says what x / y (grad_y / grad_x) point at; the
+// checks, the grids and the workspace are the same, and the kernel instance is picked at the launch.  (The fp16 entry points come with
+// max_segments = LN_GN_MAX_SEGMENTS and are refused before the range-owner branch, which has no fp16 instance.)
+static int ln_gn_forward_segments_run(const char* who, int max_segments, LnGnStorage storage, const void* x, const float* gamma, const float* beta, int m,
+                                      int channels, int groups, float eps, int relu, void* y, float* mean_rstd, float* scale_shift, void* workspace,
+                                      size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes, const int* rows_device,
+                                      const int* row_starts, int segments, void* stream) {
     int rc = ln_gn_segments_check(who, m, channels, groups, segments, max_segments, row_starts);
     if (rc) return rc;
     rc = ln_norm_check_buffers(who, x, nullptr, y, mean_rstd, scale_shift, workspace, workspace_bytes,
-                               ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, false);
+                               ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, false, storage);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
+    double* zero_next = static_cast<double*>(next_workspace);
+    const int zero_count = int(next_workspace_bytes / sizeof(double));
     if (segments > LN_GN_MAX_SEGMENTS) {  // many short ranges: one owner per range, `workspace` is not touched
-        LN_LAUNCH("k_gn_forward_range_owner", k_gn_forward_range_owner, dim3(1, segments), dim3(256), 0, st, x, gamma, beta, m, channels, groups, eps,
-                  relu, y, mean_rstd, scale_shift, static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device,
-                  row_starts, segments);
+        LN_LAUNCH("k_gn_forward_range_owner", k_gn_forward_range_owner, dim3(1, segments), dim3(256), 0, st, static_cast<const float*>(x), gamma, beta, m,
+                  channels, groups, eps, relu, static_cast<float*>(y), mean_rstd, scale_shift, zero_next, zero_count, rows_device, row_starts, segments);
         return ln_check_launch(who);
     }
     double* acc = static_cast<double*>(workspace);
     if (!next_workspace && ln_zero_async(acc, (size_t)segments * ln_group_norm_workspace_bytes(channels), st) != LN_OK)
         return ln_check_launch(who);
-    LN_LAUNCH("k_gn_stats_segments", k_gn_stats_segments, dim3(ln_gn_stats_grid(m, channels), segments), dim3(256), 0, st, x, (const float*)nullptr,
-              (const float*)nullptr, 0, m, channels, acc, rows_device, row_starts, segments);
-    LN_LAUNCH("k_gn_apply_segments", k_gn_apply_segments, dim3(ln_gn_segments_apply_grid(m, channels, segments), segments), dim3(256), 0, st, x,
-              (const double*)acc, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, static_cast<double*>(next_workspace),
-              int(next_workspace_bytes / sizeof(double)), rows_device, row_starts, segments);
+    const dim3 stats_grid(ln_gn_stats_grid(m, channels), segments), apply_grid(ln_gn_segments_apply_grid(m, channels, segments), segments);
+    if (storage == LN_GN_F16) {
+        const _Float16* xh = static_cast<const _Float16*>(x);
+        LN_LAUNCH("k_gn_stats_segments_f16", k_gn_stats_segments_f16, stats_grid, dim3(256), 0, st, xh, (const _Float16*)nullptr, (const float*)nullptr,
+                  0, m, channels, acc, rows_device, row_starts, segments);
+        LN_LAUNCH("k_gn_apply_segments_f16", k_gn_apply_segments_f16, apply_grid, dim3(256), 0, st, xh, (const double*)acc, gamma, beta, m, channels,
+                  groups, eps, relu, static_cast<_Float16*>(y), mean_rstd, scale_shift, zero_next, zero_count, rows_device, row_starts, segments);
+        return ln_check_launch(who);
+    }
+    const float* xf = static_cast<const float*>(x);
+    LN_LAUNCH("k_gn_stats_segments", k_gn_stats_segments, stats_grid, dim3(256), 0, st, xf, (const float*)nullptr, (const float*)nullptr, 0, m, channels,
+              acc, rows_device, row_starts, segments);
+    LN_LAUNCH("k_gn_apply_segments", k_gn_apply_segments, apply_grid, dim3(256), 0, st, xf, (const double*)acc, gamma, beta, m, channels, groups, eps,
+              relu, static_cast<float*>(y), mean_rstd, scale_shift, zero_next, zero_count, rows_device, row_starts, segments);
     return ln_check_launch(who);
 }
 
@@ -910,7 +1017,7 @@ extern "C" int ln_group_norm_forward_segments(const float* x, const float* gamma
                                               int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
                                               void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
                                               int segments, void* stream) {
-    return ln_gn_forward_segments_run("ln_group_norm_forward_segments", LN_GN_MAX_SEGMENTS, x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace,
+    return ln_gn_forward_segments_run("ln_group_norm_forward_segments", LN_GN_MAX_SEGMENTS, LN_GN_F32, x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace,
                                       workspace_bytes, next_workspace, next_workspace_bytes, rows_device, row_starts, segments, stream);
 }
 
@@ -918,25 +1025,36 @@ extern "C" int ln_group_norm_forward_many_segments(const float* x, const float* 
                                                    int relu, float* y, float* mean_rstd, float* scale_shift, void* workspace,
                                                    size_t workspace_bytes, void* next_workspace, size_t next_workspace_bytes,
                                                    const int* rows_device, const int* row_starts, int segments, void* stream) {
-    return ln_gn_forward_segments_run("ln_group_norm_forward_many_segments", LN_GN_MANY_MAX_SEGMENTS, x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace,
+    return ln_gn_forward_segments_run("ln_group_norm_forward_many_segments", LN_GN_MANY_MAX_SEGMENTS, LN_GN_F32, x, gamma, beta, m, channels, groups, eps, relu, y, mean_rstd, scale_shift, workspace,
                                       workspace_bytes, next_workspace, next_workspace_bytes, rows_device, row_starts, segments, stream);
 }
 
-static int ln_gn_backward_segments_run(const char* who, int max_segments, const float* x, const float* grad_y, const float* gamma, const float* mean_rstd,
-                                       const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
+extern "C" int ln_group_norm_forward_segments_f16(const void* x, const float* gamma, const float* beta, int m, int channels, int groups, float eps,
+                                                  int relu, void* y, float* mean_rstd, float* scale_shift, void* workspace, size_t workspace_bytes,
+                                                  void* next_workspace, size_t next_workspace_bytes, const int* rows_device, const int* row_starts,
+                                                  int segments, void* stream) {
+    return ln_gn_forward_segments_run("ln_group_norm_forward_segments_f16", LN_GN_MAX_SEGMENTS, LN_GN_F16, x, gamma, beta, m, channels, groups, eps, relu,
+                                      y, mean_rstd, scale_shift, workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device,
+                                      row_starts, segments, stream);
+}
+
+static int ln_gn_backward_segments_run(const char* who, int max_segments, LnGnStorage storage, const void* x, const void* grad_y, const float* gamma,
+                                       const float* mean_rstd, const float* scale_shift, int m, int channels, int groups, int relu, void* grad_x, float* grad_gamma,
                                        float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
                                        size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream) {
     int rc = ln_gn_segments_check(who, m, channels, groups, segments, max_segments, row_starts);
     if (rc) return rc;
     rc = ln_norm_check_buffers(who, x, grad_y, grad_x, mean_rstd, scale_shift, workspace, workspace_bytes,
-                               ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, true);
+                               ln_group_norm_segments_workspace_bytes(channels, segments), next_workspace, true, storage);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     double* acc = static_cast<double*>(workspace);
+    double* zero_next = static_cast<double*>(next_workspace);
+    const int zero_count = int(next_workspace_bytes / sizeof(double));
     if (segments > LN_GN_MAX_SEGMENTS) {  // many short ranges: one owner per range, the workspace is the B x 2 C terms
-        LN_LAUNCH("k_gn_backward_range_owner", k_gn_backward_range_owner, dim3(1, segments), dim3(256), 0, st, x, grad_y, gamma, mean_rstd,
-                  scale_shift, m, channels, groups, relu, grad_x, acc, static_cast<double*>(next_workspace),
-                  int(next_workspace_bytes / sizeof(double)), rows_device, row_starts, segments);
+        LN_LAUNCH("k_gn_backward_range_owner", k_gn_backward_range_owner, dim3(1, segments), dim3(256), 0, st, static_cast<const float*>(x),
+                  static_cast<const float*>(grad_y), gamma, mean_rstd, scale_shift, m, channels, groups, relu, static_cast<float*>(grad_x), acc, zero_next,
+                  zero_count, rows_device, row_starts, segments);
         if (grad_gamma || grad_beta)
             LN_LAUNCH("k_gn_param_grads_segments", k_gn_param_grads_segments, dim3(ln_div_up(2 * channels, 256)), dim3(256), 0, st,
                       (const double*)acc, segments, channels, grad_gamma, grad_beta);
@@ -945,11 +1063,22 @@ static int ln_gn_backward_segments_run(const char* who, int max_segments, const 
     const size_t slabs = (size_t)segments * ln_group_norm_workspace_bytes(channels);
     double* parts = acc + slabs / sizeof(double);
     if (!next_workspace && ln_zero_async(acc, slabs, st) != LN_OK) return ln_check_launch(who);
-    LN_LAUNCH("k_gn_stats_segments", k_gn_stats_segments, dim3(ln_gn_stats_grid(m, channels), segments), dim3(256), 0, st, x, grad_y, scale_shift, relu,
-              m, channels, acc, rows_device, row_starts, segments);
-    LN_LAUNCH("k_gn_backward_apply_segments", k_gn_backward_apply_segments, dim3(ln_gn_segments_apply_grid(m, channels, segments), segments), dim3(256),
-              0, st, x, grad_y, (const double*)acc, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x, parts,
-              static_cast<double*>(next_workspace), int(next_workspace_bytes / sizeof(double)), rows_device, row_starts, segments);
+    const dim3 stats_grid(ln_gn_stats_grid(m, channels), segments), apply_grid(ln_gn_segments_apply_grid(m, channels, segments), segments);
+    if (storage == LN_GN_F16) {
+        const _Float16 *xh = static_cast<const _Float16*>(x), *gh = static_cast<const _Float16*>(grad_y);
+        LN_LAUNCH("k_gn_stats_segments_f16", k_gn_stats_segments_f16, stats_grid, dim3(256), 0, st, xh, gh, scale_shift, relu, m, channels, acc,
+                  rows_device, row_starts, segments);
+        LN_LAUNCH("k_gn_backward_apply_segments_f16", k_gn_backward_apply_segments_f16, apply_grid, dim3(256), 0, st, xh, gh, (const double*)acc, gamma,
+                  mean_rstd, scale_shift, m, channels, groups, relu, static_cast<_Float16*>(grad_x), parts, zero_next, zero_count, rows_device,
+                  row_starts, segments);
+    } else {
+        const float *xf = static_cast<const float*>(x), *gf = static_cast<const float*>(grad_y);
+        LN_LAUNCH("k_gn_stats_segments", k_gn_stats_segments, stats_grid, dim3(256), 0, st, xf, gf, scale_shift, relu, m, channels, acc, rows_device,
+                  row_starts, segments);
+        LN_LAUNCH("k_gn_backward_apply_segments", k_gn_backward_apply_segments, apply_grid, dim3(256), 0, st, xf, gf, (const double*)acc, gamma,
+                  mean_rstd, scale_shift, m, channels, groups, relu, static_cast<float*>(grad_x), parts, zero_next, zero_count, rows_device, row_starts,
+                  segments);
+    }
     if (grad_gamma || grad_beta)
         LN_LAUNCH("k_gn_param_grads_segments", k_gn_param_grads_segments, dim3(ln_div_up(2 * channels, 256)), dim3(256), 0, st, (const double*)parts,
                   segments, channels, grad_gamma, grad_beta);
@@ -960,7 +1089,7 @@ extern "C" int ln_group_norm_backward_segments(const float* x, const float* grad
                                                const float* scale_shift, int m, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
                                                float* grad_beta, void* workspace, size_t workspace_bytes, void* next_workspace,
                                                size_t next_workspace_bytes, const int* rows_device, const int* row_starts, int segments, void* stream) {
-    return ln_gn_backward_segments_run("ln_group_norm_backward_segments", LN_GN_MAX_SEGMENTS, x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x, grad_gamma,
+    return ln_gn_backward_segments_run("ln_group_norm_backward_segments", LN_GN_MAX_SEGMENTS, LN_GN_F32, x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x, grad_gamma,
                                        grad_beta, workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device, row_starts, segments,
                                        stream);
 }
@@ -970,7 +1099,17 @@ extern "C" int ln_group_norm_backward_many_segments(const float* x, const float*
                                                     float* grad_gamma, float* grad_beta, void* workspace, size_t workspace_bytes,
                                                     void* next_workspace, size_t next_workspace_bytes, const int* rows_device,
                                                     const int* row_starts, int segments, void* stream) {
-    return ln_gn_backward_segments_run("ln_group_norm_backward_many_segments", LN_GN_MANY_MAX_SEGMENTS, x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x,
+    return ln_gn_backward_segments_run("ln_group_norm_backward_many_segments", LN_GN_MANY_MAX_SEGMENTS, LN_GN_F32, x, grad_y, gamma, mean_rstd, scale_shift, m, channels, groups, relu, grad_x,
                                        grad_gamma, grad_beta, workspace, workspace_bytes, next_workspace, next_workspace_bytes, rows_device,
                                        row_starts, segments, stream);
+}
+
+extern "C" int ln_group_norm_backward_segments_f16(const void* x, const void* grad_y, const float* gamma, const float* mean_rstd,
+                                                   const float* scale_shift, int m, int channels, int groups, int relu, void* grad_x,
+                                                   float* grad_gamma, float* grad_beta, void* workspace, size_t workspace_bytes,
+                                                   void* next_workspace, size_t next_workspace_bytes, const int* rows_device,
+                                                   const int* row_starts, int segments, void* stream) {
+    return ln_gn_backward_segments_run("ln_group_norm_backward_segments_f16", LN_GN_MAX_SEGMENTS, LN_GN_F16, x, grad_y, gamma, mean_rstd, scale_shift, m,
+                                       channels, groups, relu, grad_x, grad_gamma, grad_beta, workspace, workspace_bytes, next_workspace,
+                                       next_workspace_bytes, rows_device, row_starts, segments, stream);
 }

@@ -137,10 +137,12 @@ def _gn_check(rc: int, what: str, device, stream: int):
 
 def _gn_forward(x, weight, bias, num_groups, eps, relu, rows_dev, row_starts=None):
     """The GroupNorm forward launch, over the whole matrix or (`row_starts`) per row range: x made contiguous, y, mean_rstd [2 groups] and
-    scale_shift [2 C] (one row of each per range with `row_starts`)."""
+    scale_shift [2 C] (one row of each per range with `row_starts`).  float16 rows (per row range only) take the _f16 entry points: y is
+    float16, the parameters and the saved statistics are float32 either way."""
     lib = _lib.load()
     x = x.contiguous()
     m, c = x.shape
+    half = x.dtype == torch.float16
     ranged = row_starts is not None
     segments = int(row_starts.numel()) - 1 if ranged else 1
     y = torch.empty_like(x)
@@ -152,7 +154,8 @@ def _gn_forward(x, weight, bias, num_groups, eps, relu, rows_dev, row_starts=Non
     args = (_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), m, c, num_groups, float(eps), int(relu), _lib.ptr(y), _lib.ptr(mean_rstd),
             _lib.ptr(scale_shift), _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev))
     if ranged:
-        fn = lib.ln_group_norm_forward_many_segments if segments > DEFAULT_MAX_ROW_RANGES else lib.ln_group_norm_forward_segments
+        fn = lib.ln_group_norm_forward_segments_f16 if half else \
+            lib.ln_group_norm_forward_many_segments if segments > DEFAULT_MAX_ROW_RANGES else lib.ln_group_norm_forward_segments
         _gn_check(fn(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_forward_segments", x.device, stream)
     else:
         _gn_check(lib.ln_group_norm_forward_rows(*args, stream), "ln_group_norm_forward", x.device, stream)
@@ -162,7 +165,8 @@ def _gn_forward(x, weight, bias, num_groups, eps, relu, rows_dev, row_starts=Non
 def _gn_backward(grad_y, x, weight, mean_rstd, scale_shift, num_groups, relu, has_bias, rows_dev, row_starts=None):
     """The GroupNorm backward launch that goes with _gn_forward: grad_x, grad_weight and grad_bias (None where there is no parameter)."""
     lib = _lib.load()
-    grad_y = grad_y.contiguous()
+    half = x.dtype == torch.float16
+    grad_y = grad_y.contiguous()  # (autograd hands over a gradient of y's dtype: float16 for float16 rows)
     m, c = x.shape
     ranged = row_starts is not None
     segments = int(row_starts.numel()) - 1 if ranged else 1
@@ -175,7 +179,8 @@ def _gn_backward(grad_y, x, weight, mean_rstd, scale_shift, num_groups, relu, ha
     args = (_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(weight), _lib.ptr(mean_rstd), _lib.ptr(scale_shift), m, c, num_groups, int(relu),
             _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b), _lib.ptr(ws), ws.numel() * 8, _lib.ptr(ws_next), zero_bytes, _lib.ptr(rows_dev))
     if ranged:
-        fn = lib.ln_group_norm_backward_many_segments if segments > DEFAULT_MAX_ROW_RANGES else lib.ln_group_norm_backward_segments
+        fn = lib.ln_group_norm_backward_segments_f16 if half else \
+            lib.ln_group_norm_backward_many_segments if segments > DEFAULT_MAX_ROW_RANGES else lib.ln_group_norm_backward_segments
         _gn_check(fn(*args, _lib.ptr(row_starts), segments, stream), "ln_group_norm_backward_segments", x.device, stream)
     else:
         _gn_check(lib.ln_group_norm_backward_rows(*args, stream), "ln_group_norm_backward", x.device, stream)
@@ -333,7 +338,19 @@ def group_norm_rows(x: torch.Tensor, gn: torch.nn.GroupNorm, relu: bool = False,
     holding the number of rows that count (Lattice.rows_device(): static-rows mode, where x is taller than its lattice).
     `row_starts`: device int32 [B + 1], B <= 64, or B <= 1024 with many_ranges=True (beyond 64 ranges a kernel form made for many
     short ranges: one workgroup per range, a long range is correct and slow) — the statistics are taken per row range [row_starts[s], row_starts[s + 1]) (the
-    clouds of a batch: Lattice.cloud_row_starts(), or cloud_point_starts() for per-point rows); only the HIP kernels do that."""
+    clouds of a batch: Lattice.cloud_row_starts(), or cloud_point_starts() for per-point rows); only the HIP kernels do that.
+    float16 rows (with float32 parameters, or none) are taken with `row_starts` of up to 64 ranges and no `rows_dev`: y and grad_x are
+    float16, the statistics and the parameter gradients float32.  Every other float16 call is what it was: torch.nn.GroupNorm on the
+    transposed view, and a ValueError with `rows_dev` (DESIGN.md 4.6 says why that route is not open)."""
+    if x.dtype == torch.float16 and row_starts is not None and row_starts.numel() > DEFAULT_MAX_ROW_RANGES + 1:
+        # (shapes and dtypes only: raised before anything is asked of a device or of the library)
+        raise ValueError(f"GroupNorm per row range on float16 rows takes at most {DEFAULT_MAX_ROW_RANGES} ranges (got "
+                         f"{row_starts.numel() - 1}): the kernel form for more ranges exists for float32 rows only")
+    if x.is_cuda and x.dtype == torch.float16 and x.shape[1] % 4 == 0 and x.shape[1] <= 1024 and x.shape[0] > 0 and rows_dev is None and \
+            row_starts is not None and (gn.weight is None or gn.weight.dtype == torch.float32):
+        if row_starts.dtype != torch.int32 or row_starts.device != x.device or not row_starts.is_contiguous() or row_starts.numel() < 2:
+            raise ValueError("GroupNorm per row range needs a contiguous int32 row_starts [B + 1] on the device of the rows")
+        return GroupNormSegmentsFunction.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, relu, None, row_starts)
     native = x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.shape[1] <= 1024 and x.shape[0] > 0
     if row_starts is not None:
         limit = MAX_ROW_RANGES if many_ranges else DEFAULT_MAX_ROW_RANGES

@@ -12,7 +12,11 @@ either path's work and of no consequence here.)
 (ln_group_norm_forward_many_segments / _backward_many_segments: up to 64 ranges the accumulator-slab kernels, beyond one workgroup per
 range) against the whole-matrix GroupNorm on the same tensor, through the C ABI on buffers allocated once, the alternating accumulator
 pair as the modules use it.  A window is 200 forward + backward pairs queued between two device synchronisations, divided by 200: the
-kernels of a pair when they take longer than their launches.  Five windows of each form, alternating; median, fastest and slowest."""
+kernels of a pair when they take longer than their launches.  Five windows of each form, alternating; median, fastest and slowest.
+
+--f16: GroupNorm + ReLU forward + backward per row range (4 equal ranges) at [46 500, 64] and [120 000, 32] through the C ABI, windows as
+for --ranges: the fp16 kernels (ln_group_norm_forward_segments_f16 / _backward_segments_f16) next to the fp32 kernels on the same numbers,
+and the ratio of their medians."""
 import os
 import statistics
 import sys
@@ -91,8 +95,54 @@ def range_windows(m, c, ranges_list, dev):
               f"median / whole matrix {statistics.median(t) / whole:.2f}")
 
 
+def f16_windows(m, c, dev):
+    """C ABI, 4 equal row ranges: fp16 kernels against fp32 kernels on the same numbers."""
+    from lattice_net_amd import _lib
+    lib, p = _lib.load(), _lib.ptr
+    groups = 32
+    x32, gy32 = torch.randn((m, c), device=dev).half().float(), torch.randn((m, c), device=dev).half().float()
+    w, b = torch.rand((c,), device=dev) + 0.5, torch.randn((c,), device=dev)
+    dw, db = torch.empty_like(w), torch.empty_like(w)
+    segs = 4
+    mr, ss = torch.empty((segs, 2 * groups), device=dev), torch.empty((segs, 2 * c), device=dev)
+    starts = torch.tensor([m * i // segs for i in range(segs + 1)], dtype=torch.int32, device=dev)
+    nbytes = int(lib.ln_group_norm_segments_workspace_bytes(c, segs))
+    ws = [torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev) for _ in range(2)]
+    stream = _lib.stream_ptr(dev)
+    forms = {}
+    for name, dtype, fwd, bwd in (("fp32 kernels", torch.float32, lib.ln_group_norm_forward_segments, lib.ln_group_norm_backward_segments),
+                                  ("fp16 kernels", torch.float16, lib.ln_group_norm_forward_segments_f16, lib.ln_group_norm_backward_segments_f16)):
+        x, gy = x32.to(dtype), gy32.to(dtype)
+        y, dx = torch.empty_like(x), torch.empty_like(x)
+
+        def pair(x=x, gy=gy, y=y, dx=dx, fwd=fwd, bwd=bwd):
+            _lib.check(fwd(p(x), p(w), p(b), m, c, groups, 1e-5, 1, p(y), p(mr), p(ss), p(ws[0]), nbytes, p(ws[1]), nbytes, None, p(starts), segs, stream), "forward")
+            _lib.check(bwd(p(x), p(gy), p(w), p(mr), p(ss), m, c, groups, 1, p(dx), p(dw), p(db), p(ws[1]), nbytes, p(ws[0]), nbytes, None, p(starts), segs, stream),
+                       "backward")
+        forms[name] = pair
+    times = {name: [] for name in forms}
+    for _ in range(RUNS):
+        for name, pair in forms.items():
+            for _ in range(WARMUP):
+                pair()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(ITERS):
+                pair()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / ITERS * 1e6)
+    for name, t in times.items():
+        t = sorted(t)
+        print(f"GnRelu fwd+bwd [{m}, {c}] 4 ranges, C ABI {name}  median {statistics.median(t):7.1f} us  fastest {t[0]:7.1f}  slowest {t[-1]:7.1f}")
+    print(f"GnRelu fwd+bwd [{m}, {c}] 4 ranges, C ABI fp16 / fp32 medians {statistics.median(times['fp16 kernels']) / statistics.median(times['fp32 kernels']):.2f}")
+
+
 def main():
     dev = torch.device("cuda", 0)
+    if "--f16" in sys.argv:
+        for m, c in SHAPES:
+            f16_windows(m, c, dev)
+        return
     if "--ranges" in sys.argv:
         ranges = [int(a) for a in sys.argv[sys.argv.index("--ranges") + 1:]]
         for m, c in RANGE_SHAPES:
