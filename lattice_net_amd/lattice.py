@@ -1025,6 +1025,8 @@ class Lattice:
     def _scatter_rows(self, src: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, dst: torch.Tensor, val_dim: int, src_div: int,
                       src_stride: int):
         """dst[row] += sum of the row's contributions (segment-balanced reduce over the CSR adjacency); dst pre-zeroed."""
+        if idx.numel() == 0:
+            return  # no token (a slice / gather of zero points): nothing to add, and no source row the C call could be handed
         _, csr, max_seg, grp_row, _ = self._csr(idx)
         csr.dense = self._dense_hint(idx.numel())
         lib = _lib.load()
