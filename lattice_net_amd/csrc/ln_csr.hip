@@ -801,6 +801,10 @@ __device__ __forceinline__ float ln_ordered_to_float(unsigned int o) {
     return __uint_as_float(u);
 }
 
+// value and token of a packed maximum (k_csr_segment_max: ordered value in the high word, ~token in the low word)
+__device__ __forceinline__ float ln_packed_value(unsigned long long p) { return ln_ordered_to_float((unsigned int)(p >> 32)); }
+__device__ __forceinline__ int ln_packed_token(unsigned long long p) { return int(0xFFFFFFFFu - (unsigned int)(p & 0xFFFFFFFFull)); }
+
 // one lane per (segment, channel): running max over <=16 tokens; value and token are packed into 64 bits
 // (ordered value in the high word, ~token in the low word -> ties go to the smallest token) so that the
 // segments of a hot vertex combine with one 64-bit atomicMax.
@@ -944,8 +948,8 @@ __global__ void __launch_bounds__(256)
         out_max[g] = 0.f;
         out_arg[g] = -1;
     } else {
-        out_max[g] = ln_ordered_to_float((unsigned int)(p >> 32));
-        out_arg[g] = int(0xFFFFFFFFu - (unsigned int)(p & 0xFFFFFFFFull));
+        out_max[g] = ln_packed_value(p);
+        out_arg[g] = ln_packed_token(p);
     }
 }
 
@@ -986,24 +990,41 @@ extern "C" int ln_csr_segment_max(const LnCsr* csr, const int* grp_row, long lon
 //   out[row, :C]  = max over the row's tokens of src[t, :C]            out[row, C:] = bary[argmax token]
 //   rows with fewer than `min_points` tokens and row 0 (the "invalid" bucket) are zero; arg = -1 there and where no token is
 // (the reference: scatter_max, scatter_add of ones, index_select, cat, masked_fill, a multiplication by a keep mask).
-__global__ void __launch_bounds__(256)
-    k_pointnet_reduce_decode(const unsigned long long* __restrict__ packed, const int* __restrict__ counts, const float* __restrict__ bary,
-                             int bary_stride, long long work, int channels, int min_points, float* __restrict__ out, int* __restrict__ out_arg) {
-    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= work) return;
+// The decode step of element g = row * channels + c is ln_pointnet_decode_tail for all three kernels below; they differ in INVALID, how
+// a row is found to be a dropped "invalid" vertex (asked only where the element holds a maximum): row 0, or a mark in LDS.
+struct LnRowZeroInvalid {
+    __device__ bool operator()(long long row) const { return row == 0; }
+};
+struct LnMarkedInvalid {  // marks[i] (LDS, one byte for each of the workgroup's <= 256 rows): row row0 + i is the first vertex of a cloud
+    const unsigned char* marks;
+    long long row0;
+    __device__ bool operator()(long long row) const { return marks[row - row0] != 0; }
+};
+template <class INVALID>
+__device__ __forceinline__ void ln_pointnet_decode_tail(const unsigned long long* __restrict__ packed, const int* __restrict__ counts,
+                                                        const float* __restrict__ bary, int bary_stride, long long g, INVALID invalid,
+                                                        int channels, int min_points, float* __restrict__ out, int* __restrict__ out_arg) {
     const long long row = g / channels;
     const int c = int(g - row * channels);
     const unsigned long long p = packed[g];
     float mx = 0.f, bw = 0.f;
     int arg = -1;
-    if (p != 0ull && row != 0 && counts[row] >= min_points) {
-        mx = ln_ordered_to_float((unsigned int)(p >> 32));
-        arg = int(0xFFFFFFFFu - (unsigned int)(p & 0xFFFFFFFFull));
+    if (p != 0ull && !invalid(row) && counts[row] >= min_points) {
+        mx = ln_packed_value(p);
+        arg = ln_packed_token(p);
         bw = bary[(size_t)arg * bary_stride];
     }
     out[row * 2 * channels + c] = mx;
     out[row * 2 * channels + channels + c] = bw;
     out_arg[g] = arg;
+}
+
+__global__ void __launch_bounds__(256)
+    k_pointnet_reduce_decode(const unsigned long long* __restrict__ packed, const int* __restrict__ counts, const float* __restrict__ bary,
+                             int bary_stride, long long work, int channels, int min_points, float* __restrict__ out, int* __restrict__ out_arg) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= work) return;
+    ln_pointnet_decode_tail(packed, counts, bary, bary_stride, g, LnRowZeroInvalid{}, channels, min_points, out, out_arg);
 }
 
 // The decode step for a batch of clouds in one table: the dropped "invalid" vertex is the first vertex of EVERY cloud — row r with
@@ -1028,19 +1049,7 @@ __global__ void __launch_bounds__(256)
     __syncthreads();
     const long long g = g0 + threadIdx.x;
     if (g >= work) return;
-    const long long row = g / channels;
-    const int c = int(g - row * channels);
-    const unsigned long long p = packed[g];
-    float mx = 0.f, bw = 0.f;
-    int arg = -1;
-    if (p != 0ull && !s_invalid[row - row0] && counts[row] >= min_points) {
-        mx = ln_ordered_to_float((unsigned int)(p >> 32));
-        arg = int(0xFFFFFFFFu - (unsigned int)(p & 0xFFFFFFFFull));
-        bw = bary[(size_t)arg * bary_stride];
-    }
-    out[row * 2 * channels + c] = mx;
-    out[row * 2 * channels + channels + c] = bw;
-    out_arg[g] = arg;
+    ln_pointnet_decode_tail(packed, counts, bary, bary_stride, g, LnMarkedInvalid{s_invalid, row0}, channels, min_points, out, out_arg);
 }
 
 // The same step for LN_CLOUDS_MAX < clouds <= LN_CLOUDS_MANY_MAX: the LDS copy holds up to 1025 starts, filled by a strided loop, and
@@ -1071,19 +1080,7 @@ __global__ void __launch_bounds__(256)
     __syncthreads();
     const long long g = g0 + threadIdx.x;
     if (g >= work) return;
-    const long long row = g / channels;
-    const int c = int(g - row * channels);
-    const unsigned long long p = packed[g];
-    float mx = 0.f, bw = 0.f;
-    int arg = -1;
-    if (p != 0ull && !s_invalid[row - row0] && counts[row] >= min_points) {
-        mx = ln_ordered_to_float((unsigned int)(p >> 32));
-        arg = int(0xFFFFFFFFu - (unsigned int)(p & 0xFFFFFFFFull));
-        bw = bary[(size_t)arg * bary_stride];
-    }
-    out[row * 2 * channels + c] = mx;
-    out[row * 2 * channels + channels + c] = bw;
-    out_arg[g] = arg;
+    ln_pointnet_decode_tail(packed, counts, bary, bary_stride, g, LnMarkedInvalid{s_invalid, row0}, channels, min_points, out, out_arg);
 }
 
 // gradient of the maxima wrt the per-token rows, token-major (every element written: no zero fill, no scatter):

@@ -232,35 +232,34 @@ struct LnDiceLayout {
     int grid_tiles;
     size_t partial, terms, bytes;
 };
-// total: any argument gives a layout (ln_cloud_split)
-LnDiceLayout ln_dice_layout(long long n, long long points_per_cloud, int classes) {
-    LnDiceLayout L;
-    const LnCloudSplit S = ln_cloud_split(n < (1ll << 31) ? n : 1ll << 31, points_per_cloud);  // (2^31 rows and more are refused: any size will do)
-    const size_t B = size_t(S.clouds);
+// grid and workspace of a layout whose n0 and clouds are set: the grid by n0 (at least min_tiles), [clouds, grid_tiles, 3, C] partials,
+// then [clouds, C] terms
+LnDiceLayout ln_dice_layout_bytes(LnDiceLayout L, int classes, int min_tiles) {
+    const size_t B = size_t(L.clouds);
     const int Cc = classes < 1 ? 1 : (classes > LN_DICE_MAX_CLASSES ? LN_DICE_MAX_CLASSES : classes);
-    L.n0 = S.n0;
-    L.clouds = S.clouds;
     L.grid_tiles = ln_dice_grid_tiles(L.n0, Cc);
+    if (L.grid_tiles < min_tiles) L.grid_tiles = min_tiles;
     L.partial = 0;
     L.terms = (B * size_t(L.grid_tiles) * 3 * size_t(Cc) * 4 + 255) & ~size_t(255);
     L.bytes = ((L.terms + B * size_t(Cc) * 4 + 255) & ~size_t(255)) + 256;
     return L;
+}
+// total: any argument gives a layout (ln_cloud_split)
+LnDiceLayout ln_dice_layout(long long n, long long points_per_cloud, int classes) {
+    LnDiceLayout L;
+    const LnCloudSplit S = ln_cloud_split(n < (1ll << 31) ? n : 1ll << 31, points_per_cloud);  // (2^31 rows and more are refused: any size will do)
+    L.n0 = S.n0;
+    L.clouds = S.clouds;
+    return ln_dice_layout_bytes(L, classes, 0);
 }
 // The layout of a listed batch (ln_loss_common.h, LnCloudsListed): the grid and the stride of a cloud's partials by the longest cloud, at
 // least one tile (a batch of empty clouds still runs the finish).  Total: clouds is brought into [1, LN_DICE_MAX_CLOUDS], longest into [0, n].
 LnDiceLayout ln_dice_layout_ranges(long long n, long long clouds, long long longest, int classes) {
     LnDiceLayout L;
     const long long N = n < 0 ? 0 : (n < (1ll << 31) ? n : 1ll << 31);
-    const int Cc = classes < 1 ? 1 : (classes > LN_DICE_MAX_CLASSES ? LN_DICE_MAX_CLASSES : classes);
     L.n0 = longest < 0 ? 0 : (longest > N ? N : longest);
     L.clouds = clouds < 1 ? 1 : (clouds > LN_DICE_MAX_CLOUDS ? LN_DICE_MAX_CLOUDS : clouds);
-    const size_t B = size_t(L.clouds);
-    L.grid_tiles = ln_dice_grid_tiles(L.n0, Cc);
-    if (L.grid_tiles < 1) L.grid_tiles = 1;
-    L.partial = 0;
-    L.terms = (B * size_t(L.grid_tiles) * 3 * size_t(Cc) * 4 + 255) & ~size_t(255);
-    L.bytes = ((L.terms + B * size_t(Cc) * 4 + 255) & ~size_t(255)) + 256;
-    return L;
+    return ln_dice_layout_bytes(L, classes, 1);
 }
 int ln_dice_sizes_ranges(const char* who, long long n, const int* point_starts, int clouds, long long longest, int classes, LnDiceLayout& L) {
     LN_REQUIRE(n >= 0 && classes >= 1 && classes <= LN_DICE_MAX_CLASSES, LN_ERR_ARG, "%s: bad sizes (n >= 0, 1 <= classes <= %d)", who,
@@ -280,6 +279,34 @@ int ln_dice_sizes(const char* who, long long n, long long points_per_cloud, int 
                L.clouds, LN_DICE_MAX_CLOUDS);
     return LN_OK;
 }
+// The launch sequences, once for either cut (ln_loss_common.h): CUT = long long (n0) with CLOUD_OF = int (n0), or LnCloudsListed with
+// LnCloudOfRowListed.
+template <class CUT>
+int ln_dice_forward_run(const char* who, const float* log_probs, const long long* target, long long n, CUT cut, const LnDiceLayout& L, int classes,
+                        long long ignore_index, void* workspace, size_t workspace_bytes, float* loss, float* per_cloud, float* stats, float* coef,
+                        hipStream_t st) {
+    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "%s: null / small workspace (%zu bytes needed)", who, L.bytes);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* partial = reinterpret_cast<uint32_t*>(ws + L.partial);
+    float* terms = reinterpret_cast<float*>(ws + L.terms);
+    const dim3 grid(L.grid_tiles, (unsigned)L.clouds), thr(LN_DICE_THREADS);
+    if (classes <= LN_DICE_THREADS)
+        LN_LAUNCH("k_dice_partials", (k_dice_partials<false, CUT>), grid, thr, 0, st, log_probs, target, n, cut, classes, partial);
+    else
+        LN_LAUNCH("k_dice_partials", (k_dice_partials<true, CUT>), grid, thr, 0, st, log_probs, target, n, cut, classes, partial);
+    LN_LAUNCH("k_dice_finish", k_dice_finish<CUT>, dim3(1), thr, 0, st, partial, n, cut, classes, int(L.clouds), L.grid_tiles, ignore_index, terms, loss,
+              per_cloud, stats, coef);
+    return ln_check_launch(who);
+}
+template <class CLOUD_OF>
+int ln_dice_backward_run(const char* who, const float* log_probs, const long long* target, const float* coef, const float* grad_loss, long long n,
+                         CLOUD_OF cloud_of, int classes, float* grad_log_probs, void* stream) {
+    if (n == 0) return LN_OK;
+    LN_REQUIRE(log_probs && target && coef && grad_loss && grad_log_probs, LN_ERR_ARG, "%s: null buffer", who);
+    LN_LAUNCH("k_dice_backward", k_dice_backward<CLOUD_OF>, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, log_probs, target, coef,
+              grad_loss, int(n * classes), cloud_of, classes, grad_log_probs);
+    return ln_check_launch(who);
+}
 }  // namespace
 
 extern "C" size_t ln_dice_workspace_bytes(long long n, long long points_per_cloud, int classes) {
@@ -293,21 +320,10 @@ extern "C" int ln_dice_forward(const float* log_probs, const long long* target, 
     const int rc = ln_dice_sizes("ln_dice_forward", n, points_per_cloud, classes, L);
     if (rc != LN_OK) return rc;
     LN_REQUIRE(loss, LN_ERR_ARG, "ln_dice_forward: null buffer");
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) return ln_zero_async(loss, sizeof(float), st);  // no cloud: the loss is 0; per_cloud, stats and coef have no element
+    if (n == 0) return ln_zero_async(loss, sizeof(float), (hipStream_t)stream);  // no cloud: the loss is 0; per_cloud, stats and coef have no element
     LN_REQUIRE(log_probs && target && coef, LN_ERR_ARG, "ln_dice_forward: null buffer");
-    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_dice_forward: null / small workspace (%zu bytes needed)", L.bytes);
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* partial = reinterpret_cast<uint32_t*>(ws + L.partial);
-    float* terms = reinterpret_cast<float*>(ws + L.terms);
-    const dim3 grid(L.grid_tiles, (unsigned)L.clouds), thr(LN_DICE_THREADS);
-    if (classes <= LN_DICE_THREADS)
-        LN_LAUNCH("k_dice_partials", (k_dice_partials<false, long long>), grid, thr, 0, st, log_probs, target, n, L.n0, classes, partial);
-    else
-        LN_LAUNCH("k_dice_partials", (k_dice_partials<true, long long>), grid, thr, 0, st, log_probs, target, n, L.n0, classes, partial);
-    LN_LAUNCH("k_dice_finish", k_dice_finish<long long>, dim3(1), thr, 0, st, partial, n, L.n0, classes, int(L.clouds), L.grid_tiles, ignore_index, terms,
-              loss, per_cloud, stats, coef);
-    return ln_check_launch("ln_dice_forward");
+    return ln_dice_forward_run("ln_dice_forward", log_probs, target, n, L.n0, L, classes, ignore_index, workspace, workspace_bytes, loss, per_cloud,
+                               stats, coef, (hipStream_t)stream);
 }
 
 extern "C" int ln_dice_backward(const float* log_probs, const long long* target, const float* coef, const float* grad_loss, long long n,
@@ -315,11 +331,7 @@ extern "C" int ln_dice_backward(const float* log_probs, const long long* target,
     LnDiceLayout L;
     const int rc = ln_dice_sizes("ln_dice_backward", n, points_per_cloud, classes, L);
     if (rc != LN_OK) return rc;
-    if (n == 0) return LN_OK;
-    LN_REQUIRE(log_probs && target && coef && grad_loss && grad_log_probs, LN_ERR_ARG, "ln_dice_backward: null buffer");
-    LN_LAUNCH("k_dice_backward", k_dice_backward<int>, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, log_probs, target, coef,
-              grad_loss, int(n * classes), int(L.n0), classes, grad_log_probs);
-    return ln_check_launch("ln_dice_backward");
+    return ln_dice_backward_run("ln_dice_backward", log_probs, target, coef, grad_loss, n, int(L.n0), classes, grad_log_probs, stream);
 }
 
 // Clouds of unequal sizes: the rows of cloud b from point_starts.
@@ -335,20 +347,8 @@ extern "C" int ln_dice_forward_ranges(const float* log_probs, const long long* t
     if (rc != LN_OK) return rc;
     LN_REQUIRE(loss && coef, LN_ERR_ARG, "ln_dice_forward_ranges: null buffer");
     LN_REQUIRE(n == 0 || (log_probs && target), LN_ERR_ARG, "ln_dice_forward_ranges: null buffer");
-    LN_REQUIRE(workspace && workspace_bytes >= L.bytes, LN_ERR_ARG, "ln_dice_forward_ranges: null / small workspace (%zu bytes needed)", L.bytes);
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* partial = reinterpret_cast<uint32_t*>(ws + L.partial);
-    float* terms = reinterpret_cast<float*>(ws + L.terms);
-    const LnCloudsListed cut{point_starts, L.n0};
-    const dim3 grid(L.grid_tiles, (unsigned)L.clouds), thr(LN_DICE_THREADS);
-    if (classes <= LN_DICE_THREADS)
-        LN_LAUNCH("k_dice_partials", (k_dice_partials<false, LnCloudsListed>), grid, thr, 0, st, log_probs, target, n, cut, classes, partial);
-    else
-        LN_LAUNCH("k_dice_partials", (k_dice_partials<true, LnCloudsListed>), grid, thr, 0, st, log_probs, target, n, cut, classes, partial);
-    LN_LAUNCH("k_dice_finish", k_dice_finish<LnCloudsListed>, dim3(1), thr, 0, st, partial, n, cut, classes, int(L.clouds), L.grid_tiles, ignore_index, terms, loss,
-              per_cloud, stats, coef);
-    return ln_check_launch("ln_dice_forward_ranges");
+    return ln_dice_forward_run("ln_dice_forward_ranges", log_probs, target, n, LnCloudsListed{point_starts, L.n0}, L, classes, ignore_index, workspace,
+                               workspace_bytes, loss, per_cloud, stats, coef, (hipStream_t)stream);
 }
 
 extern "C" int ln_dice_backward_ranges(const float* log_probs, const long long* target, const float* coef, const float* grad_loss, long long n,
@@ -357,9 +357,6 @@ extern "C" int ln_dice_backward_ranges(const float* log_probs, const long long* 
     LnDiceLayout L;
     const int rc = ln_dice_sizes_ranges("ln_dice_backward_ranges", n, point_starts, clouds, longest, classes, L);
     if (rc != LN_OK) return rc;
-    if (n == 0) return LN_OK;
-    LN_REQUIRE(log_probs && target && coef && grad_loss && grad_log_probs, LN_ERR_ARG, "ln_dice_backward_ranges: null buffer");
-    LN_LAUNCH("k_dice_backward", k_dice_backward<LnCloudOfRowListed>, dim3(ln_div_up(n * classes, 256)), dim3(256), 0, (hipStream_t)stream, log_probs, target,
-              coef, grad_loss, int(n * classes), LnCloudOfRowListed{point_starts, clouds}, classes, grad_log_probs);
-    return ln_check_launch("ln_dice_backward_ranges");
+    return ln_dice_backward_run("ln_dice_backward_ranges", log_probs, target, coef, grad_loss, n, LnCloudOfRowListed{point_starts, clouds}, classes,
+                                grad_log_probs, stream);
 }

@@ -127,21 +127,84 @@ extern "C" int ln_weight_norm_backward(const float* v, const float* g, const flo
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// thread = (token, column); 256 threads walk consecutive elements of out (coalesced); the per-vertex rows come from L2
+// thread = (token, column); 256 threads walk consecutive elements of out (coalesced); the per-vertex rows come from L2.
+// One body for the three kernels: IDX is int when every element index fits 31 bits (32-bit divisions), else long long, and FIRST names
+// the "invalid" vertex of token t, whose tokens are zeroed with those that found no vertex — the first row of the token's cloud.  The
+// cloud comes from t alone (cloud_of); its first row is read only for a token that found a vertex (first_row):
+//  * LnFirstRowZero: no batch, row 0 of the table.
+//  * LnFirstRowEqualClouds: a batch of clouds in one table (LnTable.batch_points); the first vertex of EVERY cloud is invalid,
+//    row_starts[cloud] (ln_cloud_row_starts), and token t belongs to cloud min(t / tokens_per_cloud, clouds - 1).  A wave reads one or
+//    two of the at most 1025 ints: one cache line.
+//    (Measured and dropped: row_starts in LDS behind a barrier, and cloud / boundary / first rows computed once per workgroup — both slower.)
+//  * LnFirstRowListedClouds: clouds of unequal sizes (LnTableClouds.batch_point_starts); the cloud of token t is that of its point
+//    t / tokens_per_point, found by the binary search of the key pass (ln_cloud_of_point: reads inside the list and returns a cloud in
+//    [0, clouds) whatever the list holds).
+struct LnFirstRowZero {
+    template <typename IDX> __device__ __forceinline__ int cloud_of(IDX) const { return 0; }
+    __device__ __forceinline__ int first_row(int) const { return 0; }
+};
+struct LnFirstRowEqualClouds {
+    long long tokens_per_cloud;
+    const int* row_starts;
+    int clouds;
+    template <typename IDX> __device__ __forceinline__ int cloud_of(IDX t) const {
+        const IDX cloud = t / (IDX)tokens_per_cloud;
+        return cloud < (IDX)(clouds - 1) ? (int)cloud : clouds - 1;
+    }
+    __device__ __forceinline__ int first_row(int cloud) const { return row_starts[cloud]; }
+};
+struct LnFirstRowListedClouds {
+    int tokens_per_point;
+    const int* point_starts;
+    const int* row_starts;
+    int clouds;
+    template <typename IDX> __device__ __forceinline__ int cloud_of(IDX t) const {
+        return ln_cloud_of_point(point_starts, clouds, int(t / (IDX)tokens_per_point));
+    }
+    __device__ __forceinline__ int first_row(int cloud) const { return row_starts[cloud]; }
+};
+
+template <typename IDX, class FIRST>
+__device__ __forceinline__ void ln_distribute_centre_body(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
+                                                          const int* __restrict__ counts, long long tokens, int width, int pos_dim, FIRST first,
+                                                          float* __restrict__ out) {
+    const long long i64 = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i64 >= tokens * width) return;
+    const IDX i = (IDX)i64;
+    const IDX t = i / (IDX)width;
+    const int c = int(i - t * (IDX)width);
+    const int cloud = first.cloud_of(t);
+    const int row = idx[t];
+    float x = 0.f;
+    if (row >= 0 && row != first.first_row(cloud)) {
+        x = d[i64];
+        if (c < pos_dim) x -= sums[(size_t)row * pos_dim + c] / (float)max(counts[row], 1);
+    }
+    out[i64] = x;
+}
+
 __global__ void __launch_bounds__(256)
     k_distribute_centre(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
                         const int* __restrict__ counts, long long tokens, int width, int pos_dim, float* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= tokens * width) return;
-    const long long t = i / width;
-    const int c = int(i - t * width);
-    const int row = idx[t];
-    float x = 0.f;
-    if (row > 0) {
-        x = d[i];
-        if (c < pos_dim) x -= sums[(size_t)row * pos_dim + c] / (float)max(counts[row], 1);
-    }
-    out[i] = x;
+    ln_distribute_centre_body<long long>(d, idx, sums, counts, tokens, width, pos_dim, LnFirstRowZero{}, out);
+}
+
+template <typename IDX>
+__global__ void __launch_bounds__(256)
+    k_distribute_centre_clouds(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
+                               const int* __restrict__ counts, long long tokens, int width, int pos_dim, long long tokens_per_cloud,
+                               const int* __restrict__ row_starts, int clouds, float* __restrict__ out) {
+    ln_distribute_centre_body<IDX>(d, idx, sums, counts, tokens, width, pos_dim, LnFirstRowEqualClouds{tokens_per_cloud, row_starts, clouds}, out);
+}
+
+template <typename IDX>
+__global__ void __launch_bounds__(256)
+    k_distribute_centre_cloud_starts(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
+                                     const int* __restrict__ counts, long long tokens, int width, int pos_dim, int tokens_per_point,
+                                     const int* __restrict__ point_starts, const int* __restrict__ row_starts, int clouds,
+                                     float* __restrict__ out) {
+    ln_distribute_centre_body<IDX>(d, idx, sums, counts, tokens, width, pos_dim,
+                                   LnFirstRowListedClouds{tokens_per_point, point_starts, row_starts, clouds}, out);
 }
 
 extern "C" int ln_distribute_centre(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
@@ -154,121 +217,55 @@ extern "C" int ln_distribute_centre(const float* distributed, const int* splat_i
     return ln_check_launch("ln_distribute_centre");
 }
 
-// The same pass for a batch of clouds in one table (LnTable.batch_points): the "invalid" vertex of the reference is the first vertex of
-// EVERY cloud, row_starts[cloud] (ln_cloud_row_starts), not row 0 of the table.  Token t belongs to cloud min(t / tokens_per_cloud,
-// clouds - 1).  row_starts[cloud] is addressed from t alone, so its load is in flight beside idx[t] (a wave reads one or two of the at
-// most 1025 ints: one cache line).  IDX: int when every element index fits 31 bits (32-bit divisions), else long long.
-// (Measured and dropped: row_starts in LDS behind a barrier, and cloud / boundary / first rows computed once per workgroup — both slower.)
-template <typename IDX>
-__global__ void __launch_bounds__(256)
-    k_distribute_centre_clouds(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
-                               const int* __restrict__ counts, long long tokens, int width, int pos_dim, long long tokens_per_cloud,
-                               const int* __restrict__ row_starts, int clouds, float* __restrict__ out) {
-    const long long i64 = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i64 >= tokens * width) return;
-    const IDX i = (IDX)i64;
-    const IDX t = i / (IDX)width;
-    const int c = int(i - t * (IDX)width);
-    const IDX cloud = t / (IDX)tokens_per_cloud;
-    const int first = row_starts[cloud < (IDX)(clouds - 1) ? (int)cloud : clouds - 1];
-    const int row = idx[t];
-    float x = 0.f;
-    if (row >= 0 && row != first) {
-        x = d[i64];
-        if (c < pos_dim) x -= sums[(size_t)row * pos_dim + c] / (float)max(counts[row], 1);
-    }
-    out[i64] = x;
-}
-
-static int ln_distribute_centre_clouds_run(const char* who, int max_clouds, const float* distributed, const int* splat_idx, const float* position_sums,
-                                           const int* counts, long long tokens, int width, int pos_dim, long long tokens_per_cloud,
-                                           const int* row_starts, int clouds, float* out, void* stream) {
-    LN_REQUIRE(tokens >= 0 && width >= 1 && pos_dim >= 0 && pos_dim <= width && tokens_per_cloud >= 1, LN_ERR_ARG,
-               "%s: bad sizes", who);
-    LN_REQUIRE(clouds >= 1 && clouds <= max_clouds, LN_ERR_UNSUPPORTED, "%s: 1 <= clouds <= %d (got %d)", who, max_clouds,
-               clouds);
+// The four cloud entry points: `per` is tokens_per_cloud, or for the entry points that take a list of point starts (`listed`) tokens_per_point.
+// The kernels read the starts from global memory, any number of them: the plain and the _many entry points differ in the limit they check.
+static int ln_distribute_centre_clouds_run(const char* who, int max_clouds, bool listed, const float* distributed, const int* splat_idx,
+                                           const float* position_sums, const int* counts, long long tokens, int width, int pos_dim, long long per,
+                                           const int* point_starts, const int* row_starts, int clouds, float* out, void* stream) {
+    LN_REQUIRE(tokens >= 0 && width >= 1 && pos_dim >= 0 && pos_dim <= width && per >= 1, LN_ERR_ARG, "%s: bad sizes", who);
+    LN_REQUIRE(!listed || tokens / per <= 0x7fffffffll, LN_ERR_ARG, "%s: more than 2^31 points", who);
+    LN_REQUIRE(clouds >= 1 && clouds <= max_clouds, LN_ERR_UNSUPPORTED, "%s: 1 <= clouds <= %d (got %d)", who, max_clouds, clouds);
+    LN_REQUIRE(!listed || point_starts != nullptr, LN_ERR_ARG, "%s: null point_starts", who);
     if (tokens == 0) return LN_OK;
     LN_REQUIRE(distributed && splat_idx && position_sums && counts && row_starts && out, LN_ERR_ARG, "%s: null buffer", who);
     const dim3 grid(ln_div_up(tokens * width, 256));
-    if (tokens * width <= 0x7fffffffll && tokens_per_cloud <= 0x7fffffffll)
-        LN_LAUNCH("k_distribute_centre_clouds", k_distribute_centre_clouds<int>, grid, dim3(256), 0, (hipStream_t)stream, distributed, splat_idx,
-                  position_sums, counts, tokens, width, pos_dim, tokens_per_cloud, row_starts, clouds, out);
-    else
-        LN_LAUNCH("k_distribute_centre_clouds", k_distribute_centre_clouds<long long>, grid, dim3(256), 0, (hipStream_t)stream, distributed,
-                  splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_cloud, row_starts, clouds, out);
+    const bool narrow = tokens * width <= 0x7fffffffll && (listed || per <= 0x7fffffffll);  // int: every element index, and the divisor, fit 31 bits
+    if (listed) {
+        const auto kernel = narrow ? k_distribute_centre_cloud_starts<int> : k_distribute_centre_cloud_starts<long long>;
+        LN_LAUNCH("k_distribute_centre_cloud_starts", kernel, grid, dim3(256), 0, (hipStream_t)stream, distributed, splat_idx, position_sums, counts,
+                  tokens, width, pos_dim, (int)per, point_starts, row_starts, clouds, out);
+    } else {
+        const auto kernel = narrow ? k_distribute_centre_clouds<int> : k_distribute_centre_clouds<long long>;
+        LN_LAUNCH("k_distribute_centre_clouds", kernel, grid, dim3(256), 0, (hipStream_t)stream, distributed, splat_idx, position_sums, counts, tokens,
+                  width, pos_dim, per, row_starts, clouds, out);
+    }
     return ln_check_launch(who);
 }
 
-// (the kernel reads the starts from global memory, any number of them: the two entry points differ in the limit they check)
 extern "C" int ln_distribute_centre_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
                                            long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts,
                                            int clouds, float* out, void* stream) {
-    return ln_distribute_centre_clouds_run("ln_distribute_centre_clouds", LN_CLOUDS_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_cloud,
-                                           row_starts, clouds, out, stream);
+    return ln_distribute_centre_clouds_run("ln_distribute_centre_clouds", LN_CLOUDS_MAX, false, distributed, splat_idx, position_sums, counts, tokens,
+                                           width, pos_dim, tokens_per_cloud, nullptr, row_starts, clouds, out, stream);
 }
 
 extern "C" int ln_distribute_centre_many_clouds(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
                                                 long long tokens, int width, int pos_dim, long long tokens_per_cloud, const int* row_starts,
                                                 int clouds, float* out, void* stream) {
-    return ln_distribute_centre_clouds_run("ln_distribute_centre_many_clouds", LN_CLOUDS_MANY_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim,
-                                           tokens_per_cloud, row_starts, clouds, out, stream);
-}
-
-// Clouds of unequal sizes (LnTableClouds.batch_point_starts): the cloud of token t is that of its point t / tokens_per_point, found by the
-// binary search of the key pass (ln_cloud_of_point: reads inside the list and returns a cloud in [0, clouds) whatever the list holds).
-template <typename IDX>
-__global__ void __launch_bounds__(256)
-    k_distribute_centre_cloud_starts(const float* __restrict__ d, const int* __restrict__ idx, const float* __restrict__ sums,
-                                     const int* __restrict__ counts, long long tokens, int width, int pos_dim, int tokens_per_point,
-                                     const int* __restrict__ point_starts, const int* __restrict__ row_starts, int clouds,
-                                     float* __restrict__ out) {
-    const long long i64 = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i64 >= tokens * width) return;
-    const IDX i = (IDX)i64;
-    const IDX t = i / (IDX)width;
-    const int c = int(i - t * (IDX)width);
-    const int first = row_starts[ln_cloud_of_point(point_starts, clouds, int(t / (IDX)tokens_per_point))];
-    const int row = idx[t];
-    float x = 0.f;
-    if (row >= 0 && row != first) {
-        x = d[i64];
-        if (c < pos_dim) x -= sums[(size_t)row * pos_dim + c] / (float)max(counts[row], 1);
-    }
-    out[i64] = x;
-}
-
-static int ln_distribute_centre_cloud_starts_run(const char* who, int max_clouds, const float* distributed, const int* splat_idx, const float* position_sums,
-                                                 const int* counts, long long tokens, int width, int pos_dim, int tokens_per_point,
-                                                 const int* point_starts, const int* row_starts, int clouds, float* out, void* stream) {
-    LN_REQUIRE(tokens >= 0 && width >= 1 && pos_dim >= 0 && pos_dim <= width && tokens_per_point >= 1, LN_ERR_ARG,
-               "%s: bad sizes", who);
-    LN_REQUIRE(tokens / tokens_per_point <= 0x7fffffffll, LN_ERR_ARG, "%s: more than 2^31 points", who);
-    LN_REQUIRE(clouds >= 1 && clouds <= max_clouds, LN_ERR_UNSUPPORTED, "%s: 1 <= clouds <= %d (got %d)", who,
-               max_clouds, clouds);
-    LN_REQUIRE(point_starts != nullptr, LN_ERR_ARG, "%s: null point_starts", who);
-    if (tokens == 0) return LN_OK;
-    LN_REQUIRE(distributed && splat_idx && position_sums && counts && row_starts && out, LN_ERR_ARG,
-               "%s: null buffer", who);
-    const dim3 grid(ln_div_up(tokens * width, 256));
-    if (tokens * width <= 0x7fffffffll)
-        LN_LAUNCH("k_distribute_centre_cloud_starts", k_distribute_centre_cloud_starts<int>, grid, dim3(256), 0, (hipStream_t)stream, distributed,
-                  splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_point, point_starts, row_starts, clouds, out);
-    else
-        LN_LAUNCH("k_distribute_centre_cloud_starts", k_distribute_centre_cloud_starts<long long>, grid, dim3(256), 0, (hipStream_t)stream,
-                  distributed, splat_idx, position_sums, counts, tokens, width, pos_dim, tokens_per_point, point_starts, row_starts, clouds, out);
-    return ln_check_launch(who);
+    return ln_distribute_centre_clouds_run("ln_distribute_centre_many_clouds", LN_CLOUDS_MANY_MAX, false, distributed, splat_idx, position_sums, counts,
+                                           tokens, width, pos_dim, tokens_per_cloud, nullptr, row_starts, clouds, out, stream);
 }
 
 extern "C" int ln_distribute_centre_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums, const int* counts,
                                                  long long tokens, int width, int pos_dim, int tokens_per_point, const int* point_starts,
                                                  const int* row_starts, int clouds, float* out, void* stream) {
-    return ln_distribute_centre_cloud_starts_run("ln_distribute_centre_cloud_starts", LN_CLOUDS_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim,
-                                                 tokens_per_point, point_starts, row_starts, clouds, out, stream);
+    return ln_distribute_centre_clouds_run("ln_distribute_centre_cloud_starts", LN_CLOUDS_MAX, true, distributed, splat_idx, position_sums, counts, tokens,
+                                           width, pos_dim, tokens_per_point, point_starts, row_starts, clouds, out, stream);
 }
 
 extern "C" int ln_distribute_centre_many_cloud_starts(const float* distributed, const int* splat_idx, const float* position_sums,
                                                       const int* counts, long long tokens, int width, int pos_dim, int tokens_per_point,
                                                       const int* point_starts, const int* row_starts, int clouds, float* out, void* stream) {
-    return ln_distribute_centre_cloud_starts_run("ln_distribute_centre_many_cloud_starts", LN_CLOUDS_MANY_MAX, distributed, splat_idx, position_sums, counts, tokens, width, pos_dim,
-                                                 tokens_per_point, point_starts, row_starts, clouds, out, stream);
+    return ln_distribute_centre_clouds_run("ln_distribute_centre_many_cloud_starts", LN_CLOUDS_MANY_MAX, true, distributed, splat_idx, position_sums,
+                                           counts, tokens, width, pos_dim, tokens_per_point, point_starts, row_starts, clouds, out, stream);
 }

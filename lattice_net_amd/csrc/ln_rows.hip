@@ -7,6 +7,7 @@
 // Compiled with -ffp-contract=off: products and sums are rounded separately so the
 // order-deterministic kernels are bit-identical to the CPU oracle.
 #include "ln_common.h"
+#include <type_traits>
 
 // wave-tiled slice + classifier kernels for the common shapes (ln_classify.hip); return 0 when the shape is not covered
 int ln_sc_forward_wave(const float* values, const float* delta_w, const float* lin_w, const float* lin_b, const int* idx, const float* w,
@@ -142,15 +143,19 @@ __global__ void __launch_bounds__(256)
     reinterpret_cast<T*>(out)[g] = acc;
 }
 
-#define LN_SLICE_CASE(DD)                                                                                                             \
-    case DD:                                                                                                                          \
-        if (VEC == 4 && chunks == 8)                                                                                                  \
-            LN_LAUNCH("k_slice_forward", (k_slice_forward<4, DD + 1, 8>), dim3(ln_div_up(work, 256)), dim3(256), 0, (hipStream_t)stream,  \
-                      values, idx, w, work, chunks, out, zero_fill, zero_elems);                                                      \
-        else                                                                                                                          \
-        LN_LAUNCH("k_slice_forward", (k_slice_forward<VEC, DD + 1>), dim3(ln_div_up(work, 256)), dim3(256), 0, (hipStream_t)stream, values, \
-                  idx, w, work, chunks, out, zero_fill, zero_elems);                                                                  \
-        break;
+// The kernel instance for pos_dim: pick(DP1 = pos_dim + 1 as a compile-time constant); the caller has checked 1 <= pos_dim <= LN_MAX_POS_DIM.
+template <class PICK>
+static auto ln_slice_forward_kernel(int pos_dim, PICK pick) {
+    switch (pos_dim) {
+        case 1: return pick(std::integral_constant<int, 2>());
+        case 2: return pick(std::integral_constant<int, 3>());
+        case 3: return pick(std::integral_constant<int, 4>());
+        case 4: return pick(std::integral_constant<int, 5>());
+        case 5: return pick(std::integral_constant<int, 6>());
+        default: return pick(std::integral_constant<int, 7>());
+    }
+}
+
 static int ln_slice_forward_impl(const float* values, const int* idx, const float* w, int n, int pos_dim, int val_dim, float* out,
                                  float* zero_fill, long long zero_elems, void* stream) {
     int rc = ln_check_rows("ln_slice_forward", values, idx, out, n, pos_dim, val_dim);
@@ -163,8 +168,11 @@ static int ln_slice_forward_impl(const float* values, const int* idx, const floa
     LN_DISPATCH_VEC(val_dim, {
         const int chunks = val_dim / VEC;
         const long long work = (long long)n * chunks;
-        switch (pos_dim) { LN_SLICE_CASE(1) LN_SLICE_CASE(2) LN_SLICE_CASE(3) LN_SLICE_CASE(4) LN_SLICE_CASE(5) LN_SLICE_CASE(6) }
-
+        const auto kernel = ln_slice_forward_kernel(pos_dim, [&](auto dp1) {
+            return VEC == 4 && chunks == 8 ? k_slice_forward<4, decltype(dp1)::value, 8> : k_slice_forward<VEC, decltype(dp1)::value>;
+        });
+        LN_LAUNCH("k_slice_forward", kernel, dim3(ln_div_up(work, 256)), dim3(256), 0, (hipStream_t)stream, values, idx, w, work, chunks, out,
+                  zero_fill, zero_elems);
     });
     return ln_check_launch("ln_slice_forward");
 }
@@ -380,20 +388,11 @@ static int ln_slice_forward_f16_impl(const void* values_f16, const int* idx, con
     const long long work = (long long)n * chunks;
     const _Float16* vv = static_cast<const _Float16*>(values_f16);
     _Float16* oo = static_cast<_Float16*>(out_f16);
-#define LN_SLICE16_CASE(DD)                                                                                                            \
-    case DD:                                                                                                                          \
-        if (wide && chunks == 8)                                                                                                      \
-            LN_LAUNCH("k_slice_forward_f16", (k_slice_forward_f16<DD + 1, 8, 8>), dim3(ln_div_up(work, 256)), dim3(256), 0, st, vv, idx, w, work, \
-                      chunks, oo, zero_fill, zero_elems);                                                                             \
-        else if (wide)                                                                                                                \
-            LN_LAUNCH("k_slice_forward_f16", (k_slice_forward_f16<DD + 1, 8>), dim3(ln_div_up(work, 256)), dim3(256), 0, st, vv, idx, w, work, \
-                      chunks, oo, zero_fill, zero_elems);                                                                             \
-        else                                                                                                                          \
-            LN_LAUNCH("k_slice_forward_f16", (k_slice_forward_f16<DD + 1, 4>), dim3(ln_div_up(work, 256)), dim3(256), 0, st, vv, idx, w, work, \
-                      chunks, oo, zero_fill, zero_elems);                                                                             \
-        break;
-    switch (pos_dim) { LN_SLICE16_CASE(1) LN_SLICE16_CASE(2) LN_SLICE16_CASE(3) LN_SLICE16_CASE(4) LN_SLICE16_CASE(5) LN_SLICE16_CASE(6) }
-#undef LN_SLICE16_CASE
+    const auto kernel = ln_slice_forward_kernel(pos_dim, [&](auto dp1) {
+        constexpr int DP1 = decltype(dp1)::value;
+        return wide && chunks == 8 ? k_slice_forward_f16<DP1, 8, 8> : wide ? k_slice_forward_f16<DP1, 8> : k_slice_forward_f16<DP1, 4>;
+    });
+    LN_LAUNCH("k_slice_forward_f16", kernel, dim3(ln_div_up(work, 256)), dim3(256), 0, st, vv, idx, w, work, chunks, oo, zero_fill, zero_elems);
     return ln_check_launch("ln_slice_forward_f16");
 }
 
