@@ -329,6 +329,11 @@ int ln_row2im(const int* nbr, const float* rowified, int m, int filter_extent, i
  * layout of the kernel those sizes select): the split launch is skipped.  For hosts that convolve repeatedly with unchanged
  * weights (inference; several clouds per optimizer step) and keep one workspace per layer. */
 #define LN_CONV_BANK_READY 4
+/* The caller keeps several scans in flight on this GPU (the meaning of LN_BUILD_OVERLAPPED).  A speed hint only: the fused 32-channel
+ * kernels (filter_extent 9, val_dim = nr_filters = 32) then run as narrow workgroups that loop over their rows and leave room on
+ * their CU for the other scans' kernels.  Same output, bit for bit; same workspace sizes.  Accepted by ln_conv_forward,
+ * ln_conv_forward_ws and ln_conv_backward_flags. */
+#define LN_CONV_OVERLAPPED 8
 int ln_conv_forward(const int* nbr, const float* values_neigh, const float* filter, int m, int filter_extent, int val_dim,
                     int nr_filters, int flags, float* out, void* stream);
 /* ln_conv_forward with scratch.  When the lattice has few vertices (coarse levels of a U-Net: fewer vertex tiles than CUs) the
@@ -406,6 +411,11 @@ size_t ln_conv_backward_workspace_bytes(int mq, int mn, int filter_extent, int v
 int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter, int mq, int mn,
                      int filter_extent, int val_dim, int nr_filters, float* grad_values, float* grad_filter, void* workspace,
                      size_t workspace_bytes, const int* row_partition, void* stream);
+/* ln_conv_backward with `flags`: 0 or LN_CONV_OVERLAPPED (the value gradient is the same bit for bit; the filter gradient is summed
+ * over other row groups, so it differs in rounding only).  Same workspace size. */
+int ln_conv_backward_flags(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter, int mq,
+                           int mn, int filter_extent, int val_dim, int nr_filters, int flags, float* grad_values, float* grad_filter,
+                           void* workspace, size_t workspace_bytes, const int* row_partition, void* stream);
 
 /* Half-precision feature path of the scatters and the slice (C5: "features fp16, accumulate fp32"): the segment reduce with
  * fp16 source rows (fp32 weights, fp32 accumulation into an fp32 dst) — plain and fused with the neighbour traversal — and the

@@ -27,6 +27,7 @@ LN_NOT_VISITED = -2
 LN_CONV_FLIP_NEIGHBOURS = 1
 LN_CONV_TRANSPOSED_FILTER = 2
 LN_CONV_BANK_READY = 4
+LN_CONV_OVERLAPPED = 8
 LN_MAX_POS_DIM = 6
 LN_KEYS_RAW = 0
 LN_KEYS_LATTICE = 1
@@ -150,6 +151,7 @@ SIGNATURES = {
     "ln_slice_forward_f16_prepare_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
     "ln_conv_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ln_conv_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "ln_conv_backward_flags": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "ln_conv_forward_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ln_conv_grad_filter_f16_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ln_conv_grad_filter_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

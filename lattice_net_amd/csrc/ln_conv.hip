@@ -1296,6 +1296,158 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
         }
 }
 
+// The same kernel as a narrow, row-looping workgroup (LN_CONV_OVERLAPPED, ln_conv_plan.h): 256 T threads stage the bank once and walk C
+// consecutive tiles of 64 T rows.  Per row the arithmetic is k_conv_forward_b3's, instruction for instruction.  A kernel of its own, not
+// a second parameter of the one above: as one template the C = 1 instances came out of the compiler with other code than before
+// (a few instructions and waits moved), and callers that never set the hint measured 0.5 % slower at 129 k rows.
+template <int T, int C>
+__global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T, T)))
+    k_conv_forward_b3_rows(const int* __restrict__ nbr, const float* __restrict__ values, const float* __restrict__ filter, int m,
+                      float* __restrict__ out, const int* __restrict__ row_part) {
+    constexpr int V = 32, F = 32, E = 9, KQ = 8, NT = 2;
+    constexpr int THREADS = 256 * T;
+    constexpr int FRAG16 = E * NT * 3 * 64;  // 16-byte fragments of the split bank (54 KB)
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[FRAG16 * 16];
+    const u32x4* s_frag = reinterpret_cast<const u32x4*>(s_raw);
+    // Line-shaped gathers (round 5).  Loads shaped like the MFMA fragment — lane (i, q) reads its 32-byte quarter of row i — touch 64
+    // different 128-byte lines per wave-instruction and run at half the rate of loads in which 8 adjacent lanes read one whole row
+    // (tools/probes/gather_layout_probe.cpp: 3.5 vs 7.0 TB/s whatever the hit rate).  So lane l loads piece l & 7 (16 bytes) of rows
+    // l >> 3 and 8 + (l >> 3) of the wave's 16, and the wave re-shapes the 2 KB through a private LDS region: two 16-byte stores, two
+    // 16-byte reads per slot.  Piece p of row r sits at position p ^ f(r), f(r) = ((r >> 1) & 7) ^ (((r >> 2) & 1) << 1):
+    // conflict-free for the 16-lane groups of ds_read_b128 under the (i, q) mapping (checked exhaustively) and for the stores
+    // (8 adjacent lanes = one row).  LDS operations of one wave execute in program order: no barrier, only a compiler fence.
+    __shared__ __attribute__((aligned(16))) floatx4 s_x[4 * T][16 * 8];
+    __shared__ int s_nbr[64 * T * E];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int i = lane & 15;
+    const int q = lane >> 4;
+    const int bx0 = ln_partition_tile(blockIdx.x, gridDim.x, row_part, 64 * T * C) * C;  // space-ordered table: XCD x takes the tiles of kd region x
+    const int m00 = bx0 * (64 * T) + (tid >> 6) * 16;
+    // bank staging: one item = (slot e, 8 consecutive rows v of W_e, column f) = ONE 16-byte fragment per split part.  The eight
+    // loads of an item are 4 bytes each but consecutive lanes take consecutive columns, so every load instruction reads whole
+    // lines; the fragment goes to LDS with three 16-byte stores.  (Staging a float4 of four columns per thread instead scattered
+    // its twelve halfs over twelve fragments: 36 two-byte LDS stores per thread; the kernel time at T = 3 is the same, 25.3 -> 23.1 us at T = 1.)
+    constexpr int ITEMS = E * (V / 8) * F;
+    constexpr int NIT = (ITEMS + THREADS - 1) / THREADS;
+    float wv[NIT][8];
+#pragma unroll
+    for (int s = 0; s < NIT; ++s) {
+        const int x = min(tid + s * THREADS, ITEMS - 1);  // (clamped: the loads of the last, partly used round stay unconditional — no branch
+        const int f = x % F;                              //  around eight loads; the staging below skips what lies beyond ITEMS)
+        const int ev8 = x / F;  // e * (V / 8) + v / 8
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wv[s][j] = filter[(ev8 * 8 + j) * F + f];
+    }
+    // C > 1 (the narrow form of LN_CONV_OVERLAPPED): the workgroup walks C consecutive tiles of 64 T rows behind one bank staging.
+    // Per row the arithmetic below is that of C = 1.
+    bool staged = false;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+    const int bx = bx0 + c;
+    const int m0 = m00 + c * (64 * T);
+    {
+        const size_t g0 = (size_t)bx * (64 * T) * E, g_end = (size_t)m * E;
+        for (int x = tid; x < 64 * T * E; x += THREADS) s_nbr[x] = (g0 + x < g_end) ? nbr[g0 + x] : -1;
+    }
+    {
+        bool any = false;
+        for (int x = tid; x < 64 * T * E; x += THREADS) any |= s_nbr[x] >= 0;
+        if (!__syncthreads_or(any)) {
+            for (int x = tid; x < 64 * T * (F / 4); x += THREADS) {
+                const int row = bx * (64 * T) + x / (F / 4);
+                if (row < m) *reinterpret_cast<float4*>(out + (size_t)row * F + (x % (F / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            if constexpr (C == 1) return;
+            else continue;  // (s_nbr is rewritten behind the barrier of this test, which every wave has passed)
+        }
+    }
+    const int wv_ = tid >> 6;
+    const int lr = lane >> 3;  // the two rows this lane loads: lr and 8 + lr
+    int nb[2][E];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < E; ++e) nb[j][e] = s_nbr[(wv_ * 16 + 8 * j + lr) * E + e];
+    auto fsw = [](int r) -> int { return ((r >> 1) & 7) ^ (((r >> 2) & 1) << 1); };
+    floatx4* xw[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) xw[j] = &s_x[wv_][(8 * j + lr) * 8 + ((lane & 7) ^ fsw(8 * j + lr))];
+    const floatx4* xr0 = &s_x[wv_][i * 8 + ((2 * q) ^ fsw(i))];
+    const floatx4* xr1 = &s_x[wv_][i * 8 + ((2 * q + 1) ^ fsw(i))];
+#ifndef LN_FWD_DEPTH
+#define LN_FWD_DEPTH 4
+#endif
+    constexpr int DEPTH = LN_FWD_DEPTH;  // ring of gathered quarter rows: DEPTH - 1 gathers in flight (4: 14.9 us, 7: 15.7, 10 = all nine up front: 17.1)
+    floatx4 a[DEPTH][2];
+    auto gather = [&](int e, floatx4 (&dst)[2]) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            dst[j] = *reinterpret_cast<const floatx4*>(values + (size_t)(nb[j][e] >= 0 ? nb[j][e] : 0) * V + (lane & 7) * 4);
+    };
+#pragma unroll
+    for (int k = 0; k < DEPTH - 1 && k < E; ++k) gather(k, a[k]);
+    // bank -> split -> LDS fragments (16-byte unit ((e * NT + f / 16) * 3 + part) * 64 + (v / 8) * 16 + f % 16 holds rows v..v+7)
+    u32x4* s_frag_w = reinterpret_cast<u32x4*>(s_raw);
+    if (!staged) {  // once per workgroup: in its first tile with a neighbour present
+    staged = true;
+#pragma unroll
+    for (int s = 0; s < NIT; ++s) {
+        const int x = tid + s * THREADS;
+        if (x < ITEMS) {
+            const int f = x % F;
+            const int ev8 = x / F;
+            const int e = ev8 / (V / 8);
+            const int vo = ev8 - e * (V / 8);
+            unsigned int h[8], md[8], lo[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ln_split3_bits(wv[s][j], h[j], md[j], lo[j]);
+            const int unit = ((e * NT + (f >> 4)) * 3) * 64 + vo * 16 + (f & 15);
+            s_frag_w[unit] = u32x4{ln_pack_hi(h[0], h[1]), ln_pack_hi(h[2], h[3]), ln_pack_hi(h[4], h[5]), ln_pack_hi(h[6], h[7])};
+            s_frag_w[unit + 64] = u32x4{ln_pack_hi(md[0], md[1]), ln_pack_hi(md[2], md[3]), ln_pack_hi(md[4], md[5]), ln_pack_hi(md[6], md[7])};
+            s_frag_w[unit + 128] = u32x4{ln_pack_hi(lo[0], lo[1]), ln_pack_hi(lo[2], lo[3]), ln_pack_hi(lo[4], lo[5]), ln_pack_hi(lo[6], lo[7])};
+        }
+    }
+    }
+    floatx4 acc[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+    __syncthreads();  // the bank is staged; every wave has its ids out of s_nbr (the next tile refills it)
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (e + DEPTH - 1 < E) gather(e + DEPTH - 1, a[(e + DEPTH - 1) % DEPTH]);
+        // rows of absent neighbours are zeroed by the lane that loaded them; then the wave's 16 x 32 floats change shape through LDS
+#pragma unroll
+        for (int j = 0; j < 2; ++j) *xw[j] = (nb[j][e] >= 0) ? a[e % DEPTH][j] : floatx4{0.f, 0.f, 0.f, 0.f};
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const floatx4 lo4 = *xr0, hi4 = *xr1;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const float ae[KQ] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+        u32x4 p[3];
+        ln_split3_pack8(ae, 0, p);
+        const bf16x8 ap[3] = {__builtin_bit_cast(bf16x8, p[0]), __builtin_bit_cast(bf16x8, p[1]), __builtin_bit_cast(bf16x8, p[2])};
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const u32x4* pb = s_frag + ((e * NT + nt) * 3) * 64 + lane;
+            const bf16x8 bp[3] = {__builtin_bit_cast(bf16x8, pb[0]), __builtin_bit_cast(bf16x8, pb[64]), __builtin_bit_cast(bf16x8, pb[128])};
+            ln_b3_mfma16(ap, bp, acc[nt]);
+        }
+    }
+    // C/D layout: col = lane & 15, row = (lane >> 4) * 4 + reg
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = m0 + q * 4 + r;
+            if (row < m) out[(size_t)row * F + nt * 16 + i] = acc[nt][r];
+        }
+    }
+}
+
 // what the launches of one convolution call share
 template <bool FLIP, bool WT>
 struct LnConvCall {
@@ -1429,7 +1581,10 @@ static void ln_conv_run(const LnConvPlan& p, const LnConvCall<FLIP, WT>& c) {
         switch (l.kernel) {
             case LN_K_FORWARD_B3:
                 if constexpr (!FLIP && !WT) {
-                    if (l.t == 1) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<1>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, c.row_partition);
+                    if (l.c > 1)  // the narrow row-looping form (LN_CONV_OVERLAPPED): the one (T, C) the plan names
+                        LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3_rows<LN_CONV_OVL_T, LN_CONV_OVL_C>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out,
+                                  c.row_partition);
+                    else if (l.t == 1) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<1>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, c.row_partition);
                     else if (l.t == 2) LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<2>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, c.row_partition);
                     else LN_LAUNCH("k_conv_mfma", (k_conv_forward_b3<3>), grid, block, 0, c.st, c.nbr, c.values, c.filter, c.m, c.out, c.row_partition);
                 }
@@ -1484,7 +1639,7 @@ static int ln_conv_forward_riding(const int* nbr, const float* values_neigh, con
     const int rc = [&]() -> int {
         LN_REQUIRE(m >= 0 && filter_extent >= 1 && val_dim >= 1 && nr_filters >= 1, LN_ERR_ARG, "ln_conv_forward: bad sizes");
         LN_REQUIRE(m == 0 || (nbr && values_neigh && filter && out), LN_ERR_ARG, "ln_conv_forward: null buffer");
-        LN_REQUIRE((flags & ~7) == 0, LN_ERR_ARG, "ln_conv_forward: unknown flags %d", flags);
+        LN_REQUIRE((flags & ~15) == 0, LN_ERR_ARG, "ln_conv_forward: unknown flags %d", flags);
         if (m == 0) return LN_OK;
         LnConvPlanIn in = {};
         in.m = m, in.E = filter_extent, in.V = val_dim, in.F = nr_filters;
@@ -1496,6 +1651,7 @@ static int ln_conv_forward_riding(const int* nbr, const float* values_neigh, con
         // the workspace already holds the split bank of this filter (written by an earlier call with the same sizes and flags)
         in.bank_ready = (flags & LN_CONV_BANK_READY) != 0 && workspace != nullptr;
         in.riding_total = sum.partial ? sum.total : 0;
+        in.overlapped = (flags & LN_CONV_OVERLAPPED) != 0;
         switch (flags & 3) {
             case 0: ln_conv_plan_and_run<false, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, row_partition, st); break;
             case LN_CONV_FLIP_NEIGHBOURS: ln_conv_plan_and_run<true, false>(in, nbr, values_neigh, filter, out, workspace, sum, &sum_left, row_partition, st); break;
@@ -2374,6 +2530,257 @@ __global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T,
     }
 }
 
+// k_conv_backward_fused_b3 as a narrow, row-looping workgroup (LN_CONV_OVERLAPPED; a kernel of its own for the reason given at
+// k_conv_forward_b3_rows): C consecutive tiles of 64 T rows behind one bank staging, acc_w kept across the tiles, ONE slab.
+template <int T, int C>
+__global__ void __launch_bounds__(256 * T) __attribute__((amdgpu_waves_per_eu(T, T)))
+    k_conv_backward_fused_b3_rows(const int* __restrict__ nbr, const float* __restrict__ values, const float* __restrict__ grad_out,
+                             const float* __restrict__ filter, int m, float* __restrict__ grad_values, float* __restrict__ slabs,
+                             const int* __restrict__ row_part) {
+    constexpr int V = 32, F = 32, E = 9, KQ = 8, NT = 2, FT = 2;
+    constexpr int THREADS = 256 * T;
+    constexpr int BANK = E * V * F;                      // floats of one slab (the parking area at the end)
+    constexpr int FRAG16 = E * NT * 3 * 64;              // 16-byte fragments of the split bank
+    // Staged G_e rows.  Rounds 3-5: 64 bytes + 16 of padding per row — conflict-free for the 16-byte staging stores but not for the
+    // transposing reads (rows r and r + 3 / r + 8 and r + 11 of a lane group overlap).  Round 6: no padding, the 16-byte piece p of row r
+    // sits at position p ^ swz(r), swz(r) = ((r >> 1) & 3) ^ (bit 3 of r) << 1, chosen against the lane groups of MI355X_MICROARCH.md §LDS:
+    //   ds_write_b128 — 8 adjacent lanes (rows 8a .. 8a + 7 of one quarter) over 128 bytes: even rows take positions q ^ {0, 1, 2, 3} of
+    //                   the first 64 bytes, odd rows of the second — eight different 16-byte columns;
+    //   ds_read_b64_tr_b16 — 32 lanes (rows R .. R + 3 and R + 8 .. R + 11, 32 bytes each) over 256 bytes: rows R + j and R + 8 + j share
+    //                   a 64-byte column and, bit 3 flipping the half, read its two different halves.
+    // 12 KB less LDS per sub-tile.
+    constexpr int RS = 32;                               // bf16 elements per staged G_e row
+    auto swz = [](int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; };  // {0, 2, 3, 1} by row quad (see the line-shaped gathers below)
+    constexpr int PART = 64 * RS;                        // one part of one sub-tile's G_e
+    constexpr int STAGE = 2 * 3 * PART;                  // double-buffered, three parts (bf16 elements)
+    constexpr int LDS_BYTES_A = FRAG16 * 16 + T * STAGE * 2;
+    constexpr int LDS_BYTES_B = (T - 1) * BANK * 4;
+    constexpr int LDS_BYTES = LDS_BYTES_A > LDS_BYTES_B ? LDS_BYTES_A : LDS_BYTES_B;
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[LDS_BYTES];
+    u32x4* s_frag = reinterpret_cast<u32x4*>(s_raw);
+    unsigned short* s_fh = reinterpret_cast<unsigned short*>(s_raw);
+    unsigned short* s_stage = reinterpret_cast<unsigned short*>(s_raw + FRAG16 * 16);
+    const int tid = threadIdx.x;
+    const int sub = tid >> 8;
+    const int t256 = tid & 255;
+    const int lane = tid & 63;
+    const int wave = t256 >> 6;
+    const int i = lane & 15;
+    const int q = lane >> 4;
+    const int bx0 = ln_partition_tile(blockIdx.x, gridDim.x, row_part, 64 * T * C) * C;  // space-ordered table: XCD x takes the tiles of kd region x
+    const int sub00 = bx0 * (64 * T) + sub * 64;
+    const int m00 = sub00 + wave * 16;
+
+    constexpr int N4 = E * V * F / 4;
+    constexpr int NST = (N4 + THREADS - 1) / THREADS;
+    float4 wv[NST];
+#pragma unroll
+    for (int s = 0; s < NST; ++s) {
+        const int x4 = tid + s * THREADS;
+        wv[s] = (N4 % THREADS == 0 || x4 < N4) ? reinterpret_cast<const float4*>(filter)[x4] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const int vt = wave / FT, ft = wave % FT;
+    floatx4 acc_w[E];  // (every slot is assigned in the first tile)
+    // C > 1 (the narrow form of LN_CONV_OVERLAPPED): the workgroup walks C consecutive tiles of 64 T rows behind one bank staging; the
+    // filter gradient stays in acc_w across the tiles and leaves as ONE slab.  Per row the value gradient is that of C = 1.  The two
+    // G_e buffers alternate over ALL the slots the workgroup walks (E is odd): the slot barriers keep ordering them across tiles.
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+    const int sub0 = sub00 + c * (64 * T);
+    const int m0 = m00 + c * (64 * T);
+    if (c > 0 && (bx0 + c) * (64 * T) >= m) break;  // (uniform over the workgroup) no row left: tiles past the end add nothing
+    // A operand of the filter gradient, split: step s (32 rows), part p -> 8 bf16 = rows 32s + 8q + j of column vt*16 + i
+    u32x4 va[2][3];
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int row = sub0 + 32 * st + 8 * q + j;  // (unconditional load of a clamped row + select: no branch around sixteen loads)
+            const float xv = values[(size_t)min(row, m - 1) * V + vt * 16 + i];
+            x[j] = (row < m) ? xv : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unsigned int h0, m0_, l0, h1, m1_, l1;
+            ln_split3_bits(x[2 * j], h0, m0_, l0);
+            ln_split3_bits(x[2 * j + 1], h1, m1_, l1);
+            va[st][0][j] = ln_pack_hi(h0, h1);
+            va[st][1][j] = ln_pack_hi(m0_, m1_);
+            va[st][2][j] = ln_pack_hi(l0, l1);
+        }
+    }
+#ifndef LN_BWD_DEPTH
+#define LN_BWD_DEPTH 2  // (round 6, line-shaped gathers: 1 / 2 / 3 / 4 / 5 -> 19.0 / 18.7 / 19.3 / 20.4 / 20.8 us on one box)
+#endif
+    constexpr int DEPTH = LN_BWD_DEPTH;  // gathers in flight per lane
+    auto slot_of = [](int k) { return k == 0 ? E - 1 : k - 1; };
+    // Line-shaped gathers (round 6; the forward has them since round 5).  A load shaped like the MFMA fragment — lane (i, q) reads its
+    // 32-byte quarter of row i — touches 16 lines per wave-instruction, half of each; here lane l loads piece l & 7 (16 bytes) of the rows
+    // l >> 3 and 8 + (l >> 3) of the wave's 16: 8 whole lines per instruction.  The rows are staged for the filter gradient anyway; the lane
+    // splits ITS piece, stores 8 bytes per plane, and takes the A operand of the value gradient — its (i, q) quarter, all three parts —
+    // back from the staged rows behind the slot's barrier.  The swizzle {0, 2, 3, 1} by row quad serves all three access shapes:
+    //   ds_write_b64   (16 adjacent lanes = two whole rows, 64 bytes each, on the two halves of the 32 banks): any per-row permutation;
+    //   ds_read_b128   (lane groups {0-3, 12-15, 20-27} ...: quarter q of rows i, i + 12 and quarter q ^ 1 of rows i + 4, i + 8 share
+    //                   the 64-byte column i & 3): positions s(0), s(3), 1 ^ s(1), 1 ^ s(2) = 0, 1, 3, 2;
+    //   ds_read_b64_tr (rows R + j and R + 8 + j share a column and read one 32-byte half each): bit 1 of s differs between quads h, h ^ 2.
+    const int lr = lane >> 3, c8 = lane & 7;
+    int nb2[2][E];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < E; ++e) {  // (clamped row + select, as above)
+            const int id = nbr[(size_t)min(m0 + 8 * j + lr, m - 1) * E + (e < E - 1 ? (e ^ 1) : e)];
+            nb2[j][e] = (m0 + 8 * j + lr < m) ? id : -1;
+        }
+    floatx4 a[DEPTH + 1][2];
+    auto gather = [&](int e, floatx4 (&dst)[2]) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) dst[j] = *reinterpret_cast<const floatx4*>(grad_out + (size_t)(nb2[j][e] >= 0 ? nb2[j][e] : 0) * F + c8 * 4);
+    };
+#pragma unroll
+    for (int j = 0; j < 2; ++j)  // the centre slot is the row itself: no id to wait for
+        a[0][j] = *reinterpret_cast<const floatx4*>(grad_out + (size_t)(m0 + 8 * j + lr < m ? m0 + 8 * j + lr : 0) * F + c8 * 4);
+#pragma unroll
+    for (int k = 1; k < DEPTH && k < E; ++k) gather(slot_of(k), a[k % (DEPTH + 1)]);
+    // bank -> split -> LDS fragments of W_e^T: x = (e*V + v)*F + f, four consecutive f = elements j..j+3 of ONE fragment
+    if (c == 0) {
+#pragma unroll
+    for (int s = 0; s < NST; ++s) {
+        const int x4 = tid + s * THREADS;
+        if (N4 % THREADS == 0 || x4 < N4) {
+            const int x = x4 * 4;
+            const int ev = x / F;
+            const int f0 = x - ev * F;
+            const int e = ev / V;
+            const int v = ev - e * V;
+            const float v4[4] = {wv[s].x, wv[s].y, wv[s].z, wv[s].w};
+            unsigned int h[4], md[4], lo[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ln_split3_bits(v4[j], h[j], md[j], lo[j]);
+            // (the 16-byte unit of (q = f0 >> 3, i = v & 15) sits at column i ^ 2q of its 16-unit row.  ds_write_b64 is served in groups
+            // of 16 adjacent lanes over 32 banks: here two v times (four q, two halves), whose columns i ^ 2q are distinct modulo 8, so a
+            // group covers the 128 bytes once; unswizzled the four q of one v sat 256 bytes apart on the same banks (4-way).  The
+            // fragment reads below — ds_read_b128, lane groups {0-3,12-15,20-27} ... over 64 banks — stay conflict-free under this XOR:
+            // masks 0/2 keep a lane's column inside its quarter pair, masks 4/6 swap both halves of a group together.)
+            const int fr = (((e * NT + (v >> 4)) * 3) * 64 + (f0 >> 3) * 16 + ((v & 15) ^ (2 * (f0 >> 3)))) * 8 + (f0 & 7);
+            *reinterpret_cast<uint2*>(s_fh + fr) = make_uint2(ln_pack_hi(h[0], h[1]), ln_pack_hi(h[2], h[3]));
+            *reinterpret_cast<uint2*>(s_fh + fr + 64 * 8) = make_uint2(ln_pack_hi(md[0], md[1]), ln_pack_hi(md[2], md[3]));
+            *reinterpret_cast<uint2*>(s_fh + fr + 2 * 64 * 8) = make_uint2(ln_pack_hi(lo[0], lo[1]), ln_pack_hi(lo[2], lo[3]));
+        }
+    }
+    }
+    floatx4 acc_v[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc_v[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int e = slot_of(k);
+        unsigned short* sg = s_stage + (size_t)sub * STAGE + ((c * E + k) & 1) * (3 * PART);
+        if (k + DEPTH < E) gather(slot_of(k + DEPTH), a[(k + DEPTH) % (DEPTH + 1)]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {  // this lane's piece of rows lr and 8 + lr: split once, staged for both gradients
+            const floatx4 x = a[k % (DEPTH + 1)][j];
+            const bool there = nb2[j][e] >= 0;
+            unsigned int h[4], md[4], lo[4];
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) ln_split3_bits(there ? x[cc] : 0.f, h[cc], md[cc], lo[cc]);
+            const int row = wave * 16 + 8 * j + lr;
+            unsigned short* dst = sg + row * RS + (((c8 >> 1) ^ swz(row)) * 8 + (c8 & 1) * 4);
+            *reinterpret_cast<uint2*>(dst) = make_uint2(ln_pack_hi(h[0], h[1]), ln_pack_hi(h[2], h[3]));
+            *reinterpret_cast<uint2*>(dst + PART) = make_uint2(ln_pack_hi(md[0], md[1]), ln_pack_hi(md[2], md[3]));
+            *reinterpret_cast<uint2*>(dst + 2 * PART) = make_uint2(ln_pack_hi(lo[0], lo[1]), ln_pack_hi(lo[2], lo[3]));
+        }
+        __syncthreads();
+        u32x4 p1, p2, p3;
+        {
+            const unsigned short* src = sg + (wave * 16 + i) * RS + ((q ^ swz(wave * 16 + i)) * KQ);
+            p1 = *reinterpret_cast<const u32x4*>(src);
+            p2 = *reinterpret_cast<const u32x4*>(src + PART);
+            p3 = *reinterpret_cast<const u32x4*>(src + 2 * PART);
+        }
+        const bf16x8 a1 = __builtin_bit_cast(bf16x8, p1), a2 = __builtin_bit_cast(bf16x8, p2), a3 = __builtin_bit_cast(bf16x8, p3);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const u32x4* pb = s_frag + ((e * NT + nt) * 3) * 64 + q * 16 + (i ^ (2 * q));
+            const bf16x8 b1 = __builtin_bit_cast(bf16x8, pb[0]), b2 = __builtin_bit_cast(bf16x8, pb[64]), b3 = __builtin_bit_cast(bf16x8, pb[128]);
+            acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, b1, acc_v[nt], 0, 0, 0);
+            acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b3, acc_v[nt], 0, 0, 0);
+            acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, acc_v[nt], 0, 0, 0);
+            acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b1, acc_v[nt], 0, 0, 0);
+            acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b2, acc_v[nt], 0, 0, 0);
+            acc_v[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc_v[nt], 0, 0, 0);
+        }
+        // filter gradient: two 32-row steps; B fragments through the LDS transpose read (lane: 4 contiguous bf16 of row
+        // row0 + (i >> 2), columns ft*16 + 4 (i & 3) ..; it receives rows row0..row0+3 of column ft*16 + i)
+        floatx4 w0 = floatx4{0.f, 0.f, 0.f, 0.f}, w1 = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            bf16x8 b[3];
+#pragma unroll
+            for (int part = 0; part < 3; ++part) {
+                // lane: 4 contiguous bf16 (half a 16-byte piece) of row r0 + (i >> 2), elements ft * 16 + 4 (i & 3) ..
+                const int r_lo = 32 * st + 8 * q + (i >> 2), r_hi = r_lo + 4;
+                const int piece = ft * 2 + ((i & 3) >> 1), inner = (i & 1) * 4;
+                const unsigned short* base = sg + part * PART + r_lo * RS + (piece ^ swz(r_lo)) * 8 + inner;
+                const unsigned short* base_hi = sg + part * PART + r_hi * RS + (piece ^ swz(r_hi)) * 8 + inner;
+                const short4v lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(base));
+                const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(base_hi));
+                u32x4 packed;
+                packed[0] = (unsigned int)(unsigned short)lo4[0] | ((unsigned int)(unsigned short)lo4[1] << 16);
+                packed[1] = (unsigned int)(unsigned short)lo4[2] | ((unsigned int)(unsigned short)lo4[3] << 16);
+                packed[2] = (unsigned int)(unsigned short)hi4[0] | ((unsigned int)(unsigned short)hi4[1] << 16);
+                packed[3] = (unsigned int)(unsigned short)hi4[2] | ((unsigned int)(unsigned short)hi4[3] << 16);
+                b[part] = __builtin_bit_cast(bf16x8, packed);
+            }
+            const bf16x8 v1 = __builtin_bit_cast(bf16x8, va[st][0]), v2 = __builtin_bit_cast(bf16x8, va[st][1]), v3 = __builtin_bit_cast(bf16x8, va[st][2]);
+            floatx4& acc = st ? w1 : w0;
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v3, b[0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, b[2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v2, b[1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v2, b[0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, b[1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, b[0], acc, 0, 0, 0);
+        }
+        if (c == 0) acc_w[e] = w0 + w1;
+        else acc_w[e] += w0 + w1;
+    }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = m0 + q * 4 + r;
+            if (row < m) grad_values[(size_t)row * V + nt * 16 + i] = acc_v[nt][r];
+        }
+    }
+    }
+    __syncthreads();
+    float* park_all = reinterpret_cast<float*>(s_raw);
+    const int colp = (ft * 16 + i) ^ ((q & 1) << 4);  // parked column (rows are multiples of 32 floats: the swizzle only ever touches the column)
+    if (sub > 0) {
+        float* park = park_all + (size_t)(sub - 1) * BANK;
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) park[(e * V + vt * 16 + q * 4 + r) * F + colp] = acc_w[e][r];  // (lanes of
+        // quarters 0/1 and 2/3 are served together: their rows, 4 apart, would share the 16 banks of the column tile)
+    }
+    if constexpr (T > 1) __syncthreads();
+    if (sub == 0) {
+        float* dst = slabs + (size_t)blockIdx.x * BANK;
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int o = (e * V + vt * 16 + q * 4 + r) * F + ft * 16 + i;
+                float sum = acc_w[e][r];
+#pragma unroll
+                for (int k2 = 1; k2 < T; ++k2) sum += park_all[(k2 - 1) * BANK + (e * V + vt * 16 + q * 4 + r) * F + colp];
+                dst[o] = sum;
+            }
+    }
+}
+
 // Both gradients of out = conv(values_neigh; nbr_q, filter[E*V, F]):
 //   grad_filter[E*V, F] = im2row(values_neigh; nbr_q)^T @ grad_out            (ln_conv_grad_filter)
 //   grad_values[mn, V]  = conv(grad_out; nbr_n, filter, FLIP | TRANSPOSED)     (ln_conv_forward)
@@ -2384,6 +2791,13 @@ static void ln_bwd_launch_fused(const LnBwdPlan& p, const int* nbr, const float*
                                 float* grad_values, float* partial, const int* row_partition, hipStream_t st) {
     if constexpr (T <= LN_BWD_B3_MAX_T) {  // bf16 matrix cores, exactly split operands
         if (p.form == LN_BWD_FUSED_B3) {
+            if constexpr (T == LN_CONV_OVL_T) {
+                if (p.c > 1) {  // the narrow row-looping form (LN_CONV_OVERLAPPED)
+                    LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused_b3_rows<T, LN_CONV_OVL_C>), dim3(p.grid), dim3(p.block), 0, st, nbr, values, grad_out,
+                              filter, m, grad_values, partial, row_partition);
+                    return;
+                }
+            }
             LN_LAUNCH("k_conv_backward_fused", (k_conv_backward_fused_b3<T>), dim3(p.grid), dim3(p.block), 0, st, nbr, values, grad_out, filter, m,
                       grad_values, partial, row_partition);
             return;
@@ -2397,14 +2811,15 @@ extern "C" size_t ln_conv_backward_workspace_bytes(int mq, int mn, int filter_ex
     return ln_conv_backward_query(mq, mn, filter_extent, val_dim, nr_filters, ln_conv_b3_enabled());
 }
 
-extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter, int mq,
-                                int mn, int filter_extent, int val_dim, int nr_filters, float* grad_values, float* grad_filter,
-                                void* workspace, size_t workspace_bytes, const int* row_partition, void* stream) {
+extern "C" int ln_conv_backward_flags(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter,
+                                      int mq, int mn, int filter_extent, int val_dim, int nr_filters, int flags, float* grad_values,
+                                      float* grad_filter, void* workspace, size_t workspace_bytes, const int* row_partition, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    LN_REQUIRE((flags & ~LN_CONV_OVERLAPPED) == 0, LN_ERR_ARG, "ln_conv_backward: unknown flags %d", flags);
     const LnBwdPlan p = ln_conv_backward_plan(LnBwdPlanIn{
         mq, mn, filter_extent, val_dim, nr_filters, nbr_q == nbr_n,
         nbr_q && nbr_n && values_neigh && grad_out && filter && grad_values && grad_filter, workspace ? workspace_bytes : 0,
-        ln_aligned16(values_neigh) && ln_aligned16(grad_out) && ln_aligned16(filter), ln_conv_b3_enabled()});
+        ln_aligned16(values_neigh) && ln_aligned16(grad_out) && ln_aligned16(filter), ln_conv_b3_enabled(), (flags & LN_CONV_OVERLAPPED) != 0});
     float* partial = static_cast<float*>(workspace);
     const int total = filter_extent * val_dim * nr_filters;
     if (p.form == LN_BWD_FUSED_B3 || p.form == LN_BWD_FUSED_F32) {
@@ -2434,6 +2849,13 @@ extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float*
     rc = ln_conv_forward_riding(nbr_n, grad_out, filter, mn, filter_extent, nr_filters, val_dim, LN_CONV_FLIP_NEIGHBOURS | LN_CONV_TRANSPOSED_FILTER,
                                 grad_values, conv_ws, conv_ws ? workspace_bytes - gf_bytes : 0, row_partition, stream, sum);
     return rc ? rc : ln_check_launch("ln_conv_backward");
+}
+
+extern "C" int ln_conv_backward(const int* nbr_q, const int* nbr_n, const float* values_neigh, const float* grad_out, const float* filter, int mq,
+                                int mn, int filter_extent, int val_dim, int nr_filters, float* grad_values, float* grad_filter,
+                                void* workspace, size_t workspace_bytes, const int* row_partition, void* stream) {
+    return ln_conv_backward_flags(nbr_q, nbr_n, values_neigh, grad_out, filter, mq, mn, filter_extent, val_dim, nr_filters, 0, grad_values,
+                                  grad_filter, workspace, workspace_bytes, row_partition, stream);
 }
 
 // Both gradients of a per-row linear layer y = x w^T (w [cout, cin]; a 1 x 1 lattice convolution over the identity neighbour list

@@ -95,11 +95,25 @@ constexpr bool ln_conv_full_shape(int V, int F) {
 constexpr bool ln_conv_small_filter(int E, int V, int F) { return E == 9 && (size_t)E * V * F * 4 <= 64 * 1024 && V <= 32; }
 constexpr bool ln_bwd_fused_shape(int E, int V, int F) { return E == 9 && V == 32 && F == 32; }
 
-// 64-vertex sub-tiles per workgroup (1..4) of the fused backward and of k_conv_forward_b3.  A workgroup takes a whole CU, so the
-// launch runs in rounds of 256 workgroups and a round costs about T + 1: the T with the cheapest rounds(T) * (T + 1) wins, larger T on
-// ties (fewer slabs) — one round at C3 (T = 3; a 257th workgroup would run after all the others: twice the time), 3 rounds of T = 3 at
-// 129 k vertices.
-constexpr int ln_bwd_subtiles(int m, bool b3_enabled) {
+// 64-vertex sub-tiles per workgroup (1..4) of the fused backward and of k_conv_forward_b3.  The cost model is that of a chip the
+// launch has to itself: there a workgroup takes a whole CU (the T = 3 fused backward holds 3 waves per SIMD of 152 registers and
+// 126 KB of LDS), so the launch runs in rounds of 256 workgroups and a round costs about T + 1: the T with the cheapest
+// rounds(T) * (T + 1) wins, larger T on ties (fewer slabs) — one round at C3 (T = 3; a 257th workgroup would run after all the
+// others: twice the time), 3 rounds of T = 3 at 129 k vertices.  It does NOT hold while the caller keeps several scans in flight
+// (`overlapped`, LN_CONV_OVERLAPPED): then the issue slots a whole-CU workgroup leaves idle are what the other scans' kernels are
+// short of, and the bf16x3 forms take the narrow row-looping shape below instead.
+// Shape measured at C3, four scans in flight: (T, C) = (2, 2) +1.7 %, (1, 3) -4.2 % against the whole-CU T = 3.
+constexpr int LN_CONV_OVL_T = 2;  // narrow form under LN_CONV_OVERLAPPED: 256 * T threads ...
+constexpr int LN_CONV_OVL_C = 2;  // ... that walk C consecutive chunks of 64 * T rows behind ONE bank staging, and write ONE slab
+// the narrow form applies: bf16x3 kernels only, from the row count the bf16x3 forward is taken at up to TWO rounds of whole-CU
+// workgroups (2 x 256 x 192 rows).  Measured with four scans in flight: +1.6 % at 46.5 k rows (C3), +4.2 % at ~90 k
+// (C2, 16 clouds per step), -1.1 % at 129 k (C4: three rounds, between which the other scans get their turn anyway).
+constexpr int LN_CONV_OVL_MAX_ROWS = 2 * 64 * LN_BWD_B3_MAX_T * LN_BWD_CUS;
+constexpr bool ln_bwd_narrow(int m, bool b3_enabled, bool overlapped) {
+    return overlapped && b3_enabled && m >= LN_CONV_B3_MIN_ROWS && m <= LN_CONV_OVL_MAX_ROWS;
+}
+constexpr int ln_bwd_subtiles(int m, bool b3_enabled, bool overlapped = false) {
+    if (ln_bwd_narrow(m, b3_enabled, overlapped)) return LN_CONV_OVL_T;
     const int max_t = b3_enabled ? LN_BWD_B3_MAX_T : LN_BWD_MAX_SUBTILES;
     const int s = (m + 63) / 64;
     int best = 1, best_cost = 1 << 30;
@@ -114,7 +128,14 @@ constexpr int ln_bwd_subtiles(int m, bool b3_enabled) {
     }
     return best;
 }
-constexpr int ln_bwd_workgroups(int m, bool b3_enabled) { return ln_cdiv(m, 64 * ln_bwd_subtiles(m, b3_enabled)); }
+// chunks of 64 * T rows a workgroup walks (1: every form but the narrow one)
+constexpr int ln_bwd_chunks(int m, bool b3_enabled, bool overlapped = false) { return ln_bwd_narrow(m, b3_enabled, overlapped) ? LN_CONV_OVL_C : 1; }
+// workgroups = slabs of the fused backward.  64 * T * C >= 192 >= 64 * (the T of the whole-CU model), so the narrow form never
+// writes more slabs than the form it replaces and the workspace queries (ln_gf_query) cover both.
+static_assert(LN_CONV_OVL_T * LN_CONV_OVL_C >= LN_BWD_B3_MAX_T, "the narrow form would write more slabs than the workspace queries report");
+constexpr int ln_bwd_workgroups(int m, bool b3_enabled, bool overlapped = false) {
+    return ln_cdiv(m, 64 * ln_bwd_subtiles(m, b3_enabled, overlapped) * ln_bwd_chunks(m, b3_enabled, overlapped));
+}
 
 // ---- layout of the per-slot form: what the size queries report ------------------------------------------------------------------
 // bf16x3 path: channel counts that are multiples of 32, lattices large enough to be matrix-bound; bytes of the filter bank split
@@ -194,6 +215,7 @@ enum LnConvKernel : uint8_t {
 struct LnConvLaunch {
     uint8_t kernel;     // LnConvKernel
     uint8_t nt, t;      // template arguments (see LnConvKernel)
+    uint8_t c;          // LN_K_FORWARD_B3: chunks of 64 t rows per workgroup (1 elsewhere)
     bool carries_sum;   // a bank split whose extra workgroups [split_x, grid[0]) add the caller's pending slabs
     int grid[3], block;
     int f_off, cols;    // output columns [f_off, f_off + cols) (conv and bank-split launches)
@@ -211,6 +233,7 @@ struct LnConvPlanIn {
     size_t ws_bytes;
     bool bank_ready;                                   // LN_CONV_BANK_READY: no bank-split launches
     int riding_total;                                  // elements of a slab sum waiting for a bank split to ride in (0: none)
+    bool overlapped = false;                           // LN_CONV_OVERLAPPED: the caller keeps several scans in flight (speed hint)
 };
 struct LnConvPlan {
     size_t bank_bytes, slab_bytes;  // workspace layout in use: [bank][nsplit slabs]; their sum never exceeds the workspace offered
@@ -222,7 +245,7 @@ struct LnConvPlan {
 
 inline LnConvLaunch* ln_plan_add(LnConvPlan& p, LnConvKernel k, int nt, int t, int gx, int gy, int gz, int block, int f_off, int cols) {
     LnConvLaunch& l = p.launch[p.n++];
-    l = LnConvLaunch{uint8_t(k), uint8_t(nt), uint8_t(t), false, {gx, gy, gz}, block, f_off, cols, 0, 0, 0};
+    l = LnConvLaunch{uint8_t(k), uint8_t(nt), uint8_t(t), 1, false, {gx, gy, gz}, block, f_off, cols, 0, 0, 0};
     return &l;
 }
 
@@ -234,8 +257,8 @@ inline LnConvPlan ln_conv_plan(const LnConvPlanIn& in) {
     p.sum_left = in.riding_total > 0;
     if (E == 9 && in.filter_aligned) {  // d = 3 small-filter fast path
         if (!in.flip && !in.wt && V == 32 && F == 32 && m >= LN_CONV_B3_MIN_ROWS && in.b3_enabled && in.values_aligned) {
-            const int bt = ln_bwd_subtiles(m, true), t = bt < 3 ? bt : 3;
-            ln_plan_add(p, LN_K_FORWARD_B3, 2, t, ln_cdiv(m, 64 * t), 1, 1, 256 * t, 0, F);
+            const int bt = ln_bwd_subtiles(m, true, in.overlapped), t = bt < 3 ? bt : 3, c = ln_bwd_chunks(m, true, in.overlapped);
+            ln_plan_add(p, LN_K_FORWARD_B3, 2, t, ln_cdiv(m, 64 * t * c), 1, 1, 256 * t, 0, F)->c = uint8_t(c);
             return p;
         }
         if (ln_conv_full_shape(V, F)) {
@@ -358,7 +381,10 @@ constexpr int ln_gfb_rows(int m, int E, int V, int F) {
 constexpr size_t ln_gf_query(int m, int E, int V, int F, bool b3_enabled) {
     if (!ln_gf_mfma_supported(V, F) || m <= 0) return 256;
     int chunks = ln_cdiv(m, LN_GF_ROWS);
-    if (ln_bwd_fused_shape(E, V, F) && ln_bwd_workgroups(m, b3_enabled) > chunks) chunks = ln_bwd_workgroups(m, b3_enabled);
+    if (ln_bwd_fused_shape(E, V, F)) {  // with and without LN_CONV_OVERLAPPED: one workspace size serves both
+        if (ln_bwd_workgroups(m, b3_enabled, false) > chunks) chunks = ln_bwd_workgroups(m, b3_enabled, false);
+        if (ln_bwd_workgroups(m, b3_enabled, true) > chunks) chunks = ln_bwd_workgroups(m, b3_enabled, true);
+    }
     const int rows_b3 = ln_gfb_rows(m, E, V, F);
     if (rows_b3 > 0 && ln_cdiv(m, rows_b3) > chunks) chunks = ln_cdiv(m, rows_b3);
     return (size_t)chunks * E * V * F * sizeof(float) + 256;
@@ -434,22 +460,25 @@ struct LnBwdPlanIn {
     size_t ws_bytes;   // (0 without a workspace)
     bool aligned;      // values, grad_out and filter: 16 bytes
     bool b3_enabled;
+    bool overlapped = false;  // LN_CONV_OVERLAPPED
 };
 struct LnBwdPlan {
     uint8_t form;
     int t;               // fused forms: sub-tiles
+    int c;               // LN_BWD_FUSED_B3: chunks of 64 t rows per workgroup (1 elsewhere)
     int grid, block;
     int conv_blocks;     // LN_BWD_FULL_SUM: workgroups of the convolution in front of the summing ones
 };
 constexpr LnBwdPlan ln_conv_backward_plan(const LnBwdPlanIn& in) {
-    LnBwdPlan p = {LN_BWD_TWO_CALLS, 0, 0, 256, 0};
+    LnBwdPlan p = {LN_BWD_TWO_CALLS, 0, 1, 0, 256, 0};
     if (!(in.E == 9 && in.mq > 0 && in.mn > 0 && ln_gf_mfma_supported(in.val_dim, in.nr_filters) && in.buffers && in.ws_bytes > 0 &&
           in.ws_bytes >= ln_gf_query(in.mq, in.E, in.val_dim, in.nr_filters, in.b3_enabled) && in.aligned))
         return p;
     if (in.same_list && in.mq == in.mn && ln_bwd_fused_shape(in.E, in.val_dim, in.nr_filters)) {
-        p.t = ln_bwd_subtiles(in.mn, in.b3_enabled);
+        p.t = ln_bwd_subtiles(in.mn, in.b3_enabled, in.overlapped);
+        p.c = ln_bwd_chunks(in.mn, in.b3_enabled, in.overlapped);
         p.form = in.b3_enabled && p.t <= LN_BWD_B3_MAX_T ? LN_BWD_FUSED_B3 : LN_BWD_FUSED_F32;
-        p.grid = ln_cdiv(in.mn, 64 * p.t);
+        p.grid = ln_bwd_workgroups(in.mn, in.b3_enabled, in.overlapped);
         p.block = 256 * p.t;
     } else if (ln_conv_full_shape(in.nr_filters, in.val_dim)) {  // roles in the value-gradient convolution: nr_filters channels in
         p.form = LN_BWD_FULL_SUM;

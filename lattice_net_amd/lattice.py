@@ -115,7 +115,8 @@ def set_slot_order(order: str) -> str:
 
 # How many scans the caller keeps in flight on this GPU (own lattice and stream each: bench.py's throughput mode, a data loader that
 # builds ahead).  Above 1 every build carries LN_BUILD_OVERLAPPED: overlapping builds over small buckets take narrower
-# bucket-pass workgroups.  A speed hint only; a captured graph keeps what was set when it was captured.
+# bucket-pass workgroups, and every fp32 convolution call LN_CONV_OVERLAPPED: the fused 32-channel kernels run as narrow workgroups
+# that loop over their rows.  A speed hint only; a captured graph keeps what was set when it was captured.
 _SCANS_IN_FLIGHT = [max(1, int(os.environ.get("LATTICE_SCANS_IN_FLIGHT", "1")))]
 
 
@@ -1289,6 +1290,8 @@ class Lattice:
         out = torch.empty((m, nr_filters), dtype=vals.dtype, device=self._dev())
         flags = (_lib.LN_CONV_FLIP_NEIGHBOURS if flip_neighbours else 0) | (_lib.LN_CONV_TRANSPOSED_FILTER if filter_is_transposed else 0)
         lib = _lib.load()
+        if not half and _SCANS_IN_FLIGHT[0] > 1:
+            flags |= _lib.LN_CONV_OVERLAPPED  # (a speed hint, as LN_BUILD_OVERLAPPED)
         if half:
             _lib.check(lib.ln_conv_forward_f16(_lib.ptr(nbr), _lib.ptr(vals), _lib.ptr(filter_bank), m, filter_extent, v, nr_filters, flags,
                                                _lib.ptr(out), self._stream()), "ln_conv_forward_f16")
@@ -1369,8 +1372,10 @@ class Lattice:
         # both kernels already fill the chip and the event hand-offs cost more than the overlap.  What does pay is
         # putting the slab sum of the filter gradient into the value-gradient launch: ln_conv_backward.)
         part = nb._row_partition() if q.m_hash_table._storage is nb.m_hash_table._storage else None
-        _lib.check(lib.ln_conv_backward(_lib.ptr(nbr_q), _lib.ptr(nbr_n), _lib.ptr(nb.values()), _lib.ptr(grad_out), _lib.ptr(filter_bank), mq,
-                                        mn, E, v, f, _lib.ptr(gvals), _lib.ptr(gf), _lib.ptr(ws), ws.numel(), part, main), "ln_conv_backward")
+        flags = _lib.LN_CONV_OVERLAPPED if _SCANS_IN_FLIGHT[0] > 1 else 0
+        _lib.check(lib.ln_conv_backward_flags(_lib.ptr(nbr_q), _lib.ptr(nbr_n), _lib.ptr(nb.values()), _lib.ptr(grad_out), _lib.ptr(filter_bank),
+                                              mq, mn, E, v, f, flags, _lib.ptr(gvals), _lib.ptr(gf), _lib.ptr(ws), ws.numel(), part, main),
+                   "ln_conv_backward")
         return gvals, gf
 
     def convolve_im2row_grad_filter(self, grad_out: torch.Tensor, dilation: int, lattice_neighbours: Optional["Lattice"],
