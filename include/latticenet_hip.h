@@ -588,6 +588,32 @@ size_t ln_linear_backward_workspace_bytes(int rows, int cin, int cout);
 int ln_linear_backward(const int* ident, const float* x, const float* grad_y, const float* w, int rows, int cin, int cout, float* grad_x,
                        float* grad_w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The per-row linear layer on fp16 rows (the 1 x 1 layers on the half-precision feature path): a dense GEMM, no neighbour list.
+ * x [rows, cin], y / residual [rows, cout], grad_y [rows, cout], grad_x [rows, cin]: IEEE fp16 (`_Float16`), contiguous;
+ * w [cout, cin], bias [cout], grad_w [cout, cin], grad_b [cout]: fp32 (the master weights of the other fp16 operators).
+ *   y[r, o]      = fp16( sum_k x[r, k] h(w[o, k]) + bias[o] + residual[r, o] )    bias, residual: optional (NULL)
+ *   grad_x[r, k] = fp16( sum_o grad_y[r, o] h(w[o, k]) )                          optional (NULL: w is not read)
+ *   grad_w[o, k] = sum_r grad_y[r, o] x[r, k]        grad_b[o] = sum_r grad_y[r, o]   (grad_b optional)
+ * h rounds a weight to fp16 (to nearest-even) once, when a workgroup stages its bank; products are exact in fp32, every sum is
+ * accumulated in fp32, bias and residual are added in fp32 and the result is rounded ONCE on store, as a conversion rounds: beyond
+ * the fp16 range to +-inf, no clamping.  The gradient with respect to the residual is grad_y itself.  The row sums of grad_w and
+ * grad_b go through one fp32 slab per 512 rows in `workspace` and are summed in slab order: no float atomics, every output bitwise
+ * the same run to run.  A row never meets another row's values (a NaN in one row of x stays in that row of y), and rows from `rows`
+ * on are never read.
+ * Forms (csrc/ln_linear_f16_plan.h): cin and cout multiples of 16 up to 256 with x / w / residual / y (grad_y / w / grad_x; x / grad_y)
+ * 8-byte aligned run on v_mfma_f32_16x16x32_f16 (the 16x16x16 form where the contraction length is no multiple of 32); any other
+ * shape or alignment on one thread per output element, the weight gradient on one thread per (o, k) pair of a chunk.
+ * rows == 0 is legal: nothing is read, grad_w and grad_b are written as zeros, the workspace is neither needed nor touched.
+ * Refused, with nothing launched and nothing written: rows < 0, cin < 1, cout < 1, a null x / w / y (forward, rows > 0), a null
+ * grad_w, a null x / grad_y (rows > 0), a null w with grad_x wanted (LN_ERR_ARG); a workspace that is null or smaller than
+ * ln_linear_backward_f16_workspace_bytes(rows, cin, cout) at rows > 0 (LN_ERR_WORKSPACE); more output elements or (o, k) pairs
+ * than one launch of the element-wise forms reaches (LN_ERR_UNSUPPORTED). */
+int ln_linear_forward_f16(const void* x_f16, const float* w, const float* bias, const void* residual_f16, int rows, int cin, int cout,
+                          void* y_f16, void* stream);
+size_t ln_linear_backward_f16_workspace_bytes(int rows, int cin, int cout);
+int ln_linear_backward_f16(const void* x_f16, const void* grad_y_f16, const float* w, int rows, int cin, int cout, void* grad_x_f16,
+                           float* grad_w, float* grad_b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- launch diet of the glue around the lattice operators in a training step ----------------------------------------------
  * Weight normalisation of the reference's weight_norm_wrapper with v_dim=None (latticenet_py/lattice/utils.py:72-158; LinearWN,
  * ConvLatticeIm2RowWN, CoarsenLatticeWN, FinefyLatticeWN):  w = v * g / ||v||_F  for v [rows, cols] and one magnitude per row

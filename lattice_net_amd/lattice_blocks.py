@@ -401,6 +401,8 @@ class Conv1x1(torch.nn.Module):  # mods:788-804 (the linear layer is created fro
     def forward(self, lv):
         if self.linear is None:
             self._make(lv.shape[1])
+        if lv.is_cuda and lv.dtype == torch.float16 and self.linear.weight.dtype == torch.float32:
+            return linear_leaky_relu(lv, self.linear.weight, self.linear.bias, -1.0)  # float16 rows, float32 master weights: the fp16 GEMM
         return self.linear(lv)
 
 
@@ -460,9 +462,13 @@ class _Pre1x1(_PreActBlock):
         self.linear = torch.nn.Linear(in_channels, out_channels, bias=bias).to(device)
         torch.nn.init.kaiming_normal_(self.linear.weight, mode="fan_in", nonlinearity="relu")
 
-    def forward(self, lv, ls):
+    def forward(self, lv, ls, residual=None):
+        """`residual` (float16 values only): a row added in the linear layer's epilogue, in fp32, before its one rounding"""
         lv, ls = self._pre(lv, ls)
-        lv = linear_leaky_relu(lv, self.linear.weight, self.linear.bias, -1.0)  # plain per-vertex linear on the streaming kernels
+        if residual is None:
+            lv = linear_leaky_relu(lv, self.linear.weight, self.linear.bias, -1.0)  # plain per-vertex linear on the streaming kernels
+        else:
+            lv = linear_leaky_relu(lv, self.linear.weight, self.linear.bias, -1.0, residual=residual)
         ls.set_values(lv)
         return lv, ls
 
@@ -634,6 +640,9 @@ class BottleneckBlock(torch.nn.Module):  # mods:1336-1361: 1x1 contract (C/4) ->
         identity = lv
         lv, ls = self.contract(lv, ls)
         lv, ls = self.conv(lv, ls)
+        if identity.is_cuda and identity.dtype == torch.float16 and self.expand.linear.weight.dtype == torch.float32:
+            lv, ls = self.expand(lv, ls, residual=identity)  # `+ identity` in the fp16 GEMM's epilogue: one rounding, no extra pass
+            return lv, ls
         lv, ls = self.expand(lv, ls)
         lv = lv + identity
         ls.set_values(lv)

@@ -208,10 +208,60 @@ class LinearMfmaFunction(torch.autograd.Function):
         return gx, gw
 
 
-def linear_leaky_relu(x, weight, bias, slope: float):
-    """LeakyReLU(linear(x)) (slope < 0: plain linear) for [rows, channels] inputs.  Bias-free plain layers whose widths the
-    convolution's MFMA tiles cover run as a 1x1 lattice convolution; other float32 CUDA rows with <= 128 channels take the
-    streaming kernels; everything else goes through torch."""
+class LinearF16Function(torch.autograd.Function):
+    """y = x @ h(w)^T + bias + residual for a per-vertex 1x1 layer on float16 rows with float32 master weights (csrc/ln_linear_f16.hip:
+    a dense GEMM on the fp16 matrix instructions, fp32 accumulation, bias and residual added in fp32, one rounding on store).  y and
+    grad_x are float16, grad_w and grad_b float32, the gradient of the residual is grad_y itself.  Eager only, as the float16
+    GroupNorm is: the call allocates its output and its workspace."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, residual):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the float16 linear layer has no route into a stream capture: run float16 lattice values eagerly")
+        lib = _lib.load()
+        x, w = x.contiguous(), w.contiguous()
+        rows, cin = x.shape
+        cout = w.shape[0]
+        if w.shape[1] != cin or w.dtype != torch.float32 or (bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout)):
+            raise ValueError("the float16 linear layer takes float32 weights [cout, cin] and a float32 bias [cout]")
+        if residual is not None:
+            if residual.dtype != torch.float16 or tuple(residual.shape) != (rows, cout):
+                raise ValueError("the residual of the float16 linear layer is a float16 tensor of the output's shape")
+            residual = residual.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        y = torch.empty((rows, cout), dtype=torch.float16, device=x.device)
+        _lib.check(lib.ln_linear_forward_f16(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(residual), rows, cin, cout, _lib.ptr(y),
+                                             _lib.stream_ptr(x.device)), "ln_linear_forward_f16")
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        lib = _lib.load()
+        x, w = ctx.saved_tensors
+        grad_y = grad_y.contiguous()
+        rows, cin = x.shape
+        cout = w.shape[0]
+        dev = x.device
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gw = torch.empty_like(w)
+        gb = torch.empty((cout,), dtype=torch.float32, device=dev) if ctx.has_bias else None
+        ws = torch.empty((lib.ln_linear_backward_f16_workspace_bytes(rows, cin, cout),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.ln_linear_backward_f16(_lib.ptr(x), _lib.ptr(grad_y), _lib.ptr(w), rows, cin, cout, _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb),
+                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "ln_linear_backward_f16")
+        return gx, gw, gb, (grad_y if ctx.needs_input_grad[3] else None)
+
+
+def linear_leaky_relu(x, weight, bias, slope: float, residual=None):
+    """LeakyReLU(linear(x)) (slope < 0: plain linear) for [rows, channels] inputs.  Plain layers on float16 CUDA rows with float32
+    weights take the fp16 GEMM (LinearF16Function; `residual`, float16 [rows, cout], is added in its epilogue and accepted there only).
+    Bias-free plain layers whose widths the convolution's MFMA tiles cover run as a 1x1 lattice convolution; other float32 CUDA rows
+    with <= 128 channels take the streaming kernels; everything else goes through torch."""
+    if x.is_cuda and x.dtype == torch.float16 and x.dim() == 2 and x.shape[0] > 0 and weight.dtype == torch.float32 and slope < 0:
+        return LinearF16Function.apply(x, weight, bias, residual)
+    if residual is not None:
+        raise ValueError("linear_leaky_relu: a residual is fused only into the plain layer on float16 CUDA rows with float32 weights")
     cin, cout = x.shape[1], weight.shape[0]
     gpu_rows = x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0
     if gpu_rows and bias is None and slope < 0 and cin in _MFMA_LINEAR_WIDTHS and cout in _MFMA_LINEAR_WIDTHS and x.shape[0] >= 64:
