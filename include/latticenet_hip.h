@@ -430,6 +430,33 @@ int ln_slice_forward_f16(const void* values_f16, const int* idx, const float* w,
 int ln_slice_forward_f16_prepare_backward(const void* values_f16, const int* idx, const float* w, int n, int pos_dim, int val_dim, void* out_f16,
                                           float* grad_accumulator, long long grad_accumulator_elems, void* stream);
 
+/* DeformSlice head on fp16 lattice values (csrc/ln_classify_f16.hip).  `values_f16` is IEEE fp16 (`_Float16`) [M, val_dim], widened on
+ * load; every other operand, every output and every accumulator is fp32.  Each call gives, bit for bit, what its fp32 namesake gives
+ * on the same values widened to fp32 (same tiles, grids, slab layout and order of operations).
+ *
+ * ln_gather_forward_f16: out[n, (d+1)(V+1)] fp32, fully written, laid out as by ln_gather_forward.  Any val_dim >= 1, no alignment
+ * asked for.  (The gather backward stays ln_gather_backward / the fp32 segment reduce of the fp32 grad_gathered.) */
+int ln_gather_forward_f16(const void* values_f16, const int* idx, const float* w, int n, int pos_dim, int val_dim, float* out, void* stream);
+/* ln_slice_classify_forward_f16: arguments of ln_slice_classify_forward.  Covers exactly the shapes at which that call takes its
+ * wave-tiled form (val_dim % 32 == 0, nr_classes <= 32, nr_classes * val_dim <= 4096, pos_dim in {2, 3}) or a 4-channel form
+ * (val_dim % 4 == 0 and a tile of 64 / 32 / 16 points within 64 KiB of LDS), with `values_f16` 8-byte aligned.  Any other shape
+ * (val_dim % 4 != 0 among them) and a misaligned `values_f16` are LN_ERR_UNSUPPORTED, the message names V, C and d, nothing is
+ * written.  n == 0 returns LN_OK. */
+int ln_slice_classify_forward_f16(const void* values_f16, const float* delta_w, const float* lin_w, const float* lin_b, const int* idx,
+                                  const float* w, int n, int pos_dim, int val_dim, int nr_classes, float* logits, void* stream);
+/* ln_slice_classify_backward_f16: arguments and accumulate-into semantics of ln_slice_classify_backward (g_delta_w, g_lin_w, g_lin_b are
+ * added to; grad_sliced[n, V] and w_eff[n (d+1)] are written), all fp32.  `g_values` must be NULL (LN_ERR_ARG): the value gradient is the
+ * segment reduce of grad_sliced with w_eff (ln_csr_reduce_rows into an fp32 [M, V] buffer).  Covers exactly the shapes at which the fp32
+ * call takes its wave-tiled form (val_dim % 32 == 0, val_dim <= 128, nr_classes <= 32, pos_dim in {2, 3}) or its 4-channel form
+ * (val_dim % 4 == 0, 4 ceil(C / 4) * val_dim <= 12288, a tile of 64 .. 8 points within 64 KiB of LDS), with `values_f16` 8-byte and
+ * grad_sliced 16-byte aligned; any other shape or alignment is LN_ERR_UNSUPPORTED (V, C and d named, nothing written), a workspace below
+ * ln_slice_classify_backward_f16_workspace_bytes LN_ERR_WORKSPACE.  The workspace size is that of the fp32 call. */
+size_t ln_slice_classify_backward_f16_workspace_bytes(int n, int pos_dim, int val_dim, int nr_classes);
+int ln_slice_classify_backward_f16(const float* grad_logits, const void* values_f16, const float* delta_w, const float* lin_w,
+                                   const int* idx, const float* w, int n, int pos_dim, int val_dim, int nr_classes, float* g_values,
+                                   float* g_delta_w, float* g_lin_w, float* g_lin_b, float* grad_sliced, float* w_eff, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* Half-precision feature path of the convolution (BASELINE.json config 5 / SURVEY.md 8d C5: features fp16, accumulate
  * fp32).  Same arguments and flags as ln_conv_forward / ln_conv_grad_filter; values, filter bank, grad_out and out are
  * IEEE fp16 (`_Float16`), accumulation is fp32 (v_mfma_f32_16x16x16_f16 for val_dim in {16,32,64,96,128,256} and

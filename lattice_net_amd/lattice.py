@@ -1497,6 +1497,23 @@ class Lattice:
         return coarse
 
     # ---------------------------------------------------------------- slice family
+    def _head_values_are_f16(self, values, what, needs_v4=True):
+        """Dtype gate of the DeformSlice head (gather, slice-classify): False for float32 values, True for float16 ones that the
+        float16 entry points take; raises for anything else instead of letting a float kernel read it."""
+        if values.dtype == torch.float32:
+            return False
+        if values.dtype != torch.float16:
+            raise ValueError(f"{what} takes float32 or float16 lattice values, not {values.dtype}")
+        if not values.is_contiguous():
+            raise ValueError(f"{what} takes contiguous lattice values")
+        if needs_v4 and values.shape[1] % 4 != 0:
+            raise ValueError(f"{what} on float16 lattice values needs val_dim % 4 == 0 (got {values.shape[1]})")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"the float16 {what} has no route into a stream capture: run float16 lattice values eagerly")
+        if self.m_hash_table._static_rows is not None:
+            raise RuntimeError(f"the float16 {what} has no route under set_static_rows: run float16 lattice values eagerly")
+        return True
+
     def _check_slice_inputs(self, positions_raw, idx, w):
         self._check_positions(positions_raw)
         if self.val_dim() <= 0:
@@ -1568,10 +1585,13 @@ class Lattice:
         idx, w = splatting_indices_tensor.contiguous(), splatting_weights_tensor.contiguous()
         n = self._check_slice_inputs(positions_raw, idx, w)
         d, v = self.pos_dim(), self.val_dim()
+        vals = self.values()
+        half = self._head_values_are_f16(vals, "gather", needs_v4=False)
         out = torch.empty((n, (d + 1) * (v + 1)), dtype=torch.float32, device=self._dev())
         lib = _lib.load()
-        _lib.check(lib.ln_gather_forward(_lib.ptr(self.values()), _lib.ptr(idx), _lib.ptr(w), n, d, v, _lib.ptr(out), self._stream()),
-                   "ln_gather_forward")
+        fn, what = (lib.ln_gather_forward_f16, "ln_gather_forward_f16") if half else (lib.ln_gather_forward, "ln_gather_forward")
+        # (fp16 values: the gathered rows are fp32 — from here on the head runs on the point side in fp32)
+        _lib.check(fn(_lib.ptr(vals), _lib.ptr(idx), _lib.ptr(w), n, d, v, _lib.ptr(out), self._stream()), what)
         return out
 
     def gather_standalone_no_precomputation(self, positions_raw):  # Lattice.cu:835-876 (kernel cannot compile in the reference)
@@ -1588,11 +1608,14 @@ class Lattice:
         idx, w = splatting_indices_tensor.contiguous(), splatting_weights_tensor.contiguous()
         n = self._check_slice_inputs(positions_raw, idx, w)
         dw, lw, lb = delta_weights.contiguous(), linear_clasify_weight.contiguous(), linear_clasify_bias.contiguous()
+        vals = self.values()
+        half = self._head_values_are_f16(vals, "slice-classify")
         logits = torch.empty((n, nr_classes), dtype=torch.float32, device=self._dev())
         lib = _lib.load()
-        _lib.check(lib.ln_slice_classify_forward(_lib.ptr(self.values()), _lib.ptr(dw), _lib.ptr(lw), _lib.ptr(lb), _lib.ptr(idx),
-                                                 _lib.ptr(w), n, self.pos_dim(), self.val_dim(), int(nr_classes), _lib.ptr(logits),
-                                                 self._stream()), "ln_slice_classify_forward")
+        fn, what = (lib.ln_slice_classify_forward_f16, "ln_slice_classify_forward_f16") if half else \
+            (lib.ln_slice_classify_forward, "ln_slice_classify_forward")
+        _lib.check(fn(_lib.ptr(vals), _lib.ptr(dw), _lib.ptr(lw), _lib.ptr(lb), _lib.ptr(idx), _lib.ptr(w), n, self.pos_dim(), self.val_dim(),
+                      int(nr_classes), _lib.ptr(logits), self._stream()), what)
         return logits
 
     def slice_backwards_standalone_with_precomputation_no_homogeneous(self, positions_raw, grad_sliced_values, splatting_indices_tensor,
@@ -1623,20 +1646,24 @@ class Lattice:
                         ("grad_linear_clasify_weight", grad_linear_clasify_weight), ("grad_linear_clasify_bias", grad_linear_clasify_bias)):
             if not g.is_contiguous():
                 raise ValueError(f"{name} must be contiguous (it is filled in place)")
+        half = self._head_values_are_f16(initial_values, "slice-classify")
+        if half and grad_lattice_values.dtype != torch.float32:  # (the segment reduce accumulates in fp32)
+            raise ValueError("grad_lattice_values must be float32 (float16 lattice values: round the accumulated gradient afterwards)")
         iv, dw, lw = initial_values.contiguous(), delta_weights.contiguous(), linear_clasify_weight.contiguous()
         lib = _lib.load()
         v, c, d = int(iv.shape[1]), int(nr_classes), self.pos_dim()
         dev = self._dev()
         grad_sliced = torch.empty((n, v), dtype=torch.float32, device=dev)
         w_eff = torch.empty((n * (d + 1),), dtype=torch.float32, device=dev)
-        ws = self._workspace(lib.ln_slice_classify_backward_workspace_bytes(n, d, v, c))
+        size_fn, fn, what = (lib.ln_slice_classify_backward_f16_workspace_bytes, lib.ln_slice_classify_backward_f16,
+                             "ln_slice_classify_backward_f16") if half else \
+            (lib.ln_slice_classify_backward_workspace_bytes, lib.ln_slice_classify_backward, "ln_slice_classify_backward")
+        ws = self._workspace(size_fn(n, d, v, c))
         # classifier / delta-weight gradients + dL/d(sliced features); the lattice-value gradient is then the same
         # CSR segment reduce as every other scatter onto the vertices (no N(d+1)V atomics, LG:3714-3719)
-        _lib.check(lib.ln_slice_classify_backward(_lib.ptr(grad_class_logits), _lib.ptr(iv), _lib.ptr(dw), _lib.ptr(lw), _lib.ptr(idx),
-                                                  _lib.ptr(w), n, d, v, c, None, _lib.ptr(grad_delta_weights),
-                                                  _lib.ptr(grad_linear_clasify_weight), _lib.ptr(grad_linear_clasify_bias),
-                                                  _lib.ptr(grad_sliced), _lib.ptr(w_eff), _lib.ptr(ws), ws.numel(), self._stream()),
-                   "ln_slice_classify_backward")
+        _lib.check(fn(_lib.ptr(grad_class_logits), _lib.ptr(iv), _lib.ptr(dw), _lib.ptr(lw), _lib.ptr(idx), _lib.ptr(w), n, d, v, c, None,
+                      _lib.ptr(grad_delta_weights), _lib.ptr(grad_linear_clasify_weight), _lib.ptr(grad_linear_clasify_bias),
+                      _lib.ptr(grad_sliced), _lib.ptr(w_eff), _lib.ptr(ws), ws.numel(), self._stream()), what)
         self._scatter_rows(grad_sliced, idx, w_eff, grad_lattice_values, v, d + 1, v)
 
     def gather_backwards_standalone_with_precomputation(self, positions_raw, grad_sliced_values, splatting_indices_tensor,

@@ -286,7 +286,9 @@ class SliceClassifyLattice(Function):  # lattice_funcs.py:518-567
         positions, initial_values, delta_weights, linear_clasify_weight, linear_clasify_bias, splatting_indices, splatting_weights = \
             ctx.saved_tensors
         lattice_py = ctx.lattice_structure
-        grad_lattice_values = torch.zeros_like(initial_values)
+        half = initial_values.dtype == torch.float16  # accumulated in an fp32 [M, V] buffer, the sum rounded once
+        grad_lattice_values = torch.zeros(initial_values.shape, dtype=torch.float32, device=initial_values.device) if half else \
+            torch.zeros_like(initial_values)
         grad_delta_weights = torch.zeros_like(delta_weights)
         grad_linear_clasify_weight = torch.zeros_like(linear_clasify_weight)
         grad_linear_clasify_bias = torch.zeros_like(linear_clasify_bias)
@@ -295,6 +297,8 @@ class SliceClassifyLattice(Function):  # lattice_funcs.py:518-567
                                                                 grad_lattice_values, grad_delta_weights, grad_linear_clasify_weight,
                                                                 grad_linear_clasify_bias, splatting_indices, splatting_weights)
         ctx.lattice_structure = 0
+        if half:
+            grad_lattice_values = grad_lattice_values.half()
         return grad_lattice_values, None, None, grad_delta_weights, grad_linear_clasify_weight, grad_linear_clasify_bias, None, None, None
 
 
@@ -306,6 +310,7 @@ class GatherLattice(Function):  # lattice_funcs.py:569-603
         ctx.save_for_backward(positions, splatting_indices, splatting_weights)
         ctx.lattice_structure = lattice_structure
         ctx.val_dim = lattice_values.shape[1]
+        ctx.values_dtype = lattice_values.dtype
         return gathered_values
 
     @staticmethod
@@ -315,5 +320,7 @@ class GatherLattice(Function):  # lattice_funcs.py:569-603
         lattice_py.gather_backwards_standalone_with_precomputation(positions, grad_sliced_values.contiguous(), splatting_indices,
                                                                    splatting_weights)
         lattice_values = lattice_py.values()
+        if ctx.values_dtype == torch.float16:
+            lattice_values = lattice_values.half()  # accumulated in fp32, rounded once
         ctx.lattice_structure = 0
         return lattice_values, None, None, None, None
