@@ -45,6 +45,12 @@ def scatter64(src, idx, w, rows, src_div=4):
     return ref, mag
 
 
+def rounded_sum_limit(ref, mag):
+    """The bound of an fp32 sum of terms returned in fp16: the plain bound of the sum (close_terms: 1e-5 * sum |terms|) plus its one
+    rounding, half an fp16 ulp — 2^-11 |ref|, 2^-25 below the normal range."""
+    return 1e-5 * mag + np.maximum(2.0 ** -11 * np.abs(ref), 2.0 ** -25)
+
+
 def lidar(n, seed=3):
     from lattice_net_amd.synthetic import lidar_cloud
     return np.ascontiguousarray(lidar_cloud(n, seed), dtype=np.float32)
@@ -96,7 +102,7 @@ def splat_and_slice_backward(pos_np, v, dtype, seed, builds=1):
     got = N(values.grad.float())
     if dtype == torch.float16:  # the fp32 sum rounded to fp16 once
         err = np.abs(got - gref)
-        lim = 1e-5 * gmag + np.maximum(2.0 ** -11 * np.abs(gref), 2.0 ** -25)
+        lim = rounded_sum_limit(gref, gmag)
         assert np.all(err <= lim), float(np.max(err - lim))
     else:
         close_terms(got, gref, gmag)
